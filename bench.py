@@ -13,7 +13,13 @@ its own copy of the frame (weak scaling with identical work per GPU) and the ren
 is not already running under it, so both ``python bench.py --gpus 8`` and
 ``python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8`` work.
 
-Prints ONE JSON line (rank 0).  ``roofline`` is for the dominant kernel (the fused fp32-MFMA MLP,
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times ``--steps`` steps and prints the headline line; every
+secondary figure below (roofline, precision tiers, legs, baselines, clock telemetry) is measured only with ``--full``.
+``--dump-outputs DIR`` writes what the last timed step returned as ``DIR/<name>.npy`` (float32 / float64, finite: NaN / inf
+entries are 0 there and coded in ``DIR/<name>.nonfinite.npy``; a seeded sample of the larger tensors, at most 64 MB in all) with
+``DIR/manifest.json``, so that two builds can be compared output for output.
+
+``roofline`` (``--full``) is for the dominant kernel (the fused fp32-MFMA MLP,
 ``k_mlp_mfma_group`` - the tile loop of ``k_mlp_mfma``, one launch per model type for its four objects): FLOPs per launch /
 average launch duration measured with HIP events on the launch stream.  Two FLOP counts are given: ``algorithmic`` (in-box samples x FLOP/sample of the
 object's networks - what the reference evaluates) and ``executed`` (minus the feature-head FLOPs of the
@@ -46,6 +52,7 @@ SCENE_KEYS = ("camera_rotations", "camera_translations", "focals", "object_rotat
 
 
 LINE_BUDGET = 4096      # bytes of the ONE stdout line (r04's 22.6 KB line was not parsed by the driver; everything else -> bench_full.json)
+DUMP_BUDGET = 60_000_000    # bytes of array data written by --dump-outputs (64 MB at most with the .npy headers and the manifest)
 
 
 def _dig(d, *path, default=None):
@@ -157,6 +164,64 @@ def emit(result: dict, full_path: str) -> None:
             print(f"bench.py: could not write {path}: {e}", file=sys.stderr)
     sys.stderr.flush()
     print(compact_line(result, os.path.relpath(written, ROOT) if written else None), flush=True)
+
+
+def output_tensors(tree, prefix=""):
+    """(dotted name, tensor) for every tensor of a nested dict / list / tuple result."""
+    if torch.is_tensor(tree):
+        yield prefix, tree
+    elif isinstance(tree, dict):
+        for k, v in tree.items():
+            yield from output_tensors(v, f"{prefix}.{k}" if prefix else str(k))
+    elif isinstance(tree, (list, tuple)):
+        for i, v in enumerate(tree):
+            yield from output_tensors(v, f"{prefix}.{i}" if prefix else str(i))
+
+
+def dump_outputs(outputs, directory: str, budget: int = DUMP_BUDGET) -> dict:
+    """Every tensor of `outputs` -> `directory`/<name>.npy: float64 stays float64, integers and booleans become float64 (exact),
+    every other floating type float32.  Every file holds finite numbers only: a tensor with NaN / inf entries (the disparity of a
+    ray whose opacity is 0 is 0 / 0, as in the reference) is written with those entries as 0, and `directory`/<name>.nonfinite.npy
+    (float32, same elements) codes each element: 0 finite, 1 NaN, 2 +inf, 3 -inf.  The byte budget is shared out smallest first (a
+    tensor gets all of its elements or an equal share of what is left); a tensor over its share is written as the sorted flat
+    elements at seeded random positions (seed = crc32 of its name, so the sample is the same in every run and build).  The
+    manifest records shapes, samples and non-finite counts."""
+    import zlib
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    items = []
+    for name, t in output_tensors(outputs):
+        t = t.detach()
+        wide = t.dtype == torch.float64 or not t.is_floating_point()
+        dtype = torch.float64 if wide else torch.float32
+        finite = bool(torch.isfinite(t).all())
+        items.append((name.replace(os.sep, "_"), t, dtype, finite, dtype.itemsize + (0 if finite else 4)))
+    items.sort(key=lambda it: (it[1].numel() * it[4], it[0]))
+    left, manifest = budget, {}
+    for i, (name, t, dtype, finite, cost) in enumerate(items):
+        n = t.numel()
+        take = min(n, int(left / (len(items) - i)) // cost)
+        entry = {"shape": list(t.shape), "dtype": str(t.dtype).replace("torch.", ""), "saved_as": str(dtype).replace("torch.", "")}
+        if take < n:
+            seed = zlib.crc32(name.encode())
+            idx = torch.unique(torch.randint(0, n, (take,), generator=torch.Generator().manual_seed(seed)))
+            t = t.reshape(-1).index_select(0, idx.to(t.device))
+            entry.update(sampled_elements=int(idx.numel()), sample_seed=seed, sample_draws=take,
+                         sample="flat elements at torch.unique(torch.randint(0, numel, (sample_draws,), "
+                                "generator=torch.Generator().manual_seed(sample_seed)))")
+        values = t.to(dtype).cpu().numpy()
+        if not finite:
+            codes = np.select([np.isnan(values), values == np.inf, values == -np.inf], [1, 2, 3], 0).astype(np.float32)
+            values = np.where(codes == 0, values, 0).astype(values.dtype)
+            np.save(os.path.join(directory, name + ".nonfinite.npy"), codes)
+            left -= codes.nbytes
+            entry.update(nonfinite_saved=int(np.count_nonzero(codes)), nonfinite_file=name + ".nonfinite.npy")
+        np.save(os.path.join(directory, name + ".npy"), values)
+        left -= values.nbytes
+        manifest[name] = entry
+    with open(os.path.join(directory, "manifest.json"), "w") as f:
+        json.dump(manifest, f, indent=1)
+    return manifest
 
 
 def flops_per_sample(model_cfg: dict, head_only: bool = False) -> float:
@@ -979,7 +1044,16 @@ def main():
                     help="torch threads of the main CPU baseline run (all 256 host cores are >50x SLOWER on these small ops)")
     ap.add_argument("--full-json", default=os.path.join(ROOT, "bench_full.json"),
                     help="where the FULL record (every leg, note and table) is written; stdout carries one compact line < 4 KB")
+    ap.add_argument("--full", action="store_true",
+                    help="measure every secondary figure as well (roofline, precision tiers, legs, baselines, telemetry; the --no-* "
+                         "switches select among them); a plain run times the headline steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float32 / float64, <= 64 MB, seeded samples "
+                         "of the larger tensors; NaN / inf entries written as 0 and coded in DIR/<name>.nonfinite.npy) and "
+                         "DIR/manifest.json")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # self-launch: one process per GPU under torch.distributed.run, rendezvous on the loopback interface
@@ -1089,30 +1163,39 @@ def main():
             raise SystemExit(f"--only {args.only}: unknown leg")
         return
 
-    def timed(steps, warmup):
-        """warmup untimed steps, then exactly `steps` steps between barrier + synchronize; max over ranks."""
+    def timed(steps, warmup, profile=True, keep=False):
+        """warmup untimed steps, then exactly `steps` steps between barrier + synchronize; max over ranks.  `profile`: the
+        library's HIP-event timers on the dominant kernels during the timed steps (the roofline's kernel times).  `keep`: the
+        last step's result is left in ``timed.out`` (every other result is dropped when its step returns, as a caller would)."""
         for _ in range(warmup):
             step()
         drain()
         torch.cuda.synchronize()
         if multi:
             dist.barrier()
-        lib.pr_profile_enable(1)
+        if profile:
+            lib.pr_profile_enable(1)
         torch.cuda.synchronize()
         marks = [torch.cuda.Event(enable_timing=True) for _ in range(steps + 1)]
         t0 = time.perf_counter()
+        timed.out = None
         for i in range(steps):
             marks[i].record()
-            step()
+            out = step()
+            if keep and i == steps - 1:
+                timed.out = out
+            del out
         marks[steps].record()
         drain()                      # every gather of the timed steps completes inside the timed region
         torch.cuda.synchronize()
         if multi:
             dist.barrier()
         dt = time.perf_counter() - t0
-        lib.pr_profile_enable(0)
-        kernel_ms, kernel_launches = profile_arrays()
-        _lib.check(lib.pr_profile_collect(kernel_ms, kernel_launches), "pr_profile_collect")
+        kernel_ms = kernel_launches = None
+        if profile:
+            lib.pr_profile_enable(0)
+            kernel_ms, kernel_launches = profile_arrays()
+            _lib.check(lib.pr_profile_collect(kernel_ms, kernel_launches), "pr_profile_collect")
         dt = max_over_ranks(dt, dist, dev)
         timed.gaps = event_gaps_ms(marks)
         return dt, kernel_ms, kernel_launches
@@ -1120,7 +1203,7 @@ def main():
     # shader clock / package power during the timed regions (amdgpu sysfs, sampled by a thread of this process; one GPU only - the node
     # is found by the power rise of a matrix probe): says whether a measured region ran clock limited.  Never fails the run.
     telemetry = None
-    if world == 1 and not args.no_telemetry:
+    if args.full and world == 1 and not args.no_telemetry:
         try:
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import gpu_telemetry
@@ -1146,16 +1229,20 @@ def main():
         finally:
             telemetry.label = None
 
-    elapsed, ms, launches = watched("headline", lambda: timed(args.steps, args.warmup))
+    dump = bool(args.dump_outputs) and rank == 0
+    elapsed, ms, launches = watched("headline", lambda: timed(args.steps, args.warmup, profile=args.full, keep=dump))
     step_gaps = timed.gaps
+    if dump:
+        dump_outputs(timed.out, args.dump_outputs)
+        timed.out = None
     identical = None
-    if multi:
+    if multi and args.full:
         active["scene"] = to_device(synthetic.tennis_scene(seed=1234, image_size=size), dev)
         same_s, _, _ = timed(max(1, min(args.steps, 5)), 1)
         active["scene"] = scene_dev
         identical = same_s / max(1, min(args.steps, 5))
     split = half = None
-    if args.precision == "fp32" and not args.no_split_precision:
+    if args.full and args.precision == "fp32" and not args.no_split_precision:
         # secondary measurement, never the headline: the same step with the MLP on the split-precision
         # kernel (fp32 emulated with three fp16 MFMAs; same parity tolerance in tests/test_gpu.py)
         comp.precision = "f16x3"
@@ -1167,31 +1254,32 @@ def main():
         split = (split_s, split_ms[0] / max(1, args.steps))
         half = (half_s, half_ms[0] / max(1, args.steps))
 
-    # FLOPs of the MLP launches of one step (this rank's frame)
-    call_inputs = composer_call_inputs(model, cfg, scene_dev, size)
-    flops, executed, evaluated, head_samples = flop_counts(comp, cfg, call_inputs)
-
-    # HBM traffic of the dominant kernel from the committed PMC pass (collected separately: counters
-    # cannot ride along with the timed run), and the fp32 MFMA rate this box sustains
-    traffic = None
-    traffic_source = traffic_stamp = None
     sha = library_sha256()
-    for name in ("r06_pmc_summary.json", "r05_pmc_summary.json", "r04_pmc_summary.json", "r03_pmc_summary.json", "r02_pmc_summary.json"):
-        pmc_path = os.path.join(ROOT, "profiles", name)
-        if os.path.exists(pmc_path) and size == (256, 256):
-            with open(pmc_path) as f:
-                pmc = json.load(f)
-            if "k_mlp_mfma" not in pmc:        # (a summary of failed counter passes: keep looking)
-                continue
-            traffic = pmc["k_mlp_mfma"]["hbm_bytes_per_launch_avg"]
-            traffic_stamp = pmc.get("library_sha256")
-            traffic_source = "profiles/" + name
-            break
-    probe = {}
-    for name, rnd in (("constant_operands", 0), ("random_operands", 1)):
-        tf, pms = C.c_double(), C.c_double()
-        _lib.check(lib.pr_probe_mfma_f32(100000, rnd, C.byref(tf), C.byref(pms), None), "pr_probe_mfma_f32")
-        probe[name] = round(tf.value, 1)
+    if args.full:
+        # FLOPs of the MLP launches of one step (this rank's frame)
+        call_inputs = composer_call_inputs(model, cfg, scene_dev, size)
+        flops, executed, evaluated, head_samples = flop_counts(comp, cfg, call_inputs)
+
+        # HBM traffic of the dominant kernel from the committed PMC pass (collected separately: counters
+        # cannot ride along with the timed run), and the fp32 MFMA rate this box sustains
+        traffic = None
+        traffic_source = traffic_stamp = None
+        for name in ("r06_pmc_summary.json", "r05_pmc_summary.json", "r04_pmc_summary.json", "r03_pmc_summary.json", "r02_pmc_summary.json"):
+            pmc_path = os.path.join(ROOT, "profiles", name)
+            if os.path.exists(pmc_path) and size == (256, 256):
+                with open(pmc_path) as f:
+                    pmc = json.load(f)
+                if "k_mlp_mfma" not in pmc:        # (a summary of failed counter passes: keep looking)
+                    continue
+                traffic = pmc["k_mlp_mfma"]["hbm_bytes_per_launch_avg"]
+                traffic_stamp = pmc.get("library_sha256")
+                traffic_source = "profiles/" + name
+                break
+        probe = {}
+        for name, rnd in (("constant_operands", 0), ("random_operands", 1)):
+            tf, pms = C.c_double(), C.c_double()
+            _lib.check(lib.pr_probe_mfma_f32(100000, rnd, C.byref(tf), C.byref(pms), None), "pr_probe_mfma_f32")
+            probe[name] = round(tf.value, 1)
 
     distributed = {"world_size": (dist.get_world_size() if multi else 1), "backend": backend,
                    "launched_by": "torch.distributed.run" if world > 1 else ("single process, process group forced" if multi else "single process")}
@@ -1213,8 +1301,6 @@ def main():
     rays_per_gpu = size[0] * size[1]
     total_rays = rays_per_gpu * world * args.steps
     value = total_rays / elapsed / 1e6
-    mlp_ms = ms[0] / max(1, args.steps)
-    achieved = executed / (mlp_ms * 1e-3) / 1e12 if mlp_ms > 0 else 0.0
     result = {
         "metric": "Mrays/s",
         "value": round(value, 4),
@@ -1241,7 +1327,11 @@ def main():
         "frames_per_s_256x256": round(value * 1e6 / 65536.0, 3),
         "library_sha256": sha,
         "distributed": distributed,
-        "roofline": {
+    }
+    if args.full:
+        mlp_ms = ms[0] / max(1, args.steps)
+        achieved = executed / (mlp_ms * 1e-3) / 1e12 if mlp_ms > 0 else 0.0
+        result["roofline"] = {
             "bound": "mfma",
             "kernel": "k_mlp_mfma_group (fused fp32 MFMA MLP; one launch per model type evaluates its four objects; all launches of one step)",
             "achieved": round(achieved, 2),
@@ -1265,8 +1355,7 @@ def main():
             "evaluated_samples": evaluated,
             "feature_head_samples": head_samples,
             "sigma_gate": bool(comp.gate_feature_head),
-        },
-    }
+        }
 
     clocks = {}
     if telemetry is not None:
@@ -1279,10 +1368,12 @@ def main():
                                                 "(DESIGN.md 11.3)")
     if args.precision == "f16x3":
         result["dtype"] = "f16x3 (fp32 emulated with three fp16 MFMAs, fp32 accumulate)"
-        result["roofline"]["kernel"] = "k_mlp_split (fused split-precision MFMA MLP); achieved/peak are in fp32-equivalent FLOPs"
+        if args.full:
+            result["roofline"]["kernel"] = "k_mlp_split (fused split-precision MFMA MLP); achieved/peak are in fp32-equivalent FLOPs"
     if args.precision == "f16":
         result["dtype"] = "f16 (fp16 operands, fp32 accumulate: throughput tier, ~1e-3 relative error)"
-        result["roofline"]["kernel"] = "k_mlp_f16 (fused fp16 MFMA MLP); achieved is in executed FLOPs, peak is the fp32 pipe's"
+        if args.full:
+            result["roofline"]["kernel"] = "k_mlp_f16 (fused fp16 MFMA MLP); achieved is in executed FLOPs, peak is the fp32 pipe's"
     if split is not None:
         result["split_precision"] = {
             "value": round(rays_per_gpu * world * args.steps / split[0] / 1e6, 4),
@@ -1312,65 +1403,66 @@ def main():
             "value": round(rays_per_gpu * world / identical / 1e6, 4), "unit": "Mrays/s", "ms_per_step": round(identical * 1e3, 3),
             "note": "secondary: every rank renders the SAME frame (seed 1234) - exactly the same work per GPU; the headline's ranks "
                     "render distinct frames"}
-    final_feats = None
-    if multi:
-        final_feats = step()["fine"]["global"]["integrated_features"]
-        drain()
-    result["feature_gather"] = feature_gather_leg(final_feats, dist, world, rank, dev)
-    del final_feats
-    if world == 1 and not args.no_shard_balance:
-        result["shard_balance"] = {
-            "what": "the 8 virtual shards of ONE 256x256 frame rendered one after the other on this GPU (composer calls), contiguous "
-                    "ranges of the pixel list vs 8x8 tiles dealt round robin (render_sharded shard='rays' / 'tiles'); a sharded frame "
-                    "takes as long as its slowest shard",
-            "tennis_hierarchical_64_128": shard_balance_leg(model, cfg, scene_dev, size),
-        }
-    if not args.no_distinct_frames:
-        steps_d = max(1, min(args.steps, 3))
-        result["distinct_frames"] = {
-            "hierarchical_64_128": distinct_frames_leg(model, cfg, "hierarchical 64+128, the headline networks", size, dev, world,
-                                                       rank, dist, steps_d, lib=lib),
-        }
-        shipped_cfg = configs.tennis_config()
-        torch.manual_seed(0)
-        shipped = EnvironmentModel(shipped_cfg)
-        synthetic.randomize_module_state(shipped.object_composer, seed=0, step=60000, alpha_bias=0.0, bender_scale=1e4)
-        shipped.eval().to(dev)
-        shipped.frame_replay = None
-        result["distinct_frames"]["shipped_p72"] = distinct_frames_leg(shipped, shipped_cfg, "shipped 4+4+32+32 positions - BASELINE.json "
-                                                                       "configs[3]", size, dev, world, rank, dist, max(steps_d, 3), lib=lib)
-        if "shard_balance" in result:
-            result["shard_balance"]["tennis_shipped"] = shard_balance_leg(
-                shipped, shipped_cfg, to_device(synthetic.tennis_scene(seed=1234, image_size=size), dev), size)
-        del shipped
-    if not args.no_train_step:
-        result["train_step"] = train_step_leg(args, dev, world, rank, dist, lib)
-        # the same step with precision="f16x3" (opt-in split precision: fp16-pair products in the training forward's phase 1, the
-        # backward chains and every weight gradient; fp32 accumulation, gradients at fp32 round-off) - beside the fp32 figure, never as it
-        split_train = train_step_leg(args, dev, world, rank, dist, lib, precision="f16x3")
-        result["train_step"]["f16x3"] = {
-            "ms_per_step": split_train["ms_per_step"], "ms_per_step_median": split_train["ms_per_step_median"], "value": split_train["value"],
-            "unit": split_train["unit"], "kernel_ms_per_step": split_train["roofline"]["kernel_ms_per_step"],
-            "note": "ObjectComposer.precision='f16x3' on a training call (PR_FLAG_SPLIT_BACKWARD): phase 1 of the forward and the backward "
-                    "chains on fp16 pairs (x = hi + lo, three v_mfma_f32_32x32x16_f16 per product, weights packed as w x 2^8, activation and gradient tiles "
-                    "scaled by a power of two per tile: k_mlp_mfma_train_group_split, k_chain_bwd_group_f16), the weight gradients on fp16 "
-                    "pairs of 16-row half slabs scaled by powers of two (k_gemm_tn_all_f16), fp32 accumulation everywhere; the head "
-                    "phases stay fp32.  Same gradient tests as fp32 "
-                    "(reference fixtures at 1e-4, oracle autograd, float64 arbitration at shipped sizes)"}
-        if world == 1:      # (a comparison leg: not repeated on every GPU count of a scaling run)
-            separate = train_step_leg(args, dev, world, rank, dist, lib, arena=False)
-            result["train_step"]["separate_parameter_tensors"] = {
-                "ms_per_step": separate["ms_per_step"], "ms_per_step_median": separate["ms_per_step_median"],
-                "note": "the same step with torch's fused Adam on the separate parameter tensors (a multi-tensor sweep: ~0.25 ms of 38-workgroup launches)"}
-        result["train_step_with_decoder"] = train_step_with_decoder_leg(args, dev, world, rank, dist, result["train_step"]["ms_per_step"])
-    if rank == 0 and world == 1 and not args.no_native_frame:
-        result["native_eval_frame"] = native_eval_frame_leg(dev, lib)
-    if rank == 0 and world == 1 and not args.no_minecraft:
-        result["config2_minecraft_256"] = minecraft_leg(dev, lib, balance=not args.no_shard_balance)
-        if "shard_balance" in result and "shard_balance" in result["config2_minecraft_256"]:
-            result["shard_balance"]["minecraft_shipped"] = result["config2_minecraft_256"].pop("shard_balance")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        result.update(baseline_legs(args, cfg, comp, scene, size, dev, value))
+    if args.full:
+        final_feats = None
+        if multi:
+            final_feats = step()["fine"]["global"]["integrated_features"]
+            drain()
+        result["feature_gather"] = feature_gather_leg(final_feats, dist, world, rank, dev)
+        del final_feats
+        if world == 1 and not args.no_shard_balance:
+            result["shard_balance"] = {
+                "what": "the 8 virtual shards of ONE 256x256 frame rendered one after the other on this GPU (composer calls), contiguous "
+                        "ranges of the pixel list vs 8x8 tiles dealt round robin (render_sharded shard='rays' / 'tiles'); a sharded frame "
+                        "takes as long as its slowest shard",
+                "tennis_hierarchical_64_128": shard_balance_leg(model, cfg, scene_dev, size),
+            }
+        if not args.no_distinct_frames:
+            steps_d = max(1, min(args.steps, 3))
+            result["distinct_frames"] = {
+                "hierarchical_64_128": distinct_frames_leg(model, cfg, "hierarchical 64+128, the headline networks", size, dev, world,
+                                                           rank, dist, steps_d, lib=lib),
+            }
+            shipped_cfg = configs.tennis_config()
+            torch.manual_seed(0)
+            shipped = EnvironmentModel(shipped_cfg)
+            synthetic.randomize_module_state(shipped.object_composer, seed=0, step=60000, alpha_bias=0.0, bender_scale=1e4)
+            shipped.eval().to(dev)
+            shipped.frame_replay = None
+            result["distinct_frames"]["shipped_p72"] = distinct_frames_leg(shipped, shipped_cfg, "shipped 4+4+32+32 positions - BASELINE.json "
+                                                                           "configs[3]", size, dev, world, rank, dist, max(steps_d, 3), lib=lib)
+            if "shard_balance" in result:
+                result["shard_balance"]["tennis_shipped"] = shard_balance_leg(
+                    shipped, shipped_cfg, to_device(synthetic.tennis_scene(seed=1234, image_size=size), dev), size)
+            del shipped
+        if not args.no_train_step:
+            result["train_step"] = train_step_leg(args, dev, world, rank, dist, lib)
+            # the same step with precision="f16x3" (opt-in split precision: fp16-pair products in the training forward's phase 1, the
+            # backward chains and every weight gradient; fp32 accumulation, gradients at fp32 round-off) - beside the fp32 figure, never as it
+            split_train = train_step_leg(args, dev, world, rank, dist, lib, precision="f16x3")
+            result["train_step"]["f16x3"] = {
+                "ms_per_step": split_train["ms_per_step"], "ms_per_step_median": split_train["ms_per_step_median"], "value": split_train["value"],
+                "unit": split_train["unit"], "kernel_ms_per_step": split_train["roofline"]["kernel_ms_per_step"],
+                "note": "ObjectComposer.precision='f16x3' on a training call (PR_FLAG_SPLIT_BACKWARD): phase 1 of the forward and the backward "
+                        "chains on fp16 pairs (x = hi + lo, three v_mfma_f32_32x32x16_f16 per product, weights packed as w x 2^8, activation and gradient tiles "
+                        "scaled by a power of two per tile: k_mlp_mfma_train_group_split, k_chain_bwd_group_f16), the weight gradients on fp16 "
+                        "pairs of 16-row half slabs scaled by powers of two (k_gemm_tn_all_f16), fp32 accumulation everywhere; the head "
+                        "phases stay fp32.  Same gradient tests as fp32 "
+                        "(reference fixtures at 1e-4, oracle autograd, float64 arbitration at shipped sizes)"}
+            if world == 1:      # (a comparison leg: not repeated on every GPU count of a scaling run)
+                separate = train_step_leg(args, dev, world, rank, dist, lib, arena=False)
+                result["train_step"]["separate_parameter_tensors"] = {
+                    "ms_per_step": separate["ms_per_step"], "ms_per_step_median": separate["ms_per_step_median"],
+                    "note": "the same step with torch's fused Adam on the separate parameter tensors (a multi-tensor sweep: ~0.25 ms of 38-workgroup launches)"}
+            result["train_step_with_decoder"] = train_step_with_decoder_leg(args, dev, world, rank, dist, result["train_step"]["ms_per_step"])
+        if rank == 0 and world == 1 and not args.no_native_frame:
+            result["native_eval_frame"] = native_eval_frame_leg(dev, lib)
+        if rank == 0 and world == 1 and not args.no_minecraft:
+            result["config2_minecraft_256"] = minecraft_leg(dev, lib, balance=not args.no_shard_balance)
+            if "shard_balance" in result and "shard_balance" in result["config2_minecraft_256"]:
+                result["shard_balance"]["minecraft_shipped"] = result["config2_minecraft_256"].pop("shard_balance")
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            result.update(baseline_legs(args, cfg, comp, scene, size, dev, value))
     graph_rate = _dig(result, "reference_graph_on_gpu", "value")
     if graph_rate:
         # north_star: ">= 10 x the reference PyTorch renderer's Mrays/s on one MI355X at matched PSNR" - every tier against the FASTEST chunk

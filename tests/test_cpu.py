@@ -1483,3 +1483,50 @@ def test_bench_line_is_compact_and_complete():
     bloated["distributed"] = dict(wide["distributed"], rank_devices=["d" * 300 for _ in range(8)])
     text = bench.compact_line(bloated)
     assert len(text.encode()) < bench.LINE_BUDGET and json.loads(text)["roofline"]["frac"] == full["roofline"]["frac"]
+
+
+def test_bench_dump_outputs_shares_its_budget_and_samples_by_seed(tmp_path):
+    """bench.dump_outputs (--dump-outputs): every tensor of a nested result as <dotted name>.npy in float32 / float64 (integers and
+    booleans exactly, as float64), within the byte budget - small tensors whole, a large one as the seeded sample the manifest
+    describes - and the same files from a second call."""
+    import importlib.util
+    import json
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.DUMP_BUDGET <= 64e6 - 1e6
+    g = torch.Generator().manual_seed(0)
+    result = {"fine": {"global": {"integrated_features": torch.randn((1, 1, 4096, 192), generator=g),
+                                  "opacity": torch.rand((1, 1, 4096, 1), generator=g).half()}},
+              "counts": torch.arange(-5, 1000, dtype=torch.int32), "mask": torch.rand(77, generator=g) > 0.5,
+              "depth": torch.randn(300, dtype=torch.float64, generator=g), "pair": [torch.ones(3), (torch.zeros(2, 2),)], "label": "not a tensor",
+              "disparity": torch.tensor([0.5, float("nan"), float("inf"), -float("inf"), 2.0]).half()}
+    budget = 400_000
+    dirs = [os.path.join(str(tmp_path), name) for name in ("a", "b")]
+    for d in dirs:
+        manifest = bench.dump_outputs(result, d, budget=budget)
+    assert sorted(manifest) == sorted(["fine.global.integrated_features", "fine.global.opacity", "counts", "mask", "depth", "pair.0",
+                                       "pair.1.0", "disparity"])
+    assert sorted(os.listdir(dirs[0])) == sorted([n + ".npy" for n in manifest] + ["disparity.nonfinite.npy", "manifest.json"])
+    with open(os.path.join(dirs[0], "manifest.json")) as f:
+        assert json.load(f) == manifest
+    arrays = {name: np.load(os.path.join(dirs[0], name + ".npy")) for name in manifest}
+    codes = np.load(os.path.join(dirs[0], "disparity.nonfinite.npy"))
+    assert sum(a.nbytes for a in arrays.values()) + codes.nbytes <= budget
+    assert all(np.isfinite(a).all() for a in arrays.values())         # NaN / inf: 0 in the values, coded beside them
+    assert codes.dtype == np.float32 and codes.tolist() == [0, 1, 2, 3, 0] and manifest["disparity"]["nonfinite_saved"] == 3
+    assert arrays["disparity"].dtype == np.float32 and arrays["disparity"].tolist() == [0.5, 0, 0, 0, 2.0]
+    assert "nonfinite_file" not in manifest["fine.global.integrated_features"]
+    for name in manifest:
+        assert np.array_equal(arrays[name], np.load(os.path.join(dirs[1], name + ".npy")))
+    assert arrays["counts"].dtype == np.float64 and np.array_equal(arrays["counts"], np.arange(-5, 1000))
+    assert arrays["mask"].dtype == np.float64 and np.array_equal(arrays["mask"], result["mask"].numpy().astype(np.float64))
+    assert arrays["depth"].dtype == np.float64 and np.array_equal(arrays["depth"], result["depth"].numpy())
+    assert arrays["fine.global.opacity"].dtype == np.float32 and arrays["fine.global.opacity"].shape == (1, 1, 4096, 1)
+    assert np.array_equal(arrays["pair.1.0"], np.zeros((2, 2), np.float32))
+    feats, entry = arrays["fine.global.integrated_features"], manifest["fine.global.integrated_features"]
+    assert entry["shape"] == [1, 1, 4096, 192] and entry["dtype"] == "float32" and "sampled_elements" in entry
+    idx = torch.unique(torch.randint(0, 4096 * 192, (entry["sample_draws"],), generator=torch.Generator().manual_seed(entry["sample_seed"])))
+    assert feats.dtype == np.float32 and feats.size == entry["sampled_elements"] == idx.numel() > 0.4 * budget / 4
+    assert np.array_equal(feats, result["fine"]["global"]["integrated_features"].reshape(-1)[idx].numpy())

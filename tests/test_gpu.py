@@ -3069,7 +3069,9 @@ def _run_bench(argv, env, tmp_path):
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline", "distributed", "full"):
         assert key in line, key
-    assert line["roofline"]["bound"] == "mfma" and line["roofline"]["frac"] > 0 and "workload" in line["config"]
+    assert "workload" in line["config"]
+    if "--full" in argv:       # (a plain run measures the headline alone: its roofline block is empty)
+        assert line["roofline"]["bound"] == "mfma" and line["roofline"]["frac"] > 0
     with open(full_path) as f:
         full = json.load(f)
     assert full["value"] == line["value"] and full["ms_per_step"] == line["ms_per_step"]
@@ -3095,7 +3097,7 @@ def test_bench_self_launches_ranks(tmp_path, ranks):
     free, _ = torch.cuda.mem_get_info()
     light = free < ranks * 32e9
     t0 = time.perf_counter()
-    line, result = _run_bench(["--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--image", "64", "--no-cpu-baseline",
+    line, result = _run_bench(["--full", "--gpus", str(ranks), "--steps", "2", "--warmup", "1", "--image", "64", "--no-cpu-baseline",
                                "--no-split-precision"] + (["--no-train-step"] if light else []), env, tmp_path)
     elapsed = time.perf_counter() - t0
     assert elapsed < 300.0, elapsed
@@ -3123,13 +3125,53 @@ def test_bench_collectives_through_rccl_with_one_rank(tmp_path):
     env = dict(os.environ, PR_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    line, result = _run_bench(["--gpus", "1", "--steps", "2", "--warmup", "1", "--image", "64", "--no-cpu-baseline", "--no-split-precision",
-                               "--no-minecraft", "--no-distinct-frames", "--no-shard-balance"], env, tmp_path)
+    line, result = _run_bench(["--full", "--gpus", "1", "--steps", "2", "--warmup", "1", "--image", "64", "--no-cpu-baseline",
+                               "--no-split-precision", "--no-minecraft", "--no-distinct-frames", "--no-shard-balance"], env, tmp_path)
     assert line["distributed"]["backend"] == "nccl" and line["distributed"]["world_size"] == 1
     assert line["distributed"]["nccl_version"][0].isdigit(), line["distributed"]
     assert result["feature_gather"]["all_gather"]["ms"] > 0 and result["feature_gather"]["gather_dst0"]["ms"] > 0
     assert result["identical_frames"]["value"] > 0 and result["train_step"]["value"] > 0
     assert result["train_step_with_decoder"]["maps_route"]["ms_per_step"] > 0
+
+
+def test_bench_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: the headline alone (none of the secondary figures), exactly K
+    timed steps in the line, and the last step's result as .npy files (float32 / float64, <= 64 MB, manifest) - the scene inputs the
+    result echoes are the same in a second run with the same arguments, the rendered fields agree."""
+    import json
+    import numpy as np
+    runs = []
+    for i in range(2):
+        dump = os.path.join(str(tmp_path), f"outputs_{i}")
+        line, full = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "1", "--image", "64", "--dump-outputs", dump],
+                                dict(os.environ), tmp_path)
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["metric"] == line["unit"] == "Mrays/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+        assert line["roofline"] == {} and "cpu_baseline" not in line
+        for leg in ("roofline", "split_precision", "half_precision", "feature_gather", "shard_balance", "distinct_frames", "train_step",
+                    "native_eval_frame", "config2_minecraft_256", "cpu_baseline", "reference_graph_on_gpu"):
+            assert leg not in full, leg
+        with open(os.path.join(dump, "manifest.json")) as f:
+            manifest = json.load(f)
+        arrays = {name: np.load(os.path.join(dump, name + ".npy")) for name in manifest}
+        coded = {name: np.load(os.path.join(dump, e["nonfinite_file"])) for name, e in manifest.items() if "nonfinite_file" in e}
+        assert sorted(n for n in os.listdir(dump) if n.endswith(".npy")) == sorted([n + ".npy" for n in manifest] +
+                                                                                  [manifest[n]["nonfinite_file"] for n in coded])
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in list(arrays.values()) + list(coded.values()))
+        for name, codes in coded.items():       # (the disparity of a ray with opacity 0 is NaN, as in the reference)
+            assert codes.shape == arrays[name].shape and set(np.unique(codes)) <= {0.0, 1.0, 2.0, 3.0}
+            arrays[name] = np.where(codes == 0, arrays[name], np.choose(codes.astype(int), [0.0, np.nan, np.inf, -np.inf]))
+        assert sum(os.path.getsize(os.path.join(dump, n)) for n in os.listdir(dump)) <= 64e6
+        feats = arrays["fine.global.integrated_features"]
+        assert manifest["fine.global.integrated_features"]["shape"][-2:] == [64 * 64, 192] and feats.size == 64 * 64 * 192
+        assert np.isfinite(feats).all() and np.abs(feats).max() > 0
+        runs.append(arrays)
+    assert sorted(runs[0]) == sorted(runs[1])
+    for name in runs[0]:
+        if name.startswith("scene_encoding."):
+            assert np.array_equal(runs[0][name], runs[1][name]), name
+        else:
+            assert np.allclose(runs[0][name], runs[1][name], rtol=1e-5, atol=1e-6, equal_nan=True), name
 
 
 @pytest.mark.parametrize("precision", ["fp32", "f16x3"])
