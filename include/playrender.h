@@ -85,8 +85,7 @@ typedef enum pr_status {
                                        fp16 pair (x = hi + lo, three fp16 MFMAs per product): the backward chains on the gradient tile
                                        times a power of two chosen per 64-row tile and the weights times 2^8, the weight gradients on
                                        16-row half slabs - gradient rows times a power of two alpha, activation rows times C / alpha, C a
-                                       running power of two per work item (all scalings exact; a build with -DPR_TNALL_F16=0 keeps the
-                                       round-4 form of the weight gradients, three bf16 terms per operand and six bf16 MFMAs).  On the forward call the flag
+                                       running power of two per work item (all scalings exact).  On the forward call the flag
                                        selects fp16-pair products for phase 1 of a train-mode forward pass too.  The call
                                        stays PR_PRECISION_FP32 (fp32-packed weights, which carry both split forms as well).  Products
                                        that have no split kernel run the exact fp32 one. */

@@ -1345,7 +1345,7 @@ static int make_bwd_plan(const pr_call_t& c, const pr_object_t* objs, BwdPlan* b
         bp->div_stack = take(stack_need);
     }
 #ifdef PR_BWD_LAYERWISE
-    gstack_need = CHAIN_GSTACK_LIMIT + 1;     // measurement build: one product per layer and launch
+    gstack_need = CHAIN_GSTACK_LIMIT + 1;     // test build: the layer-by-layer path (one product per layer and launch) at any size
 #endif
     const bool chained = gstack_need <= CHAIN_GSTACK_LIMIT;
     bp->gstack_bytes = chained ? gstack_need : 0;
@@ -1358,13 +1358,11 @@ static int make_bwd_plan(const pr_call_t& c, const pr_object_t* objs, BwdPlan* b
     bp->tables = take(sizeof(float) * (size_t)c.frames * 4 * MAX_WIDTH);
     const size_t lane_bytes = off - lane_begin;
     bp->lanes = 1;
-#ifndef PR_BWD_ONE_LANE
     if (c.objects > 1 && lane_bytes <= LANE_SCRATCH_LIMIT) {
         bp->lanes = 2;
         bp->lane_stride = lane_bytes;
         off += lane_bytes;
     }
-#endif
     bp->bytes = off;
     // ---- grouped path: the same front, then per-object buffers for every object at once
     {
@@ -1426,9 +1424,6 @@ static int make_bwd_plan(const pr_call_t& c, const pr_object_t* objs, BwdPlan* b
         gp.zero_bytes = goff - gp.zero_begin;
         gp.end = goff;
         gp.usable = !(c.flags & PR_FLAG_DIVERGENCE_GRAD) && (goff - lane_begin) <= GROUP_SCRATCH_LIMIT;
-#ifdef PR_BWD_PER_OBJECT
-        gp.usable = false;          // measurement build: the per-object path for every call
-#endif
         if (gp.usable) bp->bytes = goff;     // (the per-object scratch is not needed)
     }
     return PR_OK;
@@ -2065,14 +2060,8 @@ static int backward_grouped(const pr_call_t& c, const pr_object_t* objs, int t, 
         float* dscale2 = tables + (size_t)c.frames * 2 * MAX_WIDTH;
         float* dbias2 = tables + (size_t)c.frames * 3 * MAX_WIDTH;
         const int frozen = (c.flags & PR_FLAG_TRAIN_BN) ? 0 : 1;
-#ifdef PR_CHAIN_BF16
-        const int split_bwd = (c.flags & PR_FLAG_SPLIT_BACKWARD) ? 1 : 0;      // products on bf16 triples (t3_* segments)
-#else
         const int split_bwd = (c.flags & PR_FLAG_SPLIT_BACKWARD) ? 2 : 0;      // products on fp16 pairs of scaled tiles (t3_* segments)
-#endif
-        // (the two head phases keep the fp32 product: with the phase's raw-activation prefetch registers the bf16 variant of
-        // k_head_bwd_group spills 125 VGPRs; they are 0.4 ms of the step)
-        const int split_head = 0;
+        // (the two head phases keep the fp32 product)
         float lo[3], hi[3], size[3];
         bbox_split(m, lo, hi, size);
         const int nb = m.backbone_count;
@@ -2084,7 +2073,7 @@ static int backward_grouped(const pr_call_t& c, const pr_object_t* objs, int t, 
         a.phase = 1; a.frozen = frozen; a.stat_count = stat_count; a.eps = m.bn_eps;
         a.table = table; a.table_stride = table_stride; a.goff = 2 * d.Wpad; a.boff = 2 * d.Wpad + d.W2pad;
         a.g_in = g_feat; a.ld_gin = Fs; a.k_real = F; a.kpad = d.Fpad;
-        a.wt = Seg{packed + (split_head ? l.t3_h6 : l.t_h6), d.Fpad / 8, 0}; a.nblk = d.W2pad / 32; a.split = split_head;
+        a.wt = Seg{packed + l.t_h6, d.Fpad / 8, 0}; a.nblk = d.W2pad / 32;
         a.h = h2v; a.ld = d.W2pad; a.mean = batch + 2 * MAX_WIDTH; a.var = batch + 3 * MAX_WIDTH; a.width = d.W2;
         a.a_out = a2; a.d_out = d2; a.sums = sums; a.dscale = dscale2; a.dbias = dbias2;
         a.tile_counter = counters + 4 * k;
@@ -2095,7 +2084,7 @@ static int backward_grouped(const pr_call_t& c, const pr_object_t* objs, int t, 
         b.g_in = nullptr;
         b.d_in = d2; b.h_in = h2v; b.mean_in = batch + 2 * MAX_WIDTH; b.var_in = batch + 3 * MAX_WIDTH; b.sums_in = sums; b.width_in = d.W2;
         b.kpad = d.W2pad;
-        b.wt = Seg{packed + (split_head ? l.t3_h3 : l.t_h3), d.W2pad / 8, 0}; b.nblk = d.Wpad / 32; b.split = split_head;
+        b.wt = Seg{packed + l.t_h3, d.W2pad / 8, 0}; b.nblk = d.Wpad / 32;
         b.h = h1v; b.ld = d.Wpad; b.mean = batch; b.var = batch + MAX_WIDTH; b.width = d.W;
         b.a_out = a1; b.d_out = d1; b.sums = sums + 2 * MAX_WIDTH; b.dscale = dscale1; b.dbias = dbias1;
         b.tile_counter = counters + 4 * k + 1;
@@ -2282,10 +2271,8 @@ static int backward_grouped(const pr_call_t& c, const pr_object_t* objs, int t, 
     auto run = [&]() -> int {
         PR_TRY(launch_head_bwd_group(h1, rows, K, s));
         PR_TRY(launch_head_bwd_group(h2, rows, K, s));
-#ifndef PR_BWD_ONE_STREAM
         PR_TRY(lane_stream(s, &aux));
         PR_TRY(stream_wait(aux, s));                 // fork: behind the head phases
-#endif
         hipLaunchKernelGGL(k_style_bwd_group, dim3(style_blocks, style_jobs), dim3(256), 0, aux ? aux : s, sj);
         PR_LAUNCH_CHECK();
         PR_TRY(launch_chain_bwd_group(cn, rows, K, s));

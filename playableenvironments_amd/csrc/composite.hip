@@ -50,9 +50,7 @@ __device__ __forceinline__ void transmittance_weights(float* al, int n, int lane
     }
 }
 
-#ifndef ROWS_IN_FLIGHT
-#define ROWS_IN_FLIGHT 8
-#endif
+constexpr int ROWS_IN_FLIGHT = 8;       // feature rows a wave loads before it accumulates them (the compositing pass below)
 
 // weights[j] = alpha[j] * prod_{i<j} (...) over al[0..n) by CW waves: wave w scans the contiguous segment
 // [w * seg, (w + 1) * seg) (seg a multiple of 64) from a unit carry, the segment products are exchanged through
@@ -253,12 +251,7 @@ __global__ __launch_bounds__(64 * CW) void k_composite(CompositeParams p) {
     {
         int counts[PR_MAX_OBJECTS];
         for (int k = 0; k < p.objects; ++k) counts[k] = p.obj[k].positions;
-#if defined(PR_COMPOSITE_ABLATE) && PR_COMPOSITE_ABLATE >= 2
-        for (int e = tid; e < PT; e += CT) sm.key[e] = (unsigned int)e;   // measurement build: no merge (wrong order)
-        __syncthreads();
-#else
         order_entries(sm.key, sm.tt, counts, p.objects, PT, S, !p.fix_overlaps, tid, CT, wide);
-#endif
     }
 
     // ---- global alphas / weights in sorted order -------------------------------------------------
@@ -350,9 +343,6 @@ __global__ __launch_bounds__(64 * CW) void k_composite(CompositeParams p) {
             }
             count += __popcll(m);
         }
-#if defined(PR_COMPOSITE_ABLATE) && PR_COMPOSITE_ABLATE >= 1
-        count = 0;   // measurement build: no feature rows are read
-#endif
         // (the list of a wave is written and read by that wave only: no barrier needed in between)
         const int* rows_w = lrow + off + begin;
         const float* w1_w = lw1 + off + begin;

@@ -15,12 +15,6 @@ namespace pr {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 #define PR_MFMA32(acc, a, b) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0)
 
-#ifndef PR_GEMM_ABLATE
-#define PR_GEMM_ABLATE 0       // timing builds only: 1 = no epilogue, 2 = no operand re-fetch, 4 = no MFMA
-#endif
-#ifndef PR_TNALL_ABLATE
-#define PR_TNALL_ABLATE 0      // timing builds only (k_gemm_tn_all): 1 = no partial write-out, 2 = no operand re-fetch, 4 = no MFMA
-#endif
 constexpr int GT = 128;        // output tile edge
 constexpr int GK = 32;         // reduction slab depth
 constexpr int GLD = 160;       // LDS row stride (floats)
@@ -99,10 +93,10 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nn(GemmNN p) {
         stage();
         __syncthreads();
         for (int k0 = 0; k0 < p.k; k0 += GK) {
-            const bool more = (k0 + GK < p.k) && !(PR_GEMM_ABLATE & 2);
+            const bool more = k0 + GK < p.k;
             if (more) fetch(k0 + GK);
 #pragma unroll
-            for (int kk = 0; kk < ((PR_GEMM_ABLATE & 4) ? 2 : GK); kk += 2) {
+            for (int kk = 0; kk < GK; kk += 2) {
                 const float a0 = SA[(wr * 64 + r) * GLA + kk + half];
                 const float a1 = SA[(wr * 64 + 32 + r) * GLA + kk + half];
                 const float b0 = SB[(kk + half) * GLD + wc * 64 + r];
@@ -119,7 +113,6 @@ __global__ __launch_bounds__(256, 2) void k_gemm_nn(GemmNN p) {
         // epilogue through LDS (the operand slabs are dead after the last barrier): every wave parks a 32 x 64 half
         // of its block, then moves whole 256-byte row segments with 16-byte accesses; the mask / previous values of
         // a half are all requested before the first store (C, mask and A may alias as far as the compiler knows)
-        if ((PR_GEMM_ABLATE & 1) && acc[0][0][0] != 123.456f) continue;
         const float* __restrict__ mask = p.mask;
         float* __restrict__ C = p.C;
         float* park = SA + wave * (32 * 68);          // 4 waves x 32 rows x 68 floats = 34 KB <= SA + SB
@@ -419,7 +412,7 @@ __device__ __forceinline__ void tn_all_tile(const TnJob& p, int tile, int split,
         float a0o = pa[2 * GLD], a1o = pa[2 * GLD + 32], b0o = pb[2 * GLD], b1o = pb[2 * GLD + 32];
         __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);      // both fragment sets are requested before the first MFMA
 #pragma unroll
-        for (int kk = 0; kk < ((PR_TNALL_ABLATE & 4) ? 4 : GK); kk += 4) {
+        for (int kk = 0; kk < GK; kk += 4) {
             PR_MFMA32(acc[0][0], a0e, b0e);
             PR_MFMA32(acc[0][1], a0e, b1e);
             PR_MFMA32(acc[1][0], a1e, b0e);
@@ -442,28 +435,26 @@ __device__ __forceinline__ void tn_all_tile(const TnJob& p, int tile, int split,
             __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
         }
     };
-    const bool prefetch = !(PR_TNALL_ABLATE & 2);
     if (m_begin < m_end) {
         fetch(ra0, rb0, w0, m_begin);
-        if (prefetch) fetch(ra1, rb1, w1, m_begin + GK);
+        fetch(ra1, rb1, w1, m_begin + GK);
         stage(ra0, rb0, w0);
     }
     __syncthreads();
     // steps in pairs: slab s is staged from set s % 2, and the set is refilled with slab s + 2 right away
     for (int m0 = m_begin; m0 < m_end; m0 += 2 * GK) {
-        if (prefetch) fetch(ra0, rb0, w0, m0 + 2 * GK);       // (rows beyond m_end read nothing)
+        fetch(ra0, rb0, w0, m0 + 2 * GK);       // (rows beyond m_end read nothing)
         step();
         __syncthreads();
         if (m0 + GK >= m_end) break;
-        if (prefetch) stage(ra1, rb1, w1);
+        stage(ra1, rb1, w1);
         __syncthreads();
-        if (prefetch) fetch(ra1, rb1, w1, m0 + 3 * GK);
+        fetch(ra1, rb1, w1, m0 + 3 * GK);
         step();
         __syncthreads();
-        if (m0 + 2 * GK < m_end && prefetch) stage(ra0, rb0, w0);
+        if (m0 + 2 * GK < m_end) stage(ra0, rb0, w0);
         __syncthreads();
     }
-    if ((PR_TNALL_ABLATE & 1) && acc[0][0][0] != 123.456f) return;
     const int ldp = tiles_j * GT;
     const int rows_p = ((p.ni + GT - 1) / GT) * GT;
     float* P = p.partial + (size_t)split * rows_p * ldp;
@@ -486,10 +477,8 @@ __device__ __forceinline__ void tn_all_tile(const TnJob& p, int tile, int split,
     }
 }
 
-#ifndef PR_TNALL_WGS
-#define PR_TNALL_WGS 2            // resident workgroups per CU
-#endif
-__global__ __launch_bounds__(256, PR_TNALL_WGS) void k_gemm_tn_all(TnAll g) {
+constexpr int TN_ALL_WGS = 2;             // resident workgroups per CU
+__global__ __launch_bounds__(256, TN_ALL_WGS) void k_gemm_tn_all(TnAll g) {
     __shared__ __attribute__((aligned(16))) float SA[GK * GLD];
     __shared__ __attribute__((aligned(16))) float SB[GK * GLD];
     __shared__ float SW[GK];
@@ -530,442 +519,11 @@ __global__ __launch_bounds__(256, PR_TNALL_WGS) void k_gemm_tn_all(TnAll g) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// The same work item in SPLIT precision (pr_call_t.precision = PR_PRECISION_F16X3 on a differentiable call): every fp32 operand
-// as THREE bf16 terms, x = b1 + b2 + b3 (each term what is left rounded to the nearest bf16: 8 + 8 + 8 mantissa bits
-// with residuals of either sign, and the fp32 exponent range - gradients of 1e-7 are as well represented as activations of 1, which
-// an fp16 pair is not), and a product as the SIX bf16 MFMAs whose terms are >= 2^-16 of it:
-//     a b ~ a1 b1 + a1 b2 + a2 b1 + a1 b3 + a3 b1 + a2 b2        (dropped: a2 b3 + a3 b2 + a3 b3 <= 3 x 2^-24 |a b|, one fp32 rounding)
-// v_mfma_f32_32x32x16_bf16 multiplies exactly and accumulates in fp32; it retires 16 K-values in 32 cycles where the fp32 pipe
-// needs 8 x 64: six of them cost 192 against 512 cycles.  The reduction index of dW = dY^T X is the SLOW dimension of both
-// operands in memory; the bf16 MFMA wants eight consecutive K-values per lane, so a slab is transposed on its way into LDS:
-// planes T[column][k] (80-byte rows: five 16-byte slots, conflict-free b128 fragment reads), a thread's four rows of a column
-// = four consecutive k (one 8-byte store per plane and column; the same k permutation for both operands), slots rotated by
-// (column >> 4) & 3 so that the 32 lanes of a store instruction spread over the banks.
-// ---------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-constexpr int TROW = 80;                       // bytes per LDS row of a plane: 32 k-values + one 16-byte pad slot
-constexpr int TPLANE = GT * TROW;              // one plane of one operand
-#define PR_MFMA_BF16(acc, a, b) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0)
-
-typedef __bf16 bf16x2_g __attribute__((ext_vector_type(2)));
-typedef float f32x2_g __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ float sub_f32_g(float a, float b) {      // (not packed into v_pk_add_f32: slow beside MFMAs)
-    float r;
-    asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// two values -> their three bf16 terms, rounded to nearest (v_cvt_pk_bf16_f32): packed pairs [x0 | x1] per term
-__device__ __forceinline__ void bf16_split_pair(float x0, float x1, unsigned& p1, unsigned& p2, unsigned& p3) {
-    const f32x2_g v = {x0, x1};
-    p1 = __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_g));
-#if defined(PR_TNBF_ABLATE) && (PR_TNBF_ABLATE & 16)
-    p2 = p1 ^ 0x00010001u; p3 = p1 ^ 0x00020002u;
-    return;
-#endif
-    const f32x2_g r = {sub_f32_g(x0, __uint_as_float(p1 << 16)), sub_f32_g(x1, __uint_as_float(p1 & 0xffff0000u))};
-    p2 = __builtin_bit_cast(unsigned, __builtin_convertvector(r, bf16x2_g));
-    const f32x2_g q = {sub_f32_g(r[0], __uint_as_float(p2 << 16)), sub_f32_g(r[1], __uint_as_float(p2 & 0xffff0000u))};
-    p3 = __builtin_bit_cast(unsigned, __builtin_convertvector(q, bf16x2_g));
-}
-
-#ifndef PR_TNBF_ABLATE
-#define PR_TNBF_ABLATE 0      // timing builds only (results are wrong): 1 = slabs are not staged, 2 = no MFMAs, 4 = no operand requests,
-#endif                        // 8 = three of the six MFMAs (what fp16 pairs would issue), 16 = one conversion per pair instead of three
-__device__ __forceinline__ void tn_all_tile_bf16(const TnJob& p, int tile, int split, unsigned char* T, float* RED) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int wr = wave >> 1, wc = wave & 1, r = lane & 31, half = lane >> 5;
-    const int M = *p.rows;
-    const int tiles_j = (p.nj + GT - 1) / GT;
-    const int ti = tile / tiles_j, tj = tile - ti * tiles_j;
-    const int i0 = ti * GT, j0 = tj * GT;
-    const int m_begin = split * TN_ALL_CHUNK;
-    const int m_end = (m_begin + TN_ALL_CHUNK < M) ? m_begin + TN_ALL_CHUNK : M;
-    f32x16 acc[2][2];
-    zero_acc(acc);
-    const bool want_bias = p.bias_partial && tj == 0;
-    const bool side = p.w != nullptr && ti == 0;
-    float bsum[4] = {0.f, 0.f, 0.f, 0.f}, wsum[4] = {0.f, 0.f, 0.f, 0.f}, wtot = 0.f;
-    const int c4 = tid & 31, rr = tid >> 5;
-    const bool acol = i0 + 4 * c4 < ((p.ni + 3) & ~3), bcol = j0 + 4 * c4 < ((p.nj + 3) & ~3);
-    float4 ra0[4], rb0[4], ra1[4], rb1[4];
-    float w0[4], w1[4];
-    const float* __restrict__ gA = p.A + i0 + 4 * c4;
-    const float* __restrict__ gB = p.B + j0 + 4 * c4;
-    const size_t lda = (size_t)p.lda, ldb = (size_t)p.ldb;
-    auto fetch = [&](float4 (&ra)[4], float4 (&rb)[4], float (&wv)[4], int m0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int m = m0 + rr + 8 * i;
-            const bool live = m < m_end;
-            ra[i] = (live && acol) ? *reinterpret_cast<const float4*>(gA + (size_t)m * lda) : make_float4(0.f, 0.f, 0.f, 0.f);
-            rb[i] = (live && bcol) ? *reinterpret_cast<const float4*>(gB + (size_t)m * ldb) : make_float4(0.f, 0.f, 0.f, 0.f);
-            if (side) wv[i] = live ? p.w[(size_t)m * p.ldw] : 0.f;
-        }
-    };
-    // the three planes of one operand: column c (of the tile), this thread's four k = 4 rr .. 4 rr + 3
-    auto put = [&](unsigned char* planes, int c, float v0, float v1, float v2, float v3) {
-        unsigned a1, a2, a3, b1, b2, b3;
-        bf16_split_pair(v0, v1, a1, a2, a3);
-        bf16_split_pair(v2, v3, b1, b2, b3);
-        const int at = c * TROW + ((((rr >> 1) + (c >> 4)) & 3) << 4) + ((rr & 1) << 3);
-        *reinterpret_cast<uint2*>(planes + at) = make_uint2(a1, b1);
-        *reinterpret_cast<uint2*>(planes + TPLANE + at) = make_uint2(a2, b2);
-        *reinterpret_cast<uint2*>(planes + 2 * TPLANE + at) = make_uint2(a3, b3);
-    };
-    auto stage = [&](const float4 (&ra)[4], const float4 (&rb)[4], const float (&wv)[4]) {
-        put(T, 4 * c4 + 0, ra[0].x, ra[1].x, ra[2].x, ra[3].x);
-        put(T, 4 * c4 + 1, ra[0].y, ra[1].y, ra[2].y, ra[3].y);
-        put(T, 4 * c4 + 2, ra[0].z, ra[1].z, ra[2].z, ra[3].z);
-        put(T, 4 * c4 + 3, ra[0].w, ra[1].w, ra[2].w, ra[3].w);
-        put(T + 3 * TPLANE, 4 * c4 + 0, rb[0].x, rb[1].x, rb[2].x, rb[3].x);
-        put(T + 3 * TPLANE, 4 * c4 + 1, rb[0].y, rb[1].y, rb[2].y, rb[3].y);
-        put(T + 3 * TPLANE, 4 * c4 + 2, rb[0].z, rb[1].z, rb[2].z, rb[3].z);
-        put(T + 3 * TPLANE, 4 * c4 + 3, rb[0].w, rb[1].w, rb[2].w, rb[3].w);
-        if (want_bias) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { bsum[0] += ra[i].x; bsum[1] += ra[i].y; bsum[2] += ra[i].z; bsum[3] += ra[i].w; }
-        }
-        if (side) {
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                wsum[0] = fmaf(wv[i], rb[i].x, wsum[0]); wsum[1] = fmaf(wv[i], rb[i].y, wsum[1]);
-                wsum[2] = fmaf(wv[i], rb[i].z, wsum[2]); wsum[3] = fmaf(wv[i], rb[i].w, wsum[3]);
-                wtot += wv[i];
-            }
-        }
-    };
-    // fragment addresses: lane (r, half) of block `blk` reads column base + blk * 32 + r, logical slot 2 kb + half
-    const int colA0 = wr * 64 + r, colB0 = wc * 64 + r;
-    auto step = [&]() {
-        // (one K block of 16 at a time, the B fragments of one column block at a time: 24 + 12 fragment registers live instead of
-        // 96 - with everything hoisted the kernel spilled)
-#pragma unroll 1
-        for (int kb = 0; kb < 2; ++kb) {
-            bf16x8 a[2][3];
-#pragma unroll
-            for (int blk = 0; blk < 2; ++blk) {
-                const int ca = colA0 + blk * 32;
-                const int oa = ca * TROW + (((2 * kb + half + (ca >> 4)) & 3) << 4);
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) a[blk][pl] = *reinterpret_cast<const bf16x8*>(T + pl * TPLANE + oa);
-            }
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb) {
-                const int cc = colB0 + cb * 32;
-                const int ob = cc * TROW + (((2 * kb + half + (cc >> 4)) & 3) << 4);
-                bf16x8 b[3];
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) b[pl] = *reinterpret_cast<const bf16x8*>(T + (3 + pl) * TPLANE + ob);
-#pragma unroll
-                for (int rb2 = 0; rb2 < 2; ++rb2) {
-                    // smallest terms first
-                    PR_MFMA_BF16(acc[rb2][cb], a[rb2][1], b[1]);
-                    PR_MFMA_BF16(acc[rb2][cb], a[rb2][0], b[2]);
-                    PR_MFMA_BF16(acc[rb2][cb], a[rb2][2], b[0]);
-                    PR_MFMA_BF16(acc[rb2][cb], a[rb2][0], b[1]);
-                    PR_MFMA_BF16(acc[rb2][cb], a[rb2][1], b[0]);
-                    PR_MFMA_BF16(acc[rb2][cb], a[rb2][0], b[0]);
-                }
-            }
-        }
-    };
-#ifdef PR_TNBF_TWO_SLABS
-    if (m_begin < m_end) {
-        fetch(ra0, rb0, w0, m_begin);
-        fetch(ra1, rb1, w1, m_begin + GK);
-        stage(ra0, rb0, w0);
-    }
-    __syncthreads();
-    for (int m0 = m_begin; m0 < m_end; m0 += 2 * GK) {
-        fetch(ra0, rb0, w0, m0 + 2 * GK);       // (rows beyond m_end read nothing)
-        step();
-        __syncthreads();
-        if (m0 + GK >= m_end) break;
-        stage(ra1, rb1, w1);
-        __syncthreads();
-        fetch(ra1, rb1, w1, m0 + 3 * GK);
-        step();
-        __syncthreads();
-        if (m0 + 2 * GK < m_end) stage(ra0, rb0, w0);
-        __syncthreads();
-    }
-#else
-    // ONE slab in flight in registers (requested before the current slab's MFMAs, staged behind them): the launch is bound by
-    // its operand traffic, and a second register set made the kernel spill
-    (void)ra1; (void)rb1; (void)w1;
-    if (m_begin < m_end) {
-        fetch(ra0, rb0, w0, m_begin);
-        stage(ra0, rb0, w0);
-    }
-    __syncthreads();
-    for (int m0 = m_begin; m0 < m_end; m0 += GK) {
-        if (!(PR_TNBF_ABLATE & 4)) fetch(ra0, rb0, w0, m0 + GK);           // (rows beyond m_end read nothing)
-        if (!(PR_TNBF_ABLATE & 2)) step();
-        __syncthreads();
-        if (m0 + GK < m_end && !(PR_TNBF_ABLATE & 1)) stage(ra0, rb0, w0);
-        __syncthreads();
-    }
-#endif
-    const int ldp = tiles_j * GT;
-    const int rows_p = ((p.ni + GT - 1) / GT) * GT;
-    float* P = p.partial + (size_t)split * rows_p * ldp;
-#pragma unroll
-    for (int rb2 = 0; rb2 < 2; ++rb2)
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-            const int col = j0 + wc * 64 + cb * 32 + r;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int row = i0 + wr * 64 + rb2 * 32 + (i & 3) + 8 * (i >> 2) + 4 * half;
-                P[(size_t)row * ldp + col] = acc[rb2][cb][i];
-            }
-        }
-    // column sums kept per thread (its 4 columns, the rows it staged): added over the 8 row groups in a fixed order
-    if (want_bias || side) {
-        __syncthreads();
-        float* R = RED;                                  // [8 row groups][128 columns] bias, then the same for the side product
-        if (want_bias) for (int e = 0; e < 4; ++e) R[rr * GT + 4 * c4 + e] = bsum[e];
-        if (side) {
-            for (int e = 0; e < 4; ++e) R[8 * GT + rr * GT + 4 * c4 + e] = wsum[e];
-            if (c4 == 0) R[16 * GT + rr] = wtot;
-        }
-        __syncthreads();
-        if (want_bias && tid < GT) {
-            float v = 0.f;
-            for (int g8 = 0; g8 < 8; ++g8) v += R[g8 * GT + tid];
-            p.bias_partial[(size_t)split * rows_p + i0 + tid] = v;
-        }
-        if (side && tid >= GT) {
-            float* W = p.w_partial + (size_t)split * (ldp + 4);
-            float v = 0.f;
-            for (int g8 = 0; g8 < 8; ++g8) v += R[8 * GT + g8 * GT + tid - GT];
-            W[j0 + tid - GT] = v;
-            if (tid == GT && tj == 0) {
-                float t = 0.f;
-                for (int g8 = 0; g8 < 8; ++g8) t += R[16 * GT + g8];
-                W[ldp] = t;
-            }
-        }
-    }
-}
-
-
-// The same tile with the staging of the NEXT half slab inside the products of the current one.  In tn_all_tile_bf16 a slab is
-// multiplied (48 MFMAs per wave), then - behind a barrier - the next one is split into bf16 triples and written to LDS (~250 VALU
-// operations and 24 LDS stores per thread), then - behind another barrier - multiplied: measured with either half removed, the two
-// phases take the same time (0.87 ms each of a 1.41 ms launch; the second workgroup of the CU is all that overlaps them).  A plane
-// row already holds its 32 k-values as two independent halves (slots 0 - 1: k 0..15, slots 2 - 3: k 16..31), so the halves serve as a
-// double buffer of 16-row half slabs with no more LDS: while the MFMAs of half h read one pair of slots, the same wave converts half
-// h + 1 into the other pair (VALU work issues while the matrix pipe executes), ONE barrier per half slab.  Waves 0 - 1 stage the A
-// operand, waves 2 - 3 the B operand (four rows x four columns per thread and half slab: the 8-byte LDS stores of the full-slab
-// version); three register sets, the requests of half h + 3 issued at the top of half step h.
-// Requests are unconditional (clamped addresses, values zeroed afterwards where a row or column is outside): see as_global() in
-// pr_common.h for what requests under a branch do to the waits.
-// Measured (same box, per launch of the training step): 1.444 -> 1.376 ms; without the operand requests 1.126, MFMAs alone 0.745,
-// staging alone 0.892 - VALU work beside MFMAs of the same SIMD is only partly free (tools/perf/probe_overlap.hip: six conversions
-// per MFMA cost + 20 - 35 % with two waves per SIMD), and the requests are bound by the 5.2 GB the launch reads, not by their latency.
-// Explicit (MFMA, n x VALU) scheduling groups were slower than hipcc's own interleaving (1.39 vs 1.31 ms).
-__device__ __forceinline__ void tn_all_tile_bf16_overlap(const TnJob& p, int tile, int split, unsigned char* T, float* RED) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int wr = wave >> 1, wc = wave & 1, r = lane & 31, half = lane >> 5;
-    const int M = *p.rows;
-    const int tiles_j = (p.nj + GT - 1) / GT;
-    const int ti = tile / tiles_j, tj = tile - ti * tiles_j;
-    const int i0 = ti * GT, j0 = tj * GT;
-    const int m_begin = split * TN_ALL_CHUNK;
-    const int m_end = (m_begin + TN_ALL_CHUNK < M) ? m_begin + TN_ALL_CHUNK : M;
-    f32x16 acc[2][2];
-    zero_acc(acc);
-    const bool want_bias = p.bias_partial && tj == 0;
-    const bool side = p.w != nullptr && ti == 0;
-    const bool opB = wave >= 2;                      // this wave stages the B operand (wave-uniform)
-    const int t7 = tid & 127, c4 = t7 & 31, rq = t7 >> 5;
-    const int ncols = opB ? ((p.nj + 3) & ~3) : ((p.ni + 3) & ~3);
-    const int base_col = opB ? j0 : i0;
-    const bool colok = base_col + 4 * c4 < ncols;
-    const bool cols_full = base_col + GT <= ncols;   // (wave-uniform)
-    const size_t ldx = opB ? (size_t)p.ldb : (size_t)p.lda;
-    const float* __restrict__ gX = (opB ? p.B : p.A) + base_col + (colok ? 4 * c4 : 0);
-    // the side product's weights: B-staging threads read w[m]; everybody else (and every thread without a side product) reads a
-    // valid dummy with stride 0 - the requests stay unconditional
-    const float* __restrict__ gW = (side && opB) ? p.w : gX;
-    const size_t ldw = (side && opB) ? (size_t)p.ldw : 0;
-    unsigned char* planes = T + (opB ? 3 * TPLANE : 0);
-    float bsum[4] = {0.f, 0.f, 0.f, 0.f}, wsum[4] = {0.f, 0.f, 0.f, 0.f}, wtot = 0.f;
-    const int halves = (m_end - m_begin + 15) >> 4;
-    if (halves > 0) {
-        f32x4_t s0[4], s1[4], s2[4];
-        float w0[4], w1[4], w2[4];
-        auto fetch = [&](f32x4_t (&sv)[4], float (&wv)[4], int h) {
-            const int mh = m_begin + 16 * h + rq;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int m = mh + 4 * i;
-                const int mc = m < m_end ? m : m_end - 1;
-                sv[i] = *reinterpret_cast<const f32x4_t*>(gX + (size_t)mc * ldx);
-                wv[i] = gW[(size_t)mc * ldw];
-            }
-        };
-        // rows / columns outside the operand contribute zeros (wave-uniform test first: full half slabs of full tiles skip the selects)
-        auto mask = [&](f32x4_t (&sv)[4], float (&wv)[4], int h) {
-            const int mh = m_begin + 16 * h;
-            if (mh + 16 <= m_end && cols_full) return;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const bool row = mh + rq + 4 * i < m_end;
-                const bool ok = row && colok;
-                sv[i].x = ok ? sv[i].x : 0.f; sv[i].y = ok ? sv[i].y : 0.f; sv[i].z = ok ? sv[i].z : 0.f; sv[i].w = ok ? sv[i].w : 0.f;
-                wv[i] = row ? wv[i] : 0.f;
-            }
-        };
-        // one column of the staged 4 x 4 block: four consecutive k of half buffer `hb` (logical slots 2 hb, 2 hb + 1)
-        const int rot = c4 >> 2;                       // (column >> 4) of the thread's four columns
-        auto put = [&](int hb, int e, float v0, float v1, float v2, float v3) {
-            unsigned a1, a2, a3, b1, b2, b3;
-            bf16_split_pair(v0, v1, a1, a2, a3);
-            bf16_split_pair(v2, v3, b1, b2, b3);
-            const int at = (4 * c4 + e) * TROW + (((2 * hb + (rq >> 1) + rot) & 3) << 4) + ((rq & 1) << 3);
-            *reinterpret_cast<uint2*>(planes + at) = make_uint2(a1, b1);
-            *reinterpret_cast<uint2*>(planes + TPLANE + at) = make_uint2(a2, b2);
-            *reinterpret_cast<uint2*>(planes + 2 * TPLANE + at) = make_uint2(a3, b3);
-        };
-        auto sums = [&](const f32x4_t (&sv)[4], const float (&wv)[4]) {
-            if (want_bias && !opB) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) { bsum[0] += sv[i].x; bsum[1] += sv[i].y; bsum[2] += sv[i].z; bsum[3] += sv[i].w; }
-            }
-            if (side && opB) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    wsum[0] = fmaf(wv[i], sv[i].x, wsum[0]); wsum[1] = fmaf(wv[i], sv[i].y, wsum[1]);
-                    wsum[2] = fmaf(wv[i], sv[i].z, wsum[2]); wsum[3] = fmaf(wv[i], sv[i].w, wsum[3]);
-                    wtot += wv[i];
-                }
-            }
-        };
-        const int colA0 = wr * 64 + r, colB0 = wc * 64 + r;
-        // the products of half buffer `hc` with the staging of `sv` into half buffer `hs` between them
-        auto half_step = [&](int hc, f32x4_t (&sv)[4], float (&wv)[4], int hs) {
-            bf16x8 a[2][3], b[3];
-#pragma unroll
-            for (int blk = 0; blk < 2; ++blk) {
-                const int ca = colA0 + blk * 32;
-                const int oa = ca * TROW + (((2 * hc + half + (ca >> 4)) & 3) << 4);
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) a[blk][pl] = *reinterpret_cast<const bf16x8*>(T + pl * TPLANE + oa);
-            }
-#pragma unroll
-            for (int cb = 0; cb < 2; ++cb) {
-                const int cc = colB0 + cb * 32;
-                const int ob = cc * TROW + (((2 * hc + half + (cc >> 4)) & 3) << 4);
-#pragma unroll
-                for (int pl = 0; pl < 3; ++pl) b[pl] = *reinterpret_cast<const bf16x8*>(T + (3 + pl) * TPLANE + ob);
-                // smallest terms first, the two row blocks alternating (independent accumulators back to back)
-                if (!(PR_TNBF_ABLATE & 2)) {
-                if (!(PR_TNBF_ABLATE & 8)) {
-                PR_MFMA_BF16(acc[0][cb], a[0][1], b[1]); PR_MFMA_BF16(acc[1][cb], a[1][1], b[1]);
-                PR_MFMA_BF16(acc[0][cb], a[0][0], b[2]); PR_MFMA_BF16(acc[1][cb], a[1][0], b[2]);
-                PR_MFMA_BF16(acc[0][cb], a[0][2], b[0]); PR_MFMA_BF16(acc[1][cb], a[1][2], b[0]);
-                }
-                PR_MFMA_BF16(acc[0][cb], a[0][0], b[1]); PR_MFMA_BF16(acc[1][cb], a[1][0], b[1]);
-                PR_MFMA_BF16(acc[0][cb], a[0][1], b[0]); PR_MFMA_BF16(acc[1][cb], a[1][1], b[0]);
-                PR_MFMA_BF16(acc[0][cb], a[0][0], b[0]); PR_MFMA_BF16(acc[1][cb], a[1][0], b[0]);
-                }
-                // (no test for "nothing left to stage": a half slab beyond the split's rows is staged as zeros and never multiplied - a
-                // branch here would end the basic block between the MFMAs and the conversions that are to issue beside them)
-                if (PR_TNBF_ABLATE & 1) {
-                } else if (cb == 0) {
-                    put(hs, 0, sv[0].x, sv[1].x, sv[2].x, sv[3].x);
-                    put(hs, 1, sv[0].y, sv[1].y, sv[2].y, sv[3].y);
-                } else {
-                    put(hs, 2, sv[0].z, sv[1].z, sv[2].z, sv[3].z);
-                    put(hs, 3, sv[0].w, sv[1].w, sv[2].w, sv[3].w);
-                    sums(sv, wv);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        };
-        // half 0 -> buffer 0 in front of the loop; THREE register sets: while one is staged, the next is in flight and the third is
-        // requested at the top of the half step (two half steps ahead of its use: with two sets the requests could only be issued
-        // behind the staging of the same registers, one half step ahead, and the conversions waited for memory)
-        fetch(s0, w0, 0);
-        fetch(s1, w1, 1);
-        fetch(s2, w2, 2);
-        mask(s0, w0, 0);
-        put(0, 0, s0[0].x, s0[1].x, s0[2].x, s0[3].x);
-        put(0, 1, s0[0].y, s0[1].y, s0[2].y, s0[3].y);
-        put(0, 2, s0[0].z, s0[1].z, s0[2].z, s0[3].z);
-        put(0, 3, s0[0].w, s0[1].w, s0[2].w, s0[3].w);
-        sums(s0, w0);
-        __syncthreads();
-        for (int h = 0; h < halves;) {
-            // half h multiplied out of buffer h & 1, half h + 1 staged into the other buffer, half h + 3 requested
-            if (!(PR_TNBF_ABLATE & 4)) fetch(s0, w0, h + 3);
-            mask(s1, w1, h + 1);
-            half_step(h & 1, s1, w1, (h + 1) & 1);
-            __syncthreads();
-            if (++h >= halves) break;
-            if (!(PR_TNBF_ABLATE & 4)) fetch(s1, w1, h + 3);
-            mask(s2, w2, h + 1);
-            half_step(h & 1, s2, w2, (h + 1) & 1);
-            __syncthreads();
-            if (++h >= halves) break;
-            if (!(PR_TNBF_ABLATE & 4)) fetch(s2, w2, h + 3);
-            mask(s0, w0, h + 1);
-            half_step(h & 1, s0, w0, (h + 1) & 1);
-            __syncthreads();
-            ++h;
-        }
-    }
-    const int ldp = tiles_j * GT;
-    const int rows_p = ((p.ni + GT - 1) / GT) * GT;
-    float* P = p.partial + (size_t)split * rows_p * ldp;
-#pragma unroll
-    for (int rb2 = 0; rb2 < 2; ++rb2)
-#pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-            const int col = j0 + wc * 64 + cb * 32 + r;
-#pragma unroll
-            for (int i = 0; i < 16; ++i) {
-                const int row = i0 + wr * 64 + rb2 * 32 + (i & 3) + 8 * (i >> 2) + 4 * half;
-                P[(size_t)row * ldp + col] = acc[rb2][cb][i];
-            }
-        }
-    // column sums kept per thread (its 4 columns, the rows it staged): added over the 4 row groups in a fixed order
-    if (want_bias || side) {
-        __syncthreads();
-        float* R = RED;                                  // [4 row groups][128 columns] bias, then the same for the side product
-        if (want_bias && !opB) for (int e = 0; e < 4; ++e) R[rq * GT + 4 * c4 + e] = bsum[e];
-        if (side && opB) {
-            for (int e = 0; e < 4; ++e) R[4 * GT + rq * GT + 4 * c4 + e] = wsum[e];
-            if (c4 == 0) R[8 * GT + rq] = wtot;
-        }
-        __syncthreads();
-        if (want_bias && tid < GT) {
-            float v = 0.f;
-            for (int g4 = 0; g4 < 4; ++g4) v += R[g4 * GT + tid];
-            p.bias_partial[(size_t)split * rows_p + i0 + tid] = v;
-        }
-        if (side && tid >= GT) {
-            float* W = p.w_partial + (size_t)split * (ldp + 4);
-            float v = 0.f;
-            for (int g4 = 0; g4 < 4; ++g4) v += R[4 * GT + g4 * GT + tid - GT];
-            W[j0 + tid - GT] = v;
-            if (tid == GT && tj == 0) {
-                float t = 0.f;
-                for (int g4 = 0; g4 < 4; ++g4) t += R[8 * GT + g4];
-                W[ldp] = t;
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// The same work item on fp16 PAIRS (k_gemm_tn_all_f16, the default of split-precision calls; -DPR_TNALL_F16=0 launches the bf16-triple
-// kernel above): x = hi + lo, a product as THREE v_mfma_f32_32x32x16_f16 (hi x hi + hi x lo + lo x hi) - measured on the triples with
-// -DPR_TNBF_ABLATE=8, half the matrix instructions are worth 0.25 ms of a 1.33 ms launch, the conversions nothing.  fp16 does not have the range of a gradient (1e-7 and below), so every HALF SLAB (16 sample rows) is scaled on its way into
-// LDS, the gradient rows by alpha_h, the activation rows by C / alpha_h: the product of a row pair is C x the true one for every half
-// slab, so all of them share the accumulators.
+// The same work item in SPLIT precision (k_gemm_tn_all_f16; pr_call_t.precision = PR_PRECISION_F16X3 on a differentiable call):
+// every operand as an fp16 PAIR, x = hi + lo, a product as THREE v_mfma_f32_32x32x16_f16 (hi x hi + hi x lo + lo x hi).  fp16 does
+// not have the range of a gradient (1e-7 and below), so every HALF SLAB (16 sample rows) is scaled on its way into LDS, the gradient
+// rows by alpha_h, the activation rows by C / alpha_h: the product of a row pair is C x the true one for every half slab, so all of
+// them share the accumulators.
 //   alpha_h = the power of two that puts the half slab's largest |dY| in [2^13, 2^14)
 //   C       = 2^(27 - E), E = the running maximum of  exponent(max |dY|) + exponent(max |X|)  over the half slabs seen: the scaled
 //             activations stay below 2^15; when a later half slab raises E by d, the accumulators are multiplied by 2^-d (exact)
@@ -973,10 +531,19 @@ __device__ __forceinline__ void tn_all_tile_bf16_overlap(const TnJob& p, int til
 // product (what k_chain_bwd_group_f16 does per 64-row tile); half slabs whose contribution is below 2^-17 of the largest one degrade
 // the same way.  The maxima travel between the A- and the B-staging waves through four rotating LDS words per operand, published one
 // half step ahead of the staging they steer (behind the barrier that is there anyway).
+// LDS: the reduction index of dW = dY^T X is the SLOW dimension of both operands in memory, the MFMA wants eight consecutive K-values
+// per lane, so a slab is transposed on its way into LDS: planes T[column][k] (80-byte rows: five 16-byte slots, conflict-free b128
+// fragment reads), a thread's four rows of a column = four consecutive k (the same k permutation for both operands), slots rotated by
+// (column >> 4) & 3 so that the 32 lanes of a store instruction spread over the banks.  A plane row holds its 32 k-values as two
+// independent halves (slots 0 - 1: k 0..15, slots 2 - 3: k 16..31), which serve as a double buffer of 16-row half slabs: while the
+// MFMAs of half h read one pair of slots, the same wave converts half h + 1 into the other pair (VALU work issues while the matrix pipe
+// executes), ONE barrier per half slab.  Waves 0 - 1 stage the A operand, waves 2 - 3 the B operand (four rows x four columns per
+// thread and half slab); three register sets, the requests of half h + 3 issued at the top of half step h.  Requests are unconditional
+// (clamped addresses, values zeroed afterwards where a row or column is outside): see as_global() in pr_common.h for what requests
+// under a branch do to the waits.
 // ---------------------------------------------------------------------------------------------
-#ifndef PR_TNALL_F16
-#define PR_TNALL_F16 1          // 0: the split-precision weight gradients on bf16 triples (k_gemm_tn_all_bf16; A/B builds)
-#endif
+constexpr int TROW = 80;                       // bytes per LDS row of a plane: 32 k-values + one 16-byte pad slot
+constexpr int TPLANE = GT * TROW;              // one plane of one operand
 typedef _Float16 f16x8_g __attribute__((ext_vector_type(8)));
 #define PR_MFMA_F16G(acc, a, b) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc, 0, 0, 0)
 // four values x scale -> packed fp16 hi halves (h01, h23) and lo halves (l01, l23): see split_quad_scaled_h in mlp_tile.h
@@ -1246,48 +813,6 @@ __device__ __forceinline__ void tn_all_tile_f16_overlap(const TnJob& p, int tile
     }
 }
 
-__global__ __launch_bounds__(256, 2) void k_gemm_tn_all_bf16(TnAll g) {
-    __shared__ __attribute__((aligned(16))) unsigned char T[6 * TPLANE];
-    __shared__ float RED[16 * GT + 8];
-    __shared__ int pair_begin[TN_ALL_MAX + 1];
-    __shared__ int claimed;
-    const int tid = threadIdx.x;
-    if (tid < g.count) pair_begin[tid + 1] = tn_all_splits(*g.job[tid].rows);
-    __syncthreads();
-    if (tid == 0) {
-        int at = 0;
-        for (int q = 0; q < g.count; ++q) {
-            const int n = pair_begin[q + 1];
-            pair_begin[q] = at;
-            at += n;
-        }
-        pair_begin[g.count] = at;
-    }
-    __syncthreads();
-    const int total_pairs = pair_begin[g.count];
-    const int xcd = blockIdx.x & 7;
-    int job = 0;
-    for (;;) {
-        if (tid == 0) claimed = atomicAdd(g.counters + xcd, 1);
-        __syncthreads();
-        const int c = claimed;
-        __syncthreads();
-        const int pair = (c / TN_ALL_TILES) * 8 + xcd;
-        if (pair >= total_pairs) break;
-        const int tile = c % TN_ALL_TILES;
-        while (pair >= pair_begin[job + 1]) ++job;
-        const TnJob& p = g.job[job];
-        const int tiles = ((p.ni + GT - 1) / GT) * ((p.nj + GT - 1) / GT);
-        if (tile >= tiles) continue;
-#ifdef PR_TNBF_SERIAL       // measurement build: the full-slab version (stage and multiply in turns)
-        tn_all_tile_bf16(p, tile, pair - pair_begin[job], T, RED);
-#else
-        tn_all_tile_bf16_overlap(p, tile, pair - pair_begin[job], T, RED);
-#endif
-        __syncthreads();
-    }
-}
-
 // the same persistent loop over the fp16-pair work item (the default of split-precision calls)
 __global__ __launch_bounds__(256, 2) void k_gemm_tn_all_f16(TnAll g) {
     __shared__ __attribute__((aligned(16))) unsigned char T[4 * TPLANE];      // A hi, A lo, B hi, B lo
@@ -1426,16 +951,11 @@ int launch_gemm_tn_all(TnAll& g, const long* max_rows, hipStream_t s) {
     int cus = 0;
     ProfileScope scope(3, s);
     if (g.split_precision) {
-#if PR_TNALL_F16
         PR_TRY(prepare_kernel(reinterpret_cast<const void*>(k_gemm_tn_all_f16), 0, &cus));
         hipLaunchKernelGGL(k_gemm_tn_all_f16, dim3(cus * 2), dim3(256), 0, s, g);
-#else
-        PR_TRY(prepare_kernel(reinterpret_cast<const void*>(k_gemm_tn_all_bf16), 0, &cus));
-        hipLaunchKernelGGL(k_gemm_tn_all_bf16, dim3(cus * 2), dim3(256), 0, s, g);
-#endif
     } else {
         PR_TRY(prepare_kernel(reinterpret_cast<const void*>(k_gemm_tn_all), 0, &cus));
-        hipLaunchKernelGGL(k_gemm_tn_all, dim3(cus * PR_TNALL_WGS), dim3(256), 0, s, g);
+        hipLaunchKernelGGL(k_gemm_tn_all, dim3(cus * TN_ALL_WGS), dim3(256), 0, s, g);
     }
     PR_LAUNCH_CHECK();
     hipLaunchKernelGGL(k_gemm_tn_all_reduce, dim3((unsigned)((max_elems + 255) / 256), g.count), dim3(256), 0, s, g);

@@ -17,10 +17,6 @@
 #include "pr_common.h"
 #include "mlp_tile.h"
 
-#ifndef PR_TRAINFWD_ABLATE
-#define PR_TRAINFWD_ABLATE 0    // timing builds only (training forward): 1 = no activation saves, 2 = no ReLU bit images, 4 = no batch statistics
-#endif
-
 #include <cstddef>
 
 #include <stdarg.h>
@@ -132,22 +128,20 @@ int compute_layout(const pr_object_model_t& m, const ModelDims& d, PackedLayout*
     off += seg_floats(d.Wpad / 32, d.W2pad);
     l->t_h6 = off;
     off += seg_floats(d.W2pad / 32, d.Fpad);
-    // ... and as bf16 triples (split-precision backward): 3 planes x 2 bytes per weight = 1.5 floats
-    auto take3 = [&](int nblk, int kpad) { const int at = off; off += seg_floats(nblk, kpad) / 2 * 3; return at; };
-    if (m.has_bender) {
-        for (int j = 1; j < m.bender_count; ++j) l->t3_b_act[j] = take3(d.BWpad / 32, d.BWpad);
-        l->t3_b_skip = take3(d.bin_pad / 32, d.BWpad);
-        l->t3_b_first = take3(d.bin_pad / 32, d.BWpad);
-    }
-    for (int i = 1; i < m.backbone_count; ++i) l->t3_n_act[i] = take3(d.Wpad / 32, d.Wpad);
-    l->t3_n_skip = take3(d.enc_pad / 32, d.Wpad);
-    l->t3_n_first = take3(d.enc_pad / 32, d.Wpad);
-    l->t3_h0 = take3(d.Wpad / 32, d.Wpad);
-    l->t3_h3 = take3(d.Wpad / 32, d.W2pad);
-    l->t3_h6 = take3(d.W2pad / 32, d.Fpad);
-    // forward segments of a training call's phase 1 in split precision: fp16 (hi, lo) fragment pairs, the layout of the split
-    // evaluation kernel (k_pack kind 2: the same number of bytes as the fp32 fragments)
+    // ... and as fp16 (hi, lo) fragment pairs of w x 2^8 (split-precision backward chains; k_pack kind 2: the same number of
+    // bytes as the fp32 fragments)
     auto take2 = [&](int nblk, int kpad) { const int at = off; off += seg_floats(nblk, kpad); return at; };
+    if (m.has_bender) {
+        for (int j = 1; j < m.bender_count; ++j) l->t3_b_act[j] = take2(d.BWpad / 32, d.BWpad);
+        l->t3_b_skip = take2(d.bin_pad / 32, d.BWpad);
+        l->t3_b_first = take2(d.bin_pad / 32, d.BWpad);
+    }
+    for (int i = 1; i < m.backbone_count; ++i) l->t3_n_act[i] = take2(d.Wpad / 32, d.Wpad);
+    l->t3_n_skip = take2(d.enc_pad / 32, d.Wpad);
+    l->t3_n_first = take2(d.enc_pad / 32, d.Wpad);
+    l->t3_h0 = take2(d.Wpad / 32, d.Wpad);
+    // forward segments of a training call's phase 1 in split precision: fp16 (hi, lo) fragment pairs, the layout of the split
+    // evaluation kernel
     if (m.has_bender) {
         const int nbb = d.BWpad / 32;
         for (int j = 0; j < m.bender_count; ++j) {
@@ -174,8 +168,7 @@ struct PackJob {
     const float* src;
     float* dst;
     int kind;       // 0 = fp32 fragment-ordered matrix segment, 1 = padded vector / raw row copy,
-                    // 2 = fp16 hi/lo split fragments (same byte size as kind 0), 3 = bf16 triples (1.5 x the size of kind 0; `count`
-                    // counts 32-bit words)
+                    // 2 = fp16 hi/lo split fragments (same byte size as kind 0)
     int in_total;   // row stride of src
     int col_off;
     int k_real, n_real, kq, nblk;
@@ -234,34 +227,6 @@ __global__ __launch_bounds__(256) void k_pack(PackJobs jobs) {
             }
             reinterpret_cast<unsigned int*>(j.dst)[idx] = (unsigned int)out[0] | ((unsigned int)out[1] << 16);
             continue;
-        } else if (j.kind == 3) {
-            // bf16 triples of a segment, w = b1 + b2 + b3 (each term what is left, rounded to the nearest bf16):
-            // word idx holds the elements e, e + 1 of [column block][K step of 16][plane][lane]; lane l carries
-            // W(n = nb*32 + (l & 31), k = 16 s + 8 (l >> 5) + e), e = 0..7 - the B fragment of v_mfma_f32_32x32x16_bf16
-            unsigned int out[2];
-            for (int t = 0; t < 2; ++t) {
-                const int h = idx * 2 + t;
-                const int e = h & 7;
-                const int lane = (h >> 3) & 63;
-                const int rest = h >> 9;
-                const int plane = rest % 3;
-                const int step = (rest / 3) % (j.kq >> 1);
-                const int nb = (rest / 3) / (j.kq >> 1);
-                const int n = nb * 32 + (lane & 31);
-                const int k = 16 * step + 8 * (lane >> 5) + e;
-                float w = 0.f;
-                if (n < j.n_real && k < j.k_real)
-                    w = j.transposed ? j.src[(size_t)k * j.in_total + j.col_off + n] : j.src[(size_t)n * j.in_total + j.col_off + k];
-                // (round to nearest, like the activations' split in the kernels)
-                const __bf16 b1 = (__bf16)w;
-                const float r1 = w - (float)b1;
-                const __bf16 b2 = (__bf16)r1;
-                const __bf16 b3 = (__bf16)(r1 - (float)b2);
-                const __bf16 sel = plane == 0 ? b1 : (plane == 1 ? b2 : b3);
-                out[t] = *reinterpret_cast<const unsigned short*>(&sel);
-            }
-            reinterpret_cast<unsigned int*>(j.dst)[idx] = out[0] | (out[1] << 16);
-            continue;
         } else {
             // rows of length kq (padded) from rows of length k_real; n_real rows
             const int row = idx / j.kq, c = idx % j.kq;
@@ -302,17 +267,12 @@ static int add_seg_t(PackJobs* js, const pr_linear_t& lin, int col_off, int k_re
 }
 
 // the same W^T segment for the split-precision backward chains: fp16 (hi, lo) pairs of w x 2^8 (kind 2; the chains scale their
-// gradient tiles into fp16's range, train_bwd.hip) - or bf16 triples (kind 3, -DPR_CHAIN_BF16: 1.5 x the bytes, six MFMAs per product)
+// gradient tiles into fp16's range, train_bwd.hip)
 static int add_seg_t3(PackJobs* js, const pr_linear_t& lin, int col_off, int k_real, int kpad, int n_real, int npad, float* dst) {
     PR_TRY(add_seg_t(js, lin, col_off, k_real, kpad, n_real, npad, dst));
     PackJob& j = js->job[js->n - 1];
-#ifdef PR_CHAIN_BF16
-    j.kind = 3;
-    j.count = j.count / 2 * 3;      // 32-bit words: two bf16 each, three planes
-#else
-    j.kind = 2;                     // (in the region sized for the triples)
+    j.kind = 2;
     j.scale_log2 = TRAIN_SPLIT_WEIGHT_SCALE_LOG2;
-#endif
     return PR_OK;
 }
 
@@ -432,8 +392,6 @@ static int build_pack_jobs(const pr_object_model_t& m, const ModelDims& d, const
     PR_TRY(add_seg_t3(js, m.backbone[m.skip_layer_idx], d.W, d.W, d.Wpad, d.enc, d.enc_pad, base + l.t3_n_skip));
     PR_TRY(add_seg_t3(js, m.backbone[0], 0, d.W, d.Wpad, d.enc, d.enc_pad, base + l.t3_n_first));
     PR_TRY(add_seg_t3(js, m.head0, 0, d.W, d.Wpad, d.W, d.Wpad, base + l.t3_h0));
-    PR_TRY(add_seg_t3(js, m.head3, 0, d.W2, d.W2pad, d.W, d.Wpad, base + l.t3_h3));
-    PR_TRY(add_seg_t3(js, m.head6, 0, d.F, d.Fpad, d.W2, d.W2pad, base + l.t3_h6));
     if (m.has_bender) {
         for (int j = 0; j < m.bender_count; ++j) {
             if (j == 0) {
@@ -733,11 +691,7 @@ __device__ __forceinline__ void mlp_tile_loop(const MlpParams& p) {
     // head: a claim at the top of a tile hoards - on a launch of ~2 tiles per workgroup (the evaluators' 11 520-ray frame:
     // 933 tiles on 512 workgroups) the first workgroups to reach an object took two of its tiles each, one after the other, while
     // a third of the chip had nothing left to take and left after one tile (1.08 ms for 0.7 ms of balanced work).
-#ifdef PR_MLP_STATIC_TILES
-    const bool dynamic_tiles = GROUP;     // measurement build: strided tile order
-#else
     const bool dynamic_tiles = GROUP || (!TRAIN && p.tile_counter != nullptr);
-#endif
     // (GROUP: the first claim was parked in LDS before the barrier that follows the head-weight staging)
     for (int tile = GROUP ? S.next_tile : (int)blockIdx.x; tile * TILE_M < total; tile = S.next_tile) {
         const int tile_base = tile * TILE_M;
@@ -746,9 +700,6 @@ __device__ __forceinline__ void mlp_tile_loop(const MlpParams& p) {
         if (GROUP && !TRAIN && tid == 0) g_mlp_trace[blockIdx.x][5 + (p.positions == 4 ? 0 : 1)] += 1;     // tiles of 4-position / other objects
 #endif
         int claimed = 0;
-#ifdef PR_MLP_EARLY_CLAIM
-        if (dynamic_tiles && tid == 0) claimed = atomicAdd(p.tile_counter, 1);      // measurement build: round 3's claim at the top of the tile
-#endif
         if (tid == 0) S.uniform_frame = 1;
         if (SPLIT && tid == 0) S.tile_max[0] = S.tile_max[1] = 0;
         // ---- load the sample records of the tile --------------------------------------------
@@ -780,9 +731,6 @@ __device__ __forceinline__ void mlp_tile_loop(const MlpParams& p) {
         }
         __syncthreads();
         if (tid < TILE_M && S.frame[tid] != S.frame[0]) S.uniform_frame = 0;   // visible after the next barrier
-#ifdef PR_MLP_EARLY_CLAIM
-        if (tid == 0) S.next_tile = GROUP ? claimed : (dynamic_tiles ? (int)gridDim.x + claimed : tile + (int)gridDim.x);   // read at the end of the tile
-#endif
         PR_PHASE(0);
 
         // ---- ray bender -----------------------------------------------------------------------
@@ -851,22 +799,20 @@ __device__ __forceinline__ void mlp_tile_loop(const MlpParams& p) {
         for (int l = 0; l < p.n_backbone; ++l) {
             if (TRAIN) {
                 run_layer<false, true, false, SPLIT>(p.layers[l], S, p, tile_base, /*input_kind=*/0, enc, nullptr,
-                                       (p.save_bits && !(PR_TRAINFWD_ABLATE & 2))
+                                       p.save_bits
                                            ? reinterpret_cast<unsigned long long*>(p.save_bits + (size_t)l * p.save_bits_stride) + (size_t)tile * p.Wpad
                                            : nullptr, nullptr, &cur);
             } else {
                 run_layer(p.layers[l], S, p, tile_base, /*input_kind=*/0, enc);
             }
             PR_PHASE(10);
-            if (TRAIN && p.save_act && !(PR_TRAINFWD_ABLATE & 1))
+            if (TRAIN && p.save_act)
                 write_tile_rows(S, p.save_act + (size_t)l * p.save_act_stride, p.Wpad, p.Wpad, tile_base, false);
             PR_PHASE(11);
         }
 
         PR_PHASE(15);
-#ifndef PR_MLP_EARLY_CLAIM
         if (dynamic_tiles && tid == 0) claimed = atomicAdd(p.tile_counter, 1);      // the next tile of this workgroup (see "Tile order")
-#endif
         // ---- sigma head -------------------------------------------------------------------------
         if (p.kind == 0) {
             for (int s = tid >> 3; s < TILE_M; s += MLP_THREADS / 8) {
@@ -886,9 +832,7 @@ __device__ __forceinline__ void mlp_tile_loop(const MlpParams& p) {
             }
         }
 
-#ifndef PR_MLP_EARLY_CLAIM
         if (tid == 0) S.next_tile = GROUP ? claimed : (dynamic_tiles ? (int)gridDim.x + claimed : tile + (int)gridDim.x);   // read at the end of the tile
-#endif
         PR_PHASE(7);
         // ---- style-modulated feature head -------------------------------------------------------
         if (!TRAIN && p.gate) {
@@ -906,7 +850,7 @@ __device__ __forceinline__ void mlp_tile_loop(const MlpParams& p) {
             // their per-channel sums feed the batch statistics
             Layer raw = p.layers[p.n_backbone];
             raw.epi = EPI_FEATURES;   // plain store into X
-            run_layer<false, false, true, SPLIT>(raw, S, p, tile_base, 0, enc, nullptr, nullptr, (PR_TRAINFWD_ABLATE & 4) ? nullptr : &cstats, &cur);
+            run_layer<false, false, true, SPLIT>(raw, S, p, tile_base, 0, enc, nullptr, nullptr, &cstats, &cur);
             PR_PHASE(12);
             if (tid < TILE_M && (S.flags[tid] & 1)) p.row_flags[tile_base + tid] = S.flags[tid];
             write_tile_rows(S, p.h_out, p.h_out_width, p.h_out_width, tile_base, /*zero_dead=*/false);
@@ -948,7 +892,6 @@ extern "C" int pr_debug_mlp_trace(unsigned long long* out) {
 
 __global__ __launch_bounds__(MLP_THREADS, MLP_BLOCKS_PER_CU) void k_mlp_mfma_train_group(MlpParams j0, MlpParams j1, MlpParams j2, MlpParams j3,
                                                                                          int count) {
-    pr_stagger(4);
     mlp_tile_loop<true, true>(j0);
     if (count > 1) mlp_tile_loop<true, true>(j1);
     if (count > 2) mlp_tile_loop<true, true>(j2);
@@ -958,7 +901,6 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_BLOCKS_PER_CU) void k_mlp_mfma_tra
 // phase 1 of a training call in split precision (PR_FLAG_SPLIT_BACKWARD): the same tile loop on fp16-pair segments (tile_products_f16x3_lean)
 __global__ __launch_bounds__(MLP_THREADS, MLP_BLOCKS_PER_CU) void k_mlp_mfma_train_group_split(MlpParams j0, MlpParams j1, MlpParams j2, MlpParams j3,
                                                                                               int count) {
-    pr_stagger(4);
     mlp_tile_loop<true, true, true>(j0);
     if (count > 1) mlp_tile_loop<true, true, true>(j1);
     if (count > 2) mlp_tile_loop<true, true, true>(j2);
@@ -970,9 +912,6 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_BLOCKS_PER_CU) void k_mlp_mfma_tra
 // GROUP: `first` is this workgroup's first tile of the object and comes back advanced by the object's tile count (mod grid): the
 // objects of a launch are dealt to the workgroups as ONE round-robin sequence - strided from the block index per object, the
 // workgroups 0 .. (tiles mod grid) of EVERY object took an extra tile (a few objects of a few hundred tiles each on 512 workgroups).
-#ifndef PR_HEADF_ABLATE
-#define PR_HEADF_ABLATE 0     // timing builds only (k_mlp_head*): 1 = no activation reads, 2 = no row write-out, 4 = no statistics flush
-#endif
 template <bool GROUP>
 __device__ __forceinline__ void mlp_head_loop(const MlpParams& p, int& first) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
@@ -1014,11 +953,7 @@ __device__ __forceinline__ void mlp_head_loop(const MlpParams& p, int& first) {
                     const int idx = base + q * MLP_THREADS;
                     const int row = idx < count ? idx / wq : 0, c = idx < count ? (idx - row * wq) * 4 : 0;
                     const int src = (tile_base + row < total) ? tile_base + row : tile_base;
-#if PR_HEADF_ABLATE & 1
-                    h[q] = make_float4(0.5f, 0.25f, -0.5f, 1.f);    // measurement build: no activation reads (results are wrong)
-#else
                     h[q] = *reinterpret_cast<const float4*>(p.h_in + (size_t)src * p.h_in_width + c);
-#endif
                     const float* tab = p.adain + (size_t)S.frame[row] * p.adain_stride + prev.adain_off;
                     g[q] = *reinterpret_cast<const float4*>(tab + c);
                     b[q] = *reinterpret_cast<const float4*>(tab + prev.nblk * 32 + c);
@@ -1040,9 +975,6 @@ __device__ __forceinline__ void mlp_head_loop(const MlpParams& p, int& first) {
         Layer raw = cur;
         raw.epi = EPI_FEATURES;   // plain store into X
         run_layer<false, false, true>(raw, S, p, tile_base, 0, enc, nullptr, nullptr, p.phase == 2 ? &cstats : nullptr);
-#if PR_HEADF_ABLATE & 2
-        __syncthreads();      // measurement build: no row write-out
-#else
         if (p.phase == 2) {
             write_tile_rows(S, p.h_out, p.h_out_width, p.h_out_width, tile_base, /*zero_dead=*/false);
             __syncthreads();
@@ -1050,11 +982,8 @@ __device__ __forceinline__ void mlp_head_loop(const MlpParams& p, int& first) {
             write_tile_rows(S, p.feat, p.F, p.F, tile_base, /*zero_dead=*/true);
             __syncthreads();
         }
-#endif
     }
-#if !(PR_HEADF_ABLATE & 4)
     if (p.phase == 2) flush_column_stats(cstats, p, cur.nblk);
-#endif
 }
 
 __global__ __launch_bounds__(MLP_THREADS, MLP_BLOCKS_PER_CU) void k_mlp_head(MlpParams p) {
@@ -1064,7 +993,6 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_BLOCKS_PER_CU) void k_mlp_head(Mlp
 // the same phase of several objects in one launch: a workgroup takes its strided share of every object's tiles in turn
 __global__ __launch_bounds__(MLP_THREADS, MLP_BLOCKS_PER_CU) void k_mlp_head_group(MlpParams j0, MlpParams j1, MlpParams j2, MlpParams j3,
                                                                                    int count) {
-    pr_stagger(1);
     int first = (int)blockIdx.x;
     mlp_head_loop<true>(j0, first);
     if (count > 1) mlp_head_loop<true>(j1, first);
@@ -1346,7 +1274,7 @@ int launch_mlp_group(const MlpParams* host_jobs, const int* max_rows, int count,
         const bool split3 = phase == 1 && host_jobs[begin].split3 != 0;
         for (int j = 0; j < n; ++j)
             PR_REQUIRE((host_jobs[begin + j].split3 != 0) == (host_jobs[begin].split3 != 0) && (phase == 1 || !host_jobs[begin + j].split3),
-                       "grouped MLP launch: bf16-triple segments belong to phase 1, for every job of the launch or none");
+                       "grouped MLP launch: fp16-pair segments belong to phase 1, for every job of the launch or none");
         const void* kernel = phase >= 2 ? reinterpret_cast<const void*>(k_mlp_head_group)
                                         : (phase == 1 ? (split3 ? reinterpret_cast<const void*>(k_mlp_mfma_train_group_split)
                                                                 : reinterpret_cast<const void*>(k_mlp_mfma_train_group))
@@ -1517,7 +1445,6 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_BLOCKS_PER_CU) void k_chain_bwd(Ch
         bool g_in_written = false;
         for (int l = c.count - 1; l >= 1; --l) {
             // the ReLU mask of this layer's input (layer l - 1's output) -> bits, visible after the barrier inside run_layer
-#if !(defined(PR_CHAIN_ABLATE) && (PR_CHAIN_ABLATE & 2))     // measurement builds: 2 = no mask bits, 1 = no gradient write-out
             if (c.bits) {
                 // the forward pass left the bit image of this tile and layer behind: 64 x (width / 8) contiguous bytes
                 const int bytes = TILE_M * (c.Wpad >> 3);
@@ -1537,7 +1464,6 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_BLOCKS_PER_CU) void k_chain_bwd(Ch
                 build_relu_mask_bits(reinterpret_cast<unsigned char*>(S.pos), c.acts + (size_t)(l - 1) * c.act_stride, c.Wpad, c.Wpad,
                                      tile_base, rows_valid);
             }
-#endif
             if (l == c.skip) {
                 e.gout = c.g_in; e.ldg = c.ld_in; e.accumulate = 0; e.n_real = c.in_real;
                 run_layer<true>(c.in0_skip, S, unused, tile_base, 0, enc, &e);
@@ -1546,9 +1472,7 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_BLOCKS_PER_CU) void k_chain_bwd(Ch
             e.gout = nullptr; e.n_real = c.W;
             run_layer<true>(c.act_layers[l], S, unused, tile_base, 0, enc, &e);
             // the pre-activation gradient of layer l - 1, for its weight-gradient product
-#if !(defined(PR_CHAIN_ABLATE) && (PR_CHAIN_ABLATE & 1))
             write_tile_rows(S, c.gstack + (size_t)(l - 1) * c.g_stride, c.Wpad, c.Wpad, tile_base, false);
-#endif
         }
         e.gout = c.g_in; e.ldg = c.ld_in; e.accumulate = g_in_written ? 1 : 0; e.n_real = c.in_real;
         run_layer<true>(c.in0_first, S, unused, tile_base, 0, enc, &e);
@@ -1674,17 +1598,15 @@ extern "C" int pr_probe_mfma_f32(int32_t iterations, int32_t random_operands, do
     PR_CHECK_HIP(hipEventCreate(&e0));
     PR_CHECK_HIP(hipEventCreate(&e1));
     hipStream_t s = (hipStream_t)stream;
-#ifndef PR_PROBE_WAVES
-#define PR_PROBE_WAVES 8   // the renderer's occupancy; 4 = one wave per SIMD (experiments)
-#endif
-    hipLaunchKernelGGL(pr::k_probe_mfma, dim3(cus), dim3(64 * PR_PROBE_WAVES), 0, s, 16, sink, random_operands);  // warm-up
+    constexpr int PROBE_WAVES = 8;     // waves per workgroup: the renderer's occupancy
+    hipLaunchKernelGGL(pr::k_probe_mfma, dim3(cus), dim3(64 * PROBE_WAVES), 0, s, 16, sink, random_operands);  // warm-up
     PR_CHECK_HIP(hipEventRecord(e0, s));
-    hipLaunchKernelGGL(pr::k_probe_mfma, dim3(cus), dim3(64 * PR_PROBE_WAVES), 0, s, iterations, sink, random_operands);
+    hipLaunchKernelGGL(pr::k_probe_mfma, dim3(cus), dim3(64 * PROBE_WAVES), 0, s, iterations, sink, random_operands);
     PR_CHECK_HIP(hipEventRecord(e1, s));
     PR_CHECK_HIP(hipEventSynchronize(e1));
     float ms = 0.f;
     PR_CHECK_HIP(hipEventElapsedTime(&ms, e0, e1));
-    const double flop = (double)cus * PR_PROBE_WAVES * (double)iterations * 8.0 * (2.0 * 32 * 32 * 2);
+    const double flop = (double)cus * PROBE_WAVES * (double)iterations * 8.0 * (2.0 * 32 * 32 * 2);
     *tflops = flop / (ms * 1e-3) / 1e12;
     if (milliseconds) *milliseconds = ms;
     PR_CHECK_HIP(hipEventDestroy(e0));

@@ -48,23 +48,6 @@ static_assert(sizeof(SmemH) * SBLOCKS_PER_CU <= 158 * 1024, "the workgroups of o
 static_assert(offsetof(SmemH, head_w) % 16 == 0 && offsetof(SmemH, Xh) % 16 == 0 && offsetof(SmemH, Xl) % 16 == 0,
               "16-byte LDS reads of the activation planes");
 
-#ifndef PR_SPLIT_ABLATE
-#define PR_SPLIT_ABLATE 0   // profiling builds only (results are wrong): 1 = every K step re-reads the operands of steps 0 / 1 (L1 hits: no L2 weight stream), 8 = no epilogue
-#endif
-#if PR_SPLIT_ABLATE & 64
-// phase timing build: thread 0 of every workgroup accumulates shader-clock deltas per phase
-__device__ unsigned long long g_phase_cycles[16];
-#define PR_PHASE_T0() unsigned long long _pt = __builtin_amdgcn_s_memtime()
-#define PR_PHASE(idx)                                                                      \
-    do {                                                                                   \
-        const unsigned long long _n = __builtin_amdgcn_s_memtime();                        \
-        if (threadIdx.x == 0) atomicAdd(&g_phase_cycles[idx], _n - _pt);                   \
-        _pt = _n;                                                                          \
-    } while (0)
-#else
-#define PR_PHASE_T0() do {} while (0)
-#define PR_PHASE(idx) do {} while (0)
-#endif
 #define PR_ACC_ROW(i) (((i) & 3) + 8 * ((i) >> 2))
 // a = activation fragment, w = weight fragment: D[feature][sample] += w (A operand) x a (B operand)
 #define PR_MFMA16(acc, a, w) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(w, a, acc, 0, 0, 0)
@@ -167,7 +150,6 @@ __device__ __forceinline__ void run_layer_h(const Layer& L, SmemH& S, const MlpP
     const int cbA = wave, cbB = wave + SWAVES;
     const bool active = cbA < nblk;
     const bool two = cbB < nblk;
-    PR_PHASE_T0();
     // accumulators: [column block A / B][row block 0 / 1]; the three partial products of a step go into the same one
     f32x16 mA0, mA1, mB0, mB1;
 #pragma unroll
@@ -191,7 +173,6 @@ __device__ __forceinline__ void run_layer_h(const Layer& L, SmemH& S, const MlpP
     }
     mA1 = mA0;
     mB1 = mB0;
-#ifndef PR_SPLIT_NO_ADAIN_PREFETCH
     // AdaIN table row of a one-frame tile: requested now, parked in LDS behind the K loop (2 VGPRs across the loop)
     const bool park = L.epi == EPI_ADAIN_RELU && S.uniform_frame != 0;
     float park_g = 0.f, park_b = 0.f;
@@ -200,9 +181,6 @@ __device__ __forceinline__ void run_layer_h(const Layer& L, SmemH& S, const MlpP
         park_g = tab[0];
         park_b = tab[nblk * 32];
     }
-#else
-    const bool park = false;
-#endif
     for (int sidx = 0; sidx < L.nseg; ++sidx) {
         const Seg& sg = L.seg[sidx];
         if (sg.src == 1 && sidx > 0) {
@@ -234,7 +212,7 @@ __device__ __forceinline__ void run_layer_h(const Layer& L, SmemH& S, const MlpP
             f16x8 bAhO = wpA[128], bAlO = wpA[192], bBhO = wpB[128], bBlO = wpB[192];
             __builtin_amdgcn_sched_barrier(0);
             for (int s = 0; s < ks; s += 2) {
-                const int se = (PR_SPLIT_ABLATE & 1) ? 0 : ((s + 2 < ks) ? s + 2 : s), so = (PR_SPLIT_ABLATE & 1) ? 1 : ((s + 3 < ks) ? s + 3 : s + 1);
+                const int se = (s + 2 < ks) ? s + 2 : s, so = (s + 3 < ks) ? s + 3 : s + 1;
                 PR_SPLIT3(mA0, ah0E, al0E, bAhE, bAlE);
                 PR_SPLIT3(mA1, ah1E, al1E, bAhE, bAlE);
                 PR_SPLIT3(mB0, ah0E, al0E, bBhE, bBlE);
@@ -272,7 +250,7 @@ __device__ __forceinline__ void run_layer_h(const Layer& L, SmemH& S, const MlpP
             f16x8 bAhO = wpA[128], bAlO = wpA[192];
             __builtin_amdgcn_sched_barrier(0);
             for (int s = 0; s < ks; s += 2) {
-                const int se = (PR_SPLIT_ABLATE & 1) ? 0 : ((s + 2 < ks) ? s + 2 : s), so = (PR_SPLIT_ABLATE & 1) ? 1 : ((s + 3 < ks) ? s + 3 : s + 1);
+                const int se = (s + 2 < ks) ? s + 2 : s, so = (s + 3 < ks) ? s + 3 : s + 1;
                 PR_SPLIT3(mA0, ah0E, al0E, bAhE, bAlE);
                 PR_SPLIT3(mA1, ah1E, al1E, bAhE, bAlE);
                 bAhE = wpA[(size_t)se * 128];
@@ -299,16 +277,12 @@ __device__ __forceinline__ void run_layer_h(const Layer& L, SmemH& S, const MlpP
         }
         __builtin_amdgcn_s_setprio(0);
     }
-    PR_PHASE(3);
-#ifndef PR_SPLIT_NO_ADAIN_PREFETCH
     if (park && (int)threadIdx.x < nblk * 32) {
         S.adain_g[threadIdx.x] = park_g;
         S.adain_b[threadIdx.x] = park_b;
     }
-#endif
     __syncthreads();  // every wave has finished reading the activation planes (and the parked table row is complete)
-    PR_PHASE(4);
-    if (active && !((PR_SPLIT_ABLATE & 8) && L.epi != EPI_FEATURES)) {
+    if (active) {
         for (int blk = 0; blk < (two ? 2 : 1); ++blk) {
             const int feat0 = (blk ? cbB : cbA) * 32 + 4 * half;   // first feature of this lane
             const f32x16& m0 = blk ? mB0 : mA0;   // samples 0..31
@@ -335,9 +309,7 @@ __device__ __forceinline__ void run_layer_h(const Layer& L, SmemH& S, const MlpP
             }
         }
     }
-    PR_PHASE(5);
     __syncthreads();
-    PR_PHASE(6);
 }
 
 // (re)computes a network input into columns [0, pad) of the activation planes (see fill_encoding in mlp.hip)
@@ -536,14 +508,9 @@ __device__ __forceinline__ void split_tile_loop(const MlpParams& p) {
     __syncthreads();
     int pending = 0;   // rows on this workgroup's pending stack (sigma-gated head)
     // dynamic tile order, as in k_mlp_mfma: further tiles are claimed from a device counter, one tile ahead
-#ifdef PR_MLP_STATIC_TILES
-    const bool dynamic_tiles = GROUP;
-#else
     const bool dynamic_tiles = GROUP || p.tile_counter != nullptr;
-#endif
     for (int tile = GROUP ? S.next_tile : (int)blockIdx.x; tile * STILE_M < total; tile = S.next_tile) {
         const int tile_base = tile * STILE_M;
-        PR_PHASE_T0();
         int claimed = 0;      // (claimed late, behind the backbone: see "Tile order" in mlp.hip)
         if (tid == 0) S.uniform_frame = 1;
         if (tid < STILE_M) {
@@ -573,7 +540,6 @@ __device__ __forceinline__ void split_tile_loop(const MlpParams& p) {
         }
         __syncthreads();
         if (tid < STILE_M && S.frame[tid] != S.frame[0]) S.uniform_frame = 0;
-        PR_PHASE(0);
 
         if (p.has_bender) {
             fill_bender_input_h(S, p);
@@ -605,13 +571,10 @@ __device__ __forceinline__ void split_tile_loop(const MlpParams& p) {
             }
             __syncthreads();
         }
-        PR_PHASE(1);
 
         fill_nerf_input_h(S, p);
         __syncthreads();
-        PR_PHASE(2);
         for (int l = 0; l < p.n_backbone; ++l) run_layer_h<TERMS>(p.layers[l], S, p, 0);
-        PR_PHASE(15);
         if (dynamic_tiles && tid == 0) claimed = atomicAdd(p.tile_counter, 1);
 
         if (p.kind == 0) {
@@ -633,15 +596,12 @@ __device__ __forceinline__ void split_tile_loop(const MlpParams& p) {
         }
 
         if (tid == 0) S.next_tile = GROUP ? claimed : (dynamic_tiles ? (int)gridDim.x + claimed : tile + (int)gridDim.x);   // read at the end of the tile
-        PR_PHASE(7);
         if (p.gate) {
             __syncthreads();   // the liveness bits are complete
             pending = gated_head_h<TERMS>(S, p, tile_base, pending);
-            PR_PHASE(8);
             continue;
         }
         for (int l = p.n_backbone; l < p.n_layers; ++l) run_layer_h<TERMS>(p.layers[l], S, p, 0);
-        PR_PHASE(15);
 
         // feature rows: the last layer staged an fp32 tile over the activation planes
         {
@@ -669,7 +629,6 @@ __device__ __forceinline__ void split_tile_loop(const MlpParams& p) {
             }
         }
         __syncthreads();
-        PR_PHASE(8);
     }
     if (p.gate) gated_head_flush_h<TERMS>(S, p, pending);
 }
@@ -677,11 +636,7 @@ __device__ __forceinline__ void split_tile_loop(const MlpParams& p) {
 __device__ __forceinline__ void claim_matrix_priority() {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     SmemH& S = *reinterpret_cast<SmemH*>(smem_raw);
-#ifdef PR_EQUAL_TILE_PRIORITY
-    if (threadIdx.x == 0) S.matrix_priority = 0;
-#else
     if (threadIdx.x == 0) S.matrix_priority = cu_arrival_parity();
-#endif
     // (published by the tile loop's first barrier)
 }
 
@@ -712,18 +667,6 @@ __global__ __launch_bounds__(STHREADS, SBLOCKS_PER_CU) void k_mlp_f16_group(MlpP
     if (count > 3) split_tile_loop<true, 1>(j3);
 }
 
-#if PR_SPLIT_ABLATE & 64
-// phase timing build: cumulative shader-clock Mcycles of thread 0 per phase, summed over the workgroups (100 MHz clock)
-static void dump_phase_cycles(hipStream_t s) {
-    unsigned long long now[16];
-    hipStreamSynchronize(s);
-    hipMemcpyFromSymbol(now, HIP_SYMBOL(g_phase_cycles), sizeof(now));
-    fprintf(stderr, "[split phases, cumulative Mcycles]");
-    for (int i = 0; i < 16; ++i) fprintf(stderr, " p%d=%.2f", i, (double)now[i] * 1e-6);
-    fprintf(stderr, "\n");
-}
-#endif
-
 int launch_mlp_split_group(const MlpParams* host_jobs, const int* max_rows, int count, int terms, hipStream_t s) {
     auto* const kernel = terms == 1 ? k_mlp_f16_group : k_mlp_split_group;
     PR_REQUIRE(count >= 1, "grouped MLP launch: no jobs");
@@ -747,9 +690,6 @@ int launch_mlp_split_group(const MlpParams* host_jobs, const int* max_rows, int 
         ProfileScope scope(0, s);
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(STHREADS), sizeof(SmemH), s, g.jobs[0], g.jobs[1], g.jobs[2], g.jobs[3], n);
         PR_LAUNCH_CHECK();
-#if PR_SPLIT_ABLATE & 64
-        dump_phase_cycles(s);
-#endif
     }
     return PR_OK;
 }
@@ -767,9 +707,6 @@ int launch_mlp_split(const MlpParams& p, int max_rows, int terms, hipStream_t s)
     ProfileScope scope(0, s);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(STHREADS), sizeof(SmemH), s, p);
     PR_LAUNCH_CHECK();
-#if PR_SPLIT_ABLATE & 64
-    dump_phase_cycles(s);
-#endif
     return PR_OK;
 }
 

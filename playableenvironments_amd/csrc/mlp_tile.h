@@ -49,11 +49,7 @@ __device__ __forceinline__ float pe_element(const float* v, int din, int enc, in
     const int fn = rem / din;
     const int ax = rem - fn * din;
     const float arg = __fmul_rn(ldexpf(1.0f, k), v[ax]);
-#ifdef PR_FAST_TRIG_ABLATION
-    float e = fn ? __cosf(arg) : __sinf(arg);
-#else
     float e = fn ? cosf(arg) : sinf(arg);
-#endif
     if (octave_weights) e = __fmul_rn(e, octave_weights[k]);
     return e;
 }
@@ -332,20 +328,13 @@ __device__ __forceinline__ void drain_chunk(const Drain& d, const float* X, int 
     // streamed once (the weight-gradient launch reads the stack from memory): non-temporal, so that the rows neither evict the weight
     // fragments from L2 nor wait for an L2 line - the loads of the following steps stand behind these stores in the wave's
     // request queue (one in-order counter on gfx9), and their waits end when the stores are acknowledged (measured: the NeRF chain
-    // of the step 1.105 -> 1.051 ms; -DPR_DRAIN_PLAIN is the plain-store measurement build)
-#ifdef PR_DRAIN_PLAIN
-    *as_global(reinterpret_cast<v4f*>(d.dst + (size_t)row * d.ld + c)) = v;
-#else
+    // of the step 1.105 -> 1.051 ms against plain stores)
     __builtin_nontemporal_store(v, as_global(reinterpret_cast<v4f*>(d.dst + (size_t)row * d.ld + c)));
-#endif
 }
 
 // The same write-out with the chunk index kept as a (row, column) cursor: drain_chunk's `idx / w4` is a division by a run-time value,
 // ~20 VALU instructions per K step of a loop whose VALU work (the operand split) is what bounds it; the cursor advances by
 // MLP_THREADS chunks per call with one carry (same chunks in the same order as drain_chunk(d, X, 0), (d, X, 1), ...)
-#ifndef PR_DRAIN_CURSOR
-#define PR_DRAIN_CURSOR 1   // 0: drain_chunk's division in every K step (A/B builds)
-#endif
 struct DrainCursor { int row, c4, drow, dc4; };
 __device__ __forceinline__ DrainCursor drain_begin(const Drain& d) {
     DrainCursor k;
@@ -360,11 +349,7 @@ __device__ __forceinline__ void drain_next(const Drain& d, const float* X, Drain
     const int c = 4 * k.c4;
     typedef float v4f __attribute__((ext_vector_type(4)));
     const v4f v = *reinterpret_cast<const v4f*>(X + row * LDX + c);
-#ifdef PR_DRAIN_PLAIN
-    *as_global(reinterpret_cast<v4f*>(d.dst + (size_t)row * d.ld + c)) = v;
-#else
     __builtin_nontemporal_store(v, as_global(reinterpret_cast<v4f*>(d.dst + (size_t)row * d.ld + c)));
-#endif
     k.c4 += k.dc4;
     k.row += k.drow;
     const int wrap = k.c4 >= d.w4 ? 1 : 0;
@@ -372,171 +357,19 @@ __device__ __forceinline__ void drain_next(const Drain& d, const float* X, Drain
     k.row += wrap;
 }
 
-// The same product in SPLIT precision (PR_FLAG_SPLIT_BACKWARD; `sg.w` then points at the bf16-triple packing of the segment,
-// k_pack kind 3): every fp32 operand as three bf16 terms, x = b1 + b2 + b3 exactly, a product as the six bf16 MFMAs whose terms
-// are >= 2^-16 of it (see k_gemm_tn_all_bf16 in gemm.hip) - 16 K-values retire in 6 x 32 cycles where the fp32 pipe needs
-// 8 x 64.  The operand tile stays fp32 in X (it is also the gradient that is written out): a lane reads its eight consecutive
-// K-values of a step (two 16-byte LDS reads) and splits them in registers, behind the MFMAs of the previous step.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-#define PR_MFMA_BF16(acc, a, b) acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc, 0, 0, 0)
-
-struct Frag3 { bf16x8 p[3]; };
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-// (plain v_sub_f32: hipcc packs adjacent subtractions into v_pk_add_f32, which is slow beside MFMAs)
-__device__ __forceinline__ float sub_f32(float a, float b) {
-    float r;
-    asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// two values -> their three bf16 terms (round to nearest even: v_cvt_pk_bf16_f32), x = b1 + b2 + b3 with |b2| <= 2^-9 |x|,
-// |b3| <= 2^-18 |x| and residuals of either sign - the dropped product terms are below one fp32 rounding and unbiased (with
-// truncated terms they were up to 2^-20 and all of one sign: a systematic error the float64 arbitration caught)
-__device__ __forceinline__ void split_pair(float x0, float x1, unsigned int& p1, unsigned int& p2, unsigned int& p3) {
-    const f32x2_t v = {x0, x1};
-    p1 = __builtin_bit_cast(unsigned int, __builtin_convertvector(v, bf16x2_t));
-    const f32x2_t r = {sub_f32(x0, __uint_as_float(p1 << 16)), sub_f32(x1, __uint_as_float(p1 & 0xffff0000u))};
-    p2 = __builtin_bit_cast(unsigned int, __builtin_convertvector(r, bf16x2_t));
-    const f32x2_t q = {sub_f32(r[0], __uint_as_float(p2 << 16)), sub_f32(r[1], __uint_as_float(p2 & 0xffff0000u))};
-    p3 = __builtin_bit_cast(unsigned int, __builtin_convertvector(q, bf16x2_t));
-}
-__device__ __forceinline__ Frag3 split_fragment(const float4& lo, const float4& hi) {
-    unsigned int a[4], b[4], c[4];
-    split_pair(lo.x, lo.y, a[0], b[0], c[0]);
-    split_pair(lo.z, lo.w, a[1], b[1], c[1]);
-    split_pair(hi.x, hi.y, a[2], b[2], c[2]);
-    split_pair(hi.z, hi.w, a[3], b[3], c[3]);
-    Frag3 f;
-    const u32x4 wa = {a[0], a[1], a[2], a[3]}, wb = {b[0], b[1], b[2], b[3]}, wc = {c[0], c[1], c[2], c[3]};
-    f.p[0] = __builtin_bit_cast(bf16x8, wa);
-    f.p[1] = __builtin_bit_cast(bf16x8, wb);
-    f.p[2] = __builtin_bit_cast(bf16x8, wc);
-    return f;
-}
-// six MFMAs of one 32 x 32 block, smallest terms first
-__device__ __forceinline__ void mfma6(f32x16& acc, const Frag3& x, const bf16x8& w1, const bf16x8& w2, const bf16x8& w3) {
-    PR_MFMA_BF16(acc, x.p[1], w2);
-    PR_MFMA_BF16(acc, x.p[0], w3);
-    PR_MFMA_BF16(acc, x.p[2], w1);
-    PR_MFMA_BF16(acc, x.p[0], w2);
-    PR_MFMA_BF16(acc, x.p[1], w1);
-    PR_MFMA_BF16(acc, x.p[0], w1);
-}
-
-// the six terms of the blocks of one step, block by block inside a term (consecutive MFMAs write different accumulators)
-#define PR_STEP_MFMAS(F0, F1, WA0, WA1, WA2, WB0, WB1, WB2)                                                                             \
-    do {                                                                                                                             \
-        if (two) {                                                                                                                   \
-            PR_MFMA_BF16(a00, F0.p[1], WA1); PR_MFMA_BF16(a01, F1.p[1], WA1); PR_MFMA_BF16(a10, F0.p[1], WB1); PR_MFMA_BF16(a11, F1.p[1], WB1); \
-            PR_MFMA_BF16(a00, F0.p[0], WA2); PR_MFMA_BF16(a01, F1.p[0], WA2); PR_MFMA_BF16(a10, F0.p[0], WB2); PR_MFMA_BF16(a11, F1.p[0], WB2); \
-            PR_MFMA_BF16(a00, F0.p[2], WA0); PR_MFMA_BF16(a01, F1.p[2], WA0); PR_MFMA_BF16(a10, F0.p[2], WB0); PR_MFMA_BF16(a11, F1.p[2], WB0); \
-            PR_MFMA_BF16(a00, F0.p[0], WA1); PR_MFMA_BF16(a01, F1.p[0], WA1); PR_MFMA_BF16(a10, F0.p[0], WB1); PR_MFMA_BF16(a11, F1.p[0], WB1); \
-            PR_MFMA_BF16(a00, F0.p[1], WA0); PR_MFMA_BF16(a01, F1.p[1], WA0); PR_MFMA_BF16(a10, F0.p[1], WB0); PR_MFMA_BF16(a11, F1.p[1], WB0); \
-            PR_MFMA_BF16(a00, F0.p[0], WA0); PR_MFMA_BF16(a01, F1.p[0], WA0); PR_MFMA_BF16(a10, F0.p[0], WB0); PR_MFMA_BF16(a11, F1.p[0], WB0); \
-        } else {                                                                                                                     \
-            PR_MFMA_BF16(a00, F0.p[1], WA1); PR_MFMA_BF16(a01, F1.p[1], WA1);                                                        \
-            PR_MFMA_BF16(a00, F0.p[0], WA2); PR_MFMA_BF16(a01, F1.p[0], WA2);                                                        \
-            PR_MFMA_BF16(a00, F0.p[2], WA0); PR_MFMA_BF16(a01, F1.p[2], WA0);                                                        \
-            PR_MFMA_BF16(a00, F0.p[0], WA1); PR_MFMA_BF16(a01, F1.p[0], WA1);                                                        \
-            PR_MFMA_BF16(a00, F0.p[1], WA0); PR_MFMA_BF16(a01, F1.p[1], WA0);                                                        \
-            PR_MFMA_BF16(a00, F0.p[0], WA0); PR_MFMA_BF16(a01, F1.p[0], WA0);                                                        \
-        }                                                                                                                            \
-    } while (0)
-
-__device__ __forceinline__ void tile_products_bf16(const Seg& sg, int nblk, const float* X, f32x16& a00, f32x16& a01, f32x16& a10,
-                                                   f32x16& a11, const Drain* drain = nullptr) {
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int r = lane & 31, half = lane >> 5;
-    const int cbA = wave, cbB = wave + MLP_WAVES;
-    if (cbA >= nblk) return;
-    const bool two = cbB < nblk;
-    __builtin_amdgcn_s_setprio(1);
-    const int ks = sg.kq >> 1;                       // K steps of 16 (even: the padded widths are multiples of 32)
-    const float* ap = X + r * LDX + 8 * half;
-    // [column block][step][plane][lane] fragments of 16 bytes
-    const auto* wpA = as_global(reinterpret_cast<const bf16x8*>(sg.w)) + (size_t)cbA * ks * 192 + lane;
-    const auto* wpB = as_global(reinterpret_cast<const bf16x8*>(sg.w)) + (size_t)(two ? cbB : cbA) * ks * 192 + lane;
-    // software pipeline with NAMED even / odd register sets (a rotating set costs a register copy per value and step: 6 moves
-    // per MFMA, measured): the MFMAs of a step run on fragments that were split during the previous step; while they execute, the
-    // raw operands of the next step (requested in front of them) are split - the conversions sit in the shadow of the MFMAs
-    float4 xl, xh, yl, yh;
-    xl = *reinterpret_cast<const float4*>(ap); xh = *reinterpret_cast<const float4*>(ap + 4);
-    yl = *reinterpret_cast<const float4*>(ap + 32 * LDX); yh = *reinterpret_cast<const float4*>(ap + 32 * LDX + 4);
-    Frag3 e0 = split_fragment(xl, xh), e1 = split_fragment(yl, yh), o0, o1;
-    bf16x8 ea0 = wpA[0], ea1 = wpA[64], ea2 = wpA[128], eb0 = wpB[0], eb1 = wpB[64], eb2 = wpB[128];
-    bf16x8 oa0, oa1, oa2, ob0 = eb0, ob1 = eb1, ob2 = eb2;
-    for (int s = 0; s < ks; s += 2) {
-        // ---- even step: request the odd step's operands, multiply the even fragments, split the odd ones
-        {
-            const float* an = ap + 16 * (s + 1);
-            xl = *reinterpret_cast<const float4*>(an); xh = *reinterpret_cast<const float4*>(an + 4);
-            yl = *reinterpret_cast<const float4*>(an + 32 * LDX); yh = *reinterpret_cast<const float4*>(an + 32 * LDX + 4);
-            const size_t at = (size_t)(s + 1) * 192;
-            oa0 = wpA[at]; oa1 = wpA[at + 64]; oa2 = wpA[at + 128];
-            ob0 = wpB[at]; ob1 = wpB[at + 64]; ob2 = wpB[at + 128];      // (unconditional: see wpB)
-            __builtin_amdgcn_sched_barrier(0);      // the requests stay in FRONT of the step's MFMAs (hipcc sank them behind: L2 latency exposed every step)
-            PR_STEP_MFMAS(e0, e1, ea0, ea1, ea2, eb0, eb1, eb2);
-            o0 = split_fragment(xl, xh); o1 = split_fragment(yl, yh);
-            if (drain) drain_chunk(*drain, X, s);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // ---- odd step
-        {
-            const int sn = (s + 2 < ks) ? s + 2 : s;
-            const float* an = ap + 16 * sn;
-            xl = *reinterpret_cast<const float4*>(an); xh = *reinterpret_cast<const float4*>(an + 4);
-            yl = *reinterpret_cast<const float4*>(an + 32 * LDX); yh = *reinterpret_cast<const float4*>(an + 32 * LDX + 4);
-            const size_t at = (size_t)sn * 192;
-            ea0 = wpA[at]; ea1 = wpA[at + 64]; ea2 = wpA[at + 128];
-            eb0 = wpB[at]; eb1 = wpB[at + 64]; eb2 = wpB[at + 128];
-            __builtin_amdgcn_sched_barrier(0);
-            PR_STEP_MFMAS(o0, o1, oa0, oa1, oa2, ob0, ob1, ob2);
-            e0 = split_fragment(xl, xh); e1 = split_fragment(yl, yh);
-            if (drain) drain_chunk(*drain, X, s + 1);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    __builtin_amdgcn_s_setprio(0);
-}
-
 // The FORWARD products of a split-precision training call (phase 1): operands as fp16 pairs, x = hi + lo (hi = fp16(x), lo =
 // fp16(x - hi): ~22 significant bits; forward activations are O(1) - the range that rules fp16 out for gradients is not an issue
 // here, and the split evaluation kernel passes the fp32 parity tolerance with this representation), a product as the THREE
-// v_mfma_f32_32x32x16_f16 hi x hi + hi x lo + lo x hi: half the matrix time and two thirds of the weight bytes of the bf16-triple
-// form, which the backward pass keeps (gradients need the fp32 exponent range).  `sg.w`: the segment as k_pack kind 2 fragments
+// v_mfma_f32_32x32x16_f16 hi x hi + hi x lo + lo x hi (the backward chains use the same form on tiles scaled into fp16's range:
+// tile_products_f16x3 below).  `sg.w`: the segment as k_pack kind 2 fragments
 // ([column block][K step][hi 64 lanes x 16 B | lo 64 lanes x 16 B]); the operand tile stays fp32 in X (it is what gets saved) and
 // is split in registers at the top of every step from the raw operands requested during the previous one (one converted set: the
 // forward carries its input encoding and its batch-statistics sums in registers across the layers).
 typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
-#ifndef PR_TRAIN_SPLIT_SCALE
-#define PR_TRAIN_SPLIT_SCALE 8
-#endif
-constexpr int TRAIN_SPLIT_WEIGHT_SCALE_LOG2 = PR_TRAIN_SPLIT_SCALE;    // the packed fp16 pairs hold w x 2^8 (add_seg3 in mlp.hip)
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+constexpr int TRAIN_SPLIT_WEIGHT_SCALE_LOG2 = 8;    // the packed fp16 pairs hold w x 2^8 (add_seg3 in mlp.hip)
 #define PR_MFMA_F16(acc, a, b) acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, acc, 0, 0, 0)
 struct FragH { f16x8_t hi, lo; };
-__device__ __forceinline__ void split_pair_h(float x0, float x1, unsigned int& ph, unsigned int& pl) {
-    // fp16 range guard (never reached by sane activations; the split evaluation kernel has the same one)
-    const f32x2_t v = {__builtin_amdgcn_fmed3f(x0, -65504.0f, 65504.0f), __builtin_amdgcn_fmed3f(x1, -65504.0f, 65504.0f)};
-    const f16x2_t h = __builtin_convertvector(v, f16x2_t);
-    const f32x2_t back = __builtin_convertvector(h, f32x2_t);
-    const f32x2_t r = {sub_f32(v[0], back[0]), sub_f32(v[1], back[1])};
-    ph = __builtin_bit_cast(unsigned int, h);
-    pl = __builtin_bit_cast(unsigned int, __builtin_convertvector(r, f16x2_t));
-}
-__device__ __forceinline__ FragH split_fragment_h(const float4& lo, const float4& hi) {
-    unsigned int a[4], b[4];
-    split_pair_h(lo.x, lo.y, a[0], b[0]);
-    split_pair_h(lo.z, lo.w, a[1], b[1]);
-    split_pair_h(hi.x, hi.y, a[2], b[2]);
-    split_pair_h(hi.z, hi.w, a[3], b[3]);
-    FragH f;
-    const u32x4 wa = {a[0], a[1], a[2], a[3]}, wb = {b[0], b[1], b[2], b[3]};
-    f.hi = __builtin_bit_cast(f16x8_t, wa);
-    f.lo = __builtin_bit_cast(f16x8_t, wb);
-    return f;
-}
 // the three terms of the blocks of one step, smallest first, block by block inside a term
 #define PR_STEP_MFMAS_H(F0, F1, WAH, WAL, WBH, WBL)                                                                          \
     do {                                                                                                                    \
@@ -549,36 +382,6 @@ __device__ __forceinline__ FragH split_fragment_h(const float4& lo, const float4
     } while (0)
 
 __device__ __forceinline__ FragH split_fragment_scaled_h(const float4& lo, const float4& hi, float scale);
-// timing builds only (results are wrong): PR_LEAN_ABLATE 1 = every step reads the first step's weight fragments, 2 = no operand
-// conversions, 4 = a third of the MFMAs
-#ifndef PR_LEAN_ABLATE
-#define PR_LEAN_ABLATE 0
-#endif
-#if PR_LEAN_ABLATE & 1
-#define PR_LEAN_WSTEP(s) ((s) & 1)
-#else
-#define PR_LEAN_WSTEP(s) (s)
-#endif
-#if PR_LEAN_ABLATE & 2
-__device__ __forceinline__ FragH raw_fragment_h(const float4& lo, const float4& hi) {
-    FragH f;
-    f.hi = __builtin_bit_cast(f16x8_t, lo);
-    f.lo = __builtin_bit_cast(f16x8_t, hi);
-    return f;
-}
-#define PR_LEAN_SPLIT(l, h) raw_fragment_h(l, h)
-#else
-#define PR_LEAN_SPLIT(l, h) split_fragment_scaled_h(l, h, scale)
-#endif
-#if PR_LEAN_ABLATE & 4
-#define PR_LEAN_MFMAS(F0, F1, WAH, WAL, WBH, WBL)                                  \
-    do {                                                                          \
-        PR_MFMA_F16(a00, F0.lo, WAH); PR_MFMA_F16(a01, F1.hi, WAL);               \
-        if (two) { PR_MFMA_F16(a10, F0.hi, WBH); PR_MFMA_F16(a11, F1.lo, WBL); }  \
-    } while (0)
-#else
-#define PR_LEAN_MFMAS(F0, F1, WAH, WAL, WBH, WBL) PR_STEP_MFMAS_H(F0, F1, WAH, WAL, WBH, WBL)
-#endif
 __device__ __forceinline__ void tile_products_f16x3_lean(const Seg& sg, int nblk, const float* X, f32x16& a00, f32x16& a01, f32x16& a10,
                                                          f32x16& a11, float scale) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -600,28 +403,28 @@ __device__ __forceinline__ void tile_products_f16x3_lean(const Seg& sg, int nblk
     f16x8_t oah, oal, obh = ebh, obl = ebl;
     for (int s = 0; s < ks; s += 2) {
         {
-            const FragH f0 = PR_LEAN_SPLIT(xl, xh), f1 = PR_LEAN_SPLIT(yl, yh);
+            const FragH f0 = split_fragment_scaled_h(xl, xh, scale), f1 = split_fragment_scaled_h(yl, yh, scale);
             const float* an = ap + 16 * (s + 1);
             xl = *reinterpret_cast<const float4*>(an); xh = *reinterpret_cast<const float4*>(an + 4);
             yl = *reinterpret_cast<const float4*>(an + 32 * LDX); yh = *reinterpret_cast<const float4*>(an + 32 * LDX + 4);
-            const size_t at = (size_t)PR_LEAN_WSTEP(s + 1) * 128;
+            const size_t at = (size_t)(s + 1) * 128;
             oah = wpA[at]; oal = wpA[at + 64];
             obh = wpB[at]; obl = wpB[at + 64];      // (unconditional: see wpB)
             __builtin_amdgcn_sched_barrier(0);      // the requests stay in front of the step's MFMAs
-            PR_LEAN_MFMAS(f0, f1, eah, eal, ebh, ebl);
+            PR_STEP_MFMAS_H(f0, f1, eah, eal, ebh, ebl);
             __builtin_amdgcn_sched_barrier(0);
         }
         {
-            const FragH f0 = PR_LEAN_SPLIT(xl, xh), f1 = PR_LEAN_SPLIT(yl, yh);
+            const FragH f0 = split_fragment_scaled_h(xl, xh, scale), f1 = split_fragment_scaled_h(yl, yh, scale);
             const int sn = (s + 2 < ks) ? s + 2 : s;
             const float* an = ap + 16 * sn;
             xl = *reinterpret_cast<const float4*>(an); xh = *reinterpret_cast<const float4*>(an + 4);
             yl = *reinterpret_cast<const float4*>(an + 32 * LDX); yh = *reinterpret_cast<const float4*>(an + 32 * LDX + 4);
-            const size_t at = (size_t)PR_LEAN_WSTEP(sn) * 128;
+            const size_t at = (size_t)sn * 128;
             eah = wpA[at]; eal = wpA[at + 64];
             ebh = wpB[at]; ebl = wpB[at + 64];
             __builtin_amdgcn_sched_barrier(0);
-            PR_LEAN_MFMAS(f0, f1, oah, oal, obh, obl);
+            PR_STEP_MFMAS_H(f0, f1, oah, oal, obh, obl);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -632,9 +435,6 @@ __device__ __forceinline__ void tile_products_f16x3_lean(const Seg& sg, int nblk
 // that its largest entry sits just under 2^15: gradients of ~1e-7 are far below fp16's range) while it is split; the caller
 // multiplies the accumulators by 1 / (scale x 2^TRAIN_SPLIT_WEIGHT_SCALE_LOG2) behind the loop.  Entries within 2^-16 of the tile's
 // largest keep 22 significant bits, smaller ones an absolute error of 2^-39 of it.  With the gradient write-out of tile_products.
-#ifndef PR_SPLIT_MIX
-#define PR_SPLIT_MIX 1      // 0: the multiply / clamp / convert / convert back / subtract / convert sequence (A/B builds)
-#endif
 // Four operands x `scale` -> their packed fp16 hi halves (h01, h23) and lo halves (l01, l23) in EIGHT instructions: v_fma_mixlo/hi_f16
 // evaluate x * scale + c in fp32 and round the result to fp16 into one half of the destination, and take c as either half of a packed
 // fp16 register.  hi = fp16(x * scale) (the product by a power of two is exact), lo = fp16(x * scale - hi) (the difference has <= 13
@@ -660,7 +460,6 @@ __device__ __forceinline__ void split_quad_scaled_h(float x0, float x1, float x2
         : "v"(x0), "v"(x1), "v"(x2), "v"(x3), "v"(scale));
 }
 __device__ __forceinline__ FragH split_fragment_scaled_h(const float4& lo, const float4& hi, float scale) {
-#if PR_SPLIT_MIX
     unsigned int a[4], b[4];
     split_quad_scaled_h(lo.x, lo.y, lo.z, lo.w, scale, a[0], a[1], b[0], b[1]);
     split_quad_scaled_h(hi.x, hi.y, hi.z, hi.w, scale, a[2], a[3], b[2], b[3]);
@@ -669,11 +468,6 @@ __device__ __forceinline__ FragH split_fragment_scaled_h(const float4& lo, const
     f.hi = __builtin_bit_cast(f16x8_t, wa);
     f.lo = __builtin_bit_cast(f16x8_t, wb);
     return f;
-#else
-    const float4 l = make_float4(lo.x * scale, lo.y * scale, lo.z * scale, lo.w * scale);
-    const float4 h = make_float4(hi.x * scale, hi.y * scale, hi.z * scale, hi.w * scale);
-    return split_fragment_h(l, h);
-#endif
 }
 __device__ __forceinline__ void tile_products_f16x3(const Seg& sg, int nblk, const float* X, f32x16& a00, f32x16& a01, f32x16& a10,
                                                     f32x16& a11, const Drain* drain, float scale) {
@@ -705,7 +499,7 @@ __device__ __forceinline__ void tile_products_f16x3(const Seg& sg, int nblk, con
             __builtin_amdgcn_sched_barrier(0);
             PR_STEP_MFMAS_H(e0, e1, eah, eal, ebh, ebl);
             o0 = split_fragment_scaled_h(xl, xh, scale); o1 = split_fragment_scaled_h(yl, yh, scale);
-            if (drain) { if (PR_DRAIN_CURSOR) drain_next(*drain, X, cursor); else drain_chunk(*drain, X, s); }
+            if (drain) drain_next(*drain, X, cursor);
             __builtin_amdgcn_sched_barrier(0);
         }
         {
@@ -719,7 +513,7 @@ __device__ __forceinline__ void tile_products_f16x3(const Seg& sg, int nblk, con
             __builtin_amdgcn_sched_barrier(0);
             PR_STEP_MFMAS_H(o0, o1, oah, oal, obh, obl);
             e0 = split_fragment_scaled_h(xl, xh, scale); e1 = split_fragment_scaled_h(yl, yh, scale);
-            if (drain) { if (PR_DRAIN_CURSOR) drain_next(*drain, X, cursor); else drain_chunk(*drain, X, s + 1); }
+            if (drain) drain_next(*drain, X, cursor);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -780,9 +574,6 @@ __device__ __forceinline__ void run_layer(const Layer& L, Smem& S, const MlpPara
         }
         if (SPLIT && threadIdx.x == 0) S.tile_max[slot ^ 1] = 0;       // the next producer's word (nobody reads it any more)
         if (!active) continue;
-#if defined(PR_MLP_ABLATE) && (PR_MLP_ABLATE & 128)
-        continue;   // measurement build: no matrix work (results are wrong)
-#endif
         if (SPLIT) {             // phase 1 of a training call with PR_FLAG_SPLIT_BACKWARD: fp16 pairs
             PR_PHASE_COUNT(8, 1000000ull * (sg.kq >> 1));       // K steps of 16 (read as p8 x 1e6)
             PR_PHASE_COUNT(9, 1000000ull);                      // products
@@ -874,9 +665,6 @@ __device__ __forceinline__ void run_layer(const Layer& L, Smem& S, const MlpPara
             a11[i] *= back;
         }
     }
-#if defined(PR_MLP_ABLATE) && (PR_MLP_ABLATE & 4)
-    return;   // measurement build: no barriers, no epilogue (results are wrong)
-#endif
     PR_PHASE(3);
     if (BWD) {
         // Backward chain (k_chain_bwd): the tile holds d loss / d pre-activation of a layer, the product is its input
@@ -943,11 +731,7 @@ __device__ __forceinline__ void run_layer(const Layer& L, Smem& S, const MlpPara
     }
     __syncthreads();  // every wave has finished reading X
     PR_PHASE(4);
-#if defined(PR_MLP_ABLATE) && (PR_MLP_ABLATE & 8)
-    if (false) {   // measurement build: no epilogue (results are wrong)
-#else
     if (active) {
-#endif
         for (int blk = 0; blk < (two ? 2 : 1); ++blk) {
             const int col = (blk ? cbB : cbA) * 32 + r;
             const f32x16& lo = blk ? a10 : a00;   // rows 0..31

@@ -42,29 +42,6 @@ constexpr int MLP_WAVES = 4;      // 256 threads; every wave owns two 32-column 
 constexpr int MLP_BLOCKS_PER_CU = 2;   // two independent tiles per CU (LDS ~70 KB each): one computes while the other
                                        // is in a prologue / epilogue / barrier
 constexpr int MLP_THREADS = MLP_WAVES * 64;
-// measurement builds only: delay every second workgroup (rule 1: the second half of the grid; 2: bit 3 of the block index) at launch
-#ifndef PR_STAGGER_RULE
-#define PR_STAGGER_RULE 0
-#endif
-#ifndef PR_STAGGER_KERNELS
-#define PR_STAGGER_KERNELS 0      // 1 head forward phases, 2 head backward phases, 4 phase 1 of the training forward
-#endif
-#ifndef PR_STAGGER_SLEEPS
-#define PR_STAGGER_SLEEPS 2       // x 127 x 64 clocks (~3.4 us each)
-#endif
-__device__ __forceinline__ void pr_stagger(int kernel_bit) {
-#if PR_STAGGER_RULE != 0
-    if (!(PR_STAGGER_KERNELS & kernel_bit)) return;
-    const unsigned b = blockIdx.x;
-    const bool late = PR_STAGGER_RULE == 1 ? (b >= gridDim.x / 2) : (((b >> 3) & 1u) != 0u);
-    if (late) {
-#pragma unroll 1
-        for (int i = 0; i < PR_STAGGER_SLEEPS; ++i) __builtin_amdgcn_s_sleep(127);
-    }
-#else
-    (void)kernel_bit;
-#endif
-}
 
 // A device pointer that reaches a kernel through a table (a Layer / Seg copied out of the kernel arguments, a pointer chosen at run
 // time) has lost its address space: hipcc then emits flat_load, and - because a flat access may also be an LDS access - waits for
@@ -151,12 +128,12 @@ struct PackedLayout {
     int t_b_act[PR_MAX_LAYERS], t_b_skip, t_b_first;   // bender chain: W_l[:, :BW]^T (l >= 1), W_skip[:, BW:]^T, W_0^T
     int t_n_act[PR_MAX_LAYERS], t_n_skip, t_n_first;   // NeRF backbone chain
     int t_h0, t_h3, t_h6;                              // head0^T (W -> W), head3^T (W/2 -> W), head6^T (F -> W/2)
-    // the same transposed segments as bf16 TRIPLES (PR_FLAG_SPLIT_BACKWARD): w = b1 + b2 + b3, fragments of v_mfma_f32_32x32x16_bf16
-    // - [column block][16-wide K step][plane][64 lanes][8 bf16] - 1.5 x the floats of the fp32 segment
+    // the chains' transposed segments as fp16 (hi, lo) pairs of w x 2^8 (PR_FLAG_SPLIT_BACKWARD): fragments of
+    // v_mfma_f32_32x32x16_f16 - [column block][16-wide K step][hi | lo][64 lanes][8 halves] - the floats of the fp32 segment
     int t3_b_act[PR_MAX_LAYERS], t3_b_skip, t3_b_first;
     int t3_n_act[PR_MAX_LAYERS], t3_n_skip, t3_n_first;
-    int t3_h0, t3_h3, t3_h6;
-    // ... and the FORWARD segments of phase 1 of a training call (ray bender, backbone, head layer 0) as bf16 triples
+    int t3_h0;
+    // ... and the FORWARD segments of phase 1 of a training call (ray bender, backbone, head layer 0) as fp16 (hi, lo) pairs
     int b_seg3[PR_MAX_LAYERS][2], n_seg3[PR_MAX_LAYERS][2], h0_3;
     int total;
 };
@@ -245,7 +222,7 @@ struct MlpParams {
     int32_t* pend_meta;          // (MAX_RESIDENT_TILES, TILE_M, 2) [compact feature row, frame] of the pending rows
     int32_t* head_count;         // device counter: rows sent through the feature head (NULL = not counted)
     int32_t* tile_counter;       // zeroed device counter: tiles beyond the first of a workgroup are claimed from it (NULL: strided)
-    int split3;                  // 1 (phase 1 of a training call): the layer segments are bf16-triple packings (six bf16 MFMAs per product)
+    int split3;                  // 1 (phase 1 of a training call): the layer segments are fp16 (hi, lo) pair packings (three fp16 MFMAs per product)
     // outputs
     float* sigma;                // dense (N,R,P)
     float* dispmag;              // dense (N,R,P) or NULL
@@ -591,7 +568,7 @@ struct HeadBwdJob {                 // feature-head backward, phase 1 (head laye
     double* sums;                   // [sum d x_hat (ld) | sum d x_hat x_hat (ld)], zeroed by the caller
     float* dscale; float* dbias;    // (frames, MAX_WIDTH) d loss / d AdaIN scale / bias, zeroed by the caller
     int32_t* tile_counter;          // zeroed
-    int split;                      // 1: `wt` is the bf16-triple packing of the segment, the product runs on six bf16 MFMAs
+    int split;                      // unused: the head phases' products are exact fp32 in every call
 };
 int launch_head_bwd_group(const HeadBwdJob* jobs, const long* max_rows, int count, hipStream_t s);
 
@@ -616,17 +593,14 @@ struct ChainBwdJob {                // backward chain of a ReLU MLP with one ski
     float* gstack; size_t g_stride; // out: pre-activation gradients of layers 0 .. count - 1, (cap, Wpad) each
     float* g_in; int ld_in;         // out: gradient of the network input (cap, ld_in)
     int32_t* tile_counter;          // zeroed
-    int split;                      // 1: the segments are bf16-triple packings, every product runs on six bf16 MFMAs
+    int split;                      // 2: the segments are fp16 (hi, lo) pair packings of w x 2^8 (t3_*), three fp16 MFMAs per product
 };
 int launch_chain_bwd_group(const ChainBwdJob* jobs, const long* max_rows, int count, hipStream_t s);
 
 // Every weight-gradient product of a backward pass in one launch (k_gemm_tn_all in gemm.hip): the products of all layers of
 // all objects as (job, split of TN_ALL_CHUNK sample rows, 128 x 128 tile) work items of a persistent grid.
 constexpr int TN_ALL_MAX = 96;         // jobs per launch
-#ifndef PR_TNALL_CHUNK
-#define PR_TNALL_CHUNK 2048
-#endif
-constexpr int TN_ALL_CHUNK = PR_TNALL_CHUNK;     // sample rows per split
+constexpr int TN_ALL_CHUNK = 2048;     // sample rows per split
 constexpr int TN_ALL_TILES = 6;        // claim slots per (job, split): the tiles of the largest gradient (256 x 384)
 struct TnJob {             // C[ni x nj] += sum_m A[m][i] B[m][j] ; bias[i] += sum_m A[m][i]
     const float* A; const float* B;
@@ -647,7 +621,7 @@ struct TnAll {
     TnJob job[TN_ALL_MAX];
     int count;
     int32_t* counters;                 // 8 zeroed ints: the per-XCD claim counters
-    int split_precision;               // 1: operands as fp16 pairs of scaled half slabs (k_gemm_tn_all_f16; -DPR_TNALL_F16=0: bf16 triples)
+    int split_precision;               // 1: operands as fp16 pairs of scaled half slabs (k_gemm_tn_all_f16)
 };
 size_t tn_all_partial_floats(int ni, int nj, long max_rows);
 int launch_gemm_tn_all(TnAll& g, const long* max_rows, hipStream_t s);

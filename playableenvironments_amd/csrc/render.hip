@@ -272,20 +272,12 @@ int make_plan(const pr_call_t& c, const pr_object_t* objs, Plan* plan) {
 
 // Evaluation calls run the objects of a model type as ONE grouped launch (k_mlp_mfma_group / k_mlp_split_group).
 bool group_active(const pr_call_t& c) {
-#ifdef PR_MLP_UNGROUPED
-    return false;      // measurement build: one launch per object
-#else
     return !(c.flags & (PR_FLAG_TRAIN_BN | PR_FLAG_SAVE_FOR_BACKWARD | PR_FLAG_NAIVE_MLP)) && c.objects > 1;
-#endif
 }
 
 // Differentiable calls (everything saved per object) with several objects: phase 1 of the phased launches is grouped as well.
 bool group_train_active(const pr_call_t& c) {
-#ifdef PR_MLP_UNGROUPED
-    return false;
-#else
     return (c.flags & PR_FLAG_SAVE_FOR_BACKWARD) && !(c.flags & PR_FLAG_NAIVE_MLP) && c.objects > 1;
-#endif
 }
 
 void bbox_split(const pr_object_model_t& m, float* lo, float* hi, float* size) {
@@ -498,7 +490,7 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_outputs_
 
             MlpParams mp;
             memset(&mp, 0, sizeof(mp));
-            // training calls with PR_FLAG_SPLIT_BACKWARD: phase 1 of the grouped launches reads the bf16-triple packings
+            // training calls with PR_FLAG_SPLIT_BACKWARD: phase 1 of the grouped launches reads the fp16-pair packings
             const bool split3 = train_grouped && (c.flags & PR_FLAG_SPLIT_BACKWARD) && (c.flags & PR_FLAG_SAVE_FOR_BACKWARD);
             PR_TRY(build_mlp_layers(m, d, l, packed, &mp, split3));
             mp.rec_pos = rec_pos; mp.rec_flat = rec_flat; mp.total = totals + k;

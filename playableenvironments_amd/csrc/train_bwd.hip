@@ -33,12 +33,6 @@ struct BSmem {
 static_assert(sizeof(BSmem) * MLP_BLOCKS_PER_CU <= 160 * 1024 - MLP_BLOCKS_PER_CU * 1024, "two backward tiles per CU");
 static_assert(offsetof(BSmem, cst) % 16 == 0 && offsetof(BSmem, ws) % 16 == 0, "16-byte LDS accesses");
 
-#ifndef PR_HEADB_ABLATE
-#define PR_HEADB_ABLATE 0       // timing builds only (k_head_bwd_group): 1 = no raw-activation prefetch, 2 = no a_out stores, 4 = no d_out rows,
-#endif                          // 8 = no MFMA, 16 = no operand load from memory, 32 = no statistics atomics
-#ifndef PR_CHAINGRP_ABLATE
-#define PR_CHAINGRP_ABLATE 0    // timing builds only (k_chain_bwd_group): 1 = no gradient write-out, 2 = no mask bits, 4 = no MFMA
-#endif
 #ifdef PR_CHAIN_TIMING
 // phase timing build: thread 0 of every workgroup accumulates shader-clock deltas per phase of k_chain_bwd_group
 __device__ unsigned long long g_chain_phase[16];
@@ -81,13 +75,7 @@ __device__ __forceinline__ void zero4(f32x16& a, f32x16& b, f32x16& c, f32x16& d
 // loop iteration (a tile of width Wpad has Wpad / 16 chunks per thread and the loop Wpad / 16 iterations), so that the 64 KB of a
 // tile reach the memory system spread over the K loop instead of as one burst in front of it.
 // every wave runs the loop (so every thread drains its chunks) when the product has at least MLP_WAVES column blocks
-__device__ __forceinline__ bool drains_in_loop(int nblk) {
-#ifdef PR_NO_DRAIN
-    return false;
-#else
-    return nblk >= MLP_WAVES;
-#endif
-}
+__device__ __forceinline__ bool drains_in_loop(int nblk) { return nblk >= MLP_WAVES; }
 
 // DRAIN is a template parameter: tested inside the loop (a pointer compare and a branch) it ended the basic block in front of the
 // scheduling groups, and hipcc issued all 32 MFMAs of an iteration first and the operand requests of the next one behind them
@@ -99,7 +87,6 @@ __device__ __forceinline__ void tile_products_loop(const Seg& sg, int nblk, cons
     const int cbA = wave, cbB = wave + MLP_WAVES;
     if (cbA >= nblk) return;
     const bool two = cbB < nblk;
-    if (PR_CHAINGRP_ABLATE & 4) return;
     __builtin_amdgcn_s_setprio(1);
     const int kq = sg.kq;
     const float* ap = X + r * LDX + half * 4 * kq;
@@ -191,12 +178,11 @@ __device__ __forceinline__ void tile_products(const Seg& sg, int nblk, const flo
     else tile_products_loop<false>(sg, nblk, X, a00, a01, a10, a11, nullptr);
 }
 
-// MODE 0: exact fp32; 1: bf16 triples; 2: fp16 pairs of the operand x `scale` (chain_bwd_loop: per-tile power-of-two scales)
+// MODE 0: exact fp32; 2: fp16 pairs of the operand x `scale` (chain_bwd_loop: per-tile power-of-two scales)
 template <int MODE>
 __device__ __forceinline__ void tile_products_any(const Seg& sg, int nblk, const float* X, f32x16& a00, f32x16& a01, f32x16& a10,
                                                   f32x16& a11, const Drain* drain = nullptr, float scale = 1.0f) {
     if (MODE == 2) tile_products_f16x3(sg, nblk, X, a00, a01, a10, a11, drain, scale);
-    else if (MODE == 1) tile_products_bf16(sg, nblk, X, a00, a01, a10, a11, drain);
     else tile_products(sg, nblk, X, a00, a01, a10, a11, drain);
 }
 
@@ -209,11 +195,7 @@ __device__ __forceinline__ void store_tile_rows(const float* X, float* dst, int 
         const int row = idx / w4, c = (idx - row * w4) * 4;
         if (row < rows_valid) {
             const f32x4_t v = *reinterpret_cast<const f32x4_t*>(X + row * LDX + c);
-#ifdef PR_STORE_ROWS_NT      // measurement build (no difference for the head phases' rows)
-            __builtin_nontemporal_store(v, reinterpret_cast<f32x4_t*>(dst + (size_t)(tile_base + row) * ld + c));
-#else
             *reinterpret_cast<f32x4_t*>(dst + (size_t)(tile_base + row) * ld + c) = v;
-#endif
         }
     }
 }
@@ -246,7 +228,6 @@ __device__ __forceinline__ void store_masked(BSmem& S, int nblk, const ColMasks&
         const f32x16& hi = blk ? a11 : a01;
         float* x0 = S.X + (4 * half) * LDX + col;
         unsigned long long mine = (blk ? masks.b : masks.a) >> (4 * half);     // bit ro <-> tile row ro + 4 half
-        if (PR_CHAINGRP_ABLATE & 2) mine = ~0ull;
         const unsigned int mlo = (unsigned int)mine, mhi = (unsigned int)(mine >> 32);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -388,7 +369,6 @@ __device__ __forceinline__ void flush_frame_sums(ColumnSums& cs, float* dscale, 
 // ---------------------------------------------------------------------------------------------
 // Feature-head backward, phases 1 and 2
 // ---------------------------------------------------------------------------------------------
-template <int SPLIT>
 __device__ __forceinline__ void head_bwd_loop(const HeadBwdJob& p) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     BSmem& S = *reinterpret_cast<BSmem*>(smem_raw);
@@ -452,10 +432,8 @@ __device__ __forceinline__ void head_bwd_loop(const HeadBwdJob& p) {
                     v[b] = *reinterpret_cast<const float4*>(src);
                 }
 #pragma unroll
-                for (int b = 0; b < BATCH; ++b) {
-                    if (PR_HEADB_ABLATE & 16) v[b] = make_float4(1e-3f, -1e-3f, 2e-3f, 0.f);
+                for (int b = 0; b < BATCH; ++b)
                     if (kind[b] != 1) v[b] = make_float4(0.f, 0.f, 0.f, 0.f);
-                }
 #pragma unroll
                 for (int b = 0; b < BATCH; ++b) {
                     const int idx = base + b * MLP_THREADS;
@@ -473,9 +451,6 @@ __device__ __forceinline__ void head_bwd_loop(const HeadBwdJob& p) {
                     *reinterpret_cast<float4*>(S.X + row * LDX + c) = v[b];
                 }
             }
-        } else if (PR_HEADB_ABLATE & 16) {
-            for (int idx = tid; idx < TILE_M * (p.kpad >> 2); idx += MLP_THREADS)
-                *reinterpret_cast<float4*>(S.X + (idx / (p.kpad >> 2)) * LDX + (idx % (p.kpad >> 2)) * 4) = make_float4(1e-3f, -1e-3f, 2e-3f, 0.f);
         } else {
             load_bn_backward(S, p.d_in, p.h_in, p.kpad, tile_base, rows_valid);
         }
@@ -499,28 +474,20 @@ __device__ __forceinline__ void head_bwd_loop(const HeadBwdJob& p) {
                 const int ro = PR_ACC_ROW(i & 15) + 32 * (i >> 4);
                 int rc = ro < last ? ro : last;
                 rc = rc > -4 * half ? rc : (live ? -4 * half : 0);
-                hv[i] = (PR_HEADB_ABLATE & 1) ? 0.25f : hb[rc * ld];
+                hv[i] = hb[rc * ld];
             }
         };
         float hvA[32], hvB[32];
-#ifndef PR_HEAD_NO_PREFETCH
         prefetch(0, hvA);
-#endif
         PR_HT(2);
         f32x16 a00, a01, a10, a11;
         zero4(a00, a01, a10, a11);
-        if (!(PR_HEADB_ABLATE & 8)) tile_products_any<SPLIT>(p.wt, p.nblk, S.X, a00, a01, a10, a11);
+        tile_products(p.wt, p.nblk, S.X, a00, a01, a10, a11);
         PR_HT(3);
         if (tid == 0) claimed = atomicAdd(p.tile_counter, 1);
-#ifndef PR_HEAD_NO_PREFETCH
         prefetch(1, hvB);
-#endif
         __syncthreads();      // every wave has finished reading X
         PR_HT(4);
-#ifdef PR_HEAD_NO_PREFETCH
-        prefetch(0, hvA);
-        prefetch(1, hvB);
-#endif
         // ---- AdaIN + ReLU backward, normalisation backward up to the batch terms -------------------------
         //   y = h g[frame] + b[frame] (g = scale rstd), a = relu(y);  dy = (y > 0) d a;  d scale += dy xh, d bias += dy;
         //   d xh = dy scale;  the batch terms mean(d xh), mean(d xh xh) are applied by the next phase
@@ -569,7 +536,7 @@ __device__ __forceinline__ void head_bwd_loop(const HeadBwdJob& p) {
                     ds = fmaf(dy, xh, ds);
                     db += dy;
                     xb[ro * LDX] = dxh;
-                    if (!(PR_HEADB_ABLATE & 2) && (full || ro < limit)) ab[ro * ld] = a;
+                    if (full || ro < limit) ab[ro * ld] = a;
                 }
                 // the two halves of the wave hold the same column: combine
                 s1 += __shfl_xor(s1, 32, 64);
@@ -631,11 +598,10 @@ __device__ __forceinline__ void head_bwd_loop(const HeadBwdJob& p) {
         if (tid == 0) S.next_tile = claimed;
         __syncthreads();
         PR_HT(6);
-        if (!(PR_HEADB_ABLATE & 4)) store_tile_rows(S.X, p.d_out, p.nblk * 32, p.ld, tile_base, rows_valid);
+        store_tile_rows(S.X, p.d_out, p.nblk * 32, p.ld, tile_base, rows_valid);
         __syncthreads();      // the next tile overwrites X and the records
         PR_HT(7);
     }
-    if (PR_HEADB_ABLATE & 32) return;
     flush_frame_sums(cs, p.dscale, p.dbias, p.nblk, p.width);
     if (lane < 32 && !p.frozen) {
 #pragma unroll
@@ -651,19 +617,10 @@ __device__ __forceinline__ void head_bwd_loop(const HeadBwdJob& p) {
 
 __global__ __launch_bounds__(MLP_THREADS, MLP_BLOCKS_PER_CU) void k_head_bwd_group(HeadBwdJob j0, HeadBwdJob j1, HeadBwdJob j2, HeadBwdJob j3,
                                                                                    int count) {
-    pr_stagger(2);
-    head_bwd_loop<0>(j0);
-    if (count > 1) head_bwd_loop<0>(j1);
-    if (count > 2) head_bwd_loop<0>(j2);
-    if (count > 3) head_bwd_loop<0>(j3);
-}
-
-__global__ __launch_bounds__(MLP_THREADS, MLP_BLOCKS_PER_CU) void k_head_bwd_group_bf16(HeadBwdJob j0, HeadBwdJob j1, HeadBwdJob j2, HeadBwdJob j3,
-                                                                                        int count) {
-    head_bwd_loop<1>(j0);
-    if (count > 1) head_bwd_loop<1>(j1);
-    if (count > 2) head_bwd_loop<1>(j2);
-    if (count > 3) head_bwd_loop<1>(j3);
+    head_bwd_loop(j0);
+    if (count > 1) head_bwd_loop(j1);
+    if (count > 2) head_bwd_loop(j2);
+    if (count > 3) head_bwd_loop(j3);
 }
 
 int launch_head_bwd_group(const HeadBwdJob* jobs, const long* max_rows, int count, hipStream_t s) {
@@ -678,22 +635,11 @@ int launch_head_bwd_group(const HeadBwdJob* jobs, const long* max_rows, int coun
         }
         if (max_tiles <= 0) continue;
         int cus = 0;
-        const bool split = g[0].split != 0;
-        for (int j = 1; j < n; ++j) PR_REQUIRE((g[j].split != 0) == split, "head backward: jobs of one launch differ in precision");
-        PR_TRY(prepare_kernel(split ? reinterpret_cast<const void*>(k_head_bwd_group_bf16) : reinterpret_cast<const void*>(k_head_bwd_group),
-                              (int)sizeof(BSmem), &cus));
-        #ifdef PR_HEAD_RESIDENT
-        const long resident = (long)cus * PR_HEAD_RESIDENT;        // measurement build: workgroups per CU of the head backward launch
-#else
+        PR_TRY(prepare_kernel(reinterpret_cast<const void*>(k_head_bwd_group), (int)sizeof(BSmem), &cus));
         const long resident = (long)cus * MLP_BLOCKS_PER_CU;
-#endif
         ProfileScope scope(2, s);
-        if (split)
-            hipLaunchKernelGGL(k_head_bwd_group_bf16, dim3((unsigned)(max_tiles < resident ? max_tiles : resident)), dim3(MLP_THREADS),
-                               sizeof(BSmem), s, g[0], g[1], g[2], g[3], n);
-        else
-            hipLaunchKernelGGL(k_head_bwd_group, dim3((unsigned)(max_tiles < resident ? max_tiles : resident)), dim3(MLP_THREADS), sizeof(BSmem), s,
-                               g[0], g[1], g[2], g[3], n);
+        hipLaunchKernelGGL(k_head_bwd_group, dim3((unsigned)(max_tiles < resident ? max_tiles : resident)), dim3(MLP_THREADS), sizeof(BSmem), s,
+                           g[0], g[1], g[2], g[3], n);
         PR_LAUNCH_CHECK();
     }
     return PR_OK;
@@ -847,8 +793,7 @@ __device__ __forceinline__ void chain_bwd_loop(const ChainBwdJob& c) {
             PR_CT(3);
             __syncthreads();
             PR_CT(4);
-            if (!(PR_CHAINGRP_ABLATE & 1))
-                pending = Drain{c.gstack + (size_t)(l - 1) * c.g_stride + (size_t)tile_base * c.Wpad, c.Wpad, c.Wpad >> 2, rows_valid};
+            pending = Drain{c.gstack + (size_t)(l - 1) * c.g_stride + (size_t)tile_base * c.Wpad, c.Wpad, c.Wpad >> 2, rows_valid};
         }
         PR_CT(5);
         if (tid == 0) S.next_tile = claimed;
@@ -871,16 +816,7 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_BLOCKS_PER_CU) void k_chain_bwd_gr
     if (count > 3) chain_bwd_loop<0>(j3);
 }
 
-// split precision (PR_FLAG_SPLIT_BACKWARD): the chains' products on bf16 triples
-__global__ __launch_bounds__(MLP_THREADS, MLP_BLOCKS_PER_CU) void k_chain_bwd_group_bf16(ChainBwdJob j0, ChainBwdJob j1, ChainBwdJob j2, ChainBwdJob j3,
-                                                                                         int count) {
-    chain_bwd_loop<1>(j0);
-    if (count > 1) chain_bwd_loop<1>(j1);
-    if (count > 2) chain_bwd_loop<1>(j2);
-    if (count > 3) chain_bwd_loop<1>(j3);
-}
-
-// ... or (the default of PR_FLAG_SPLIT_BACKWARD) on fp16 pairs of the tile x a per-tile power of two (job.split == 2)
+// split precision (PR_FLAG_SPLIT_BACKWARD): the chains' products on fp16 pairs of the tile x a per-tile power of two (job.split == 2)
 __global__ __launch_bounds__(MLP_THREADS, MLP_BLOCKS_PER_CU) void k_chain_bwd_group_f16(ChainBwdJob j0, ChainBwdJob j1, ChainBwdJob j2, ChainBwdJob j3,
                                                                                         int count) {
     chain_bwd_loop<2>(j0);
@@ -927,7 +863,7 @@ int launch_chain_bwd_group(const ChainBwdJob* jobs, const long* max_rows, int co
         int cus = 0;
         const int split = g[0].split;
         for (int j = 1; j < n; ++j) PR_REQUIRE(g[j].split == split, "backward chain: jobs of one launch differ in precision");
-        auto* const kernel = split == 2 ? k_chain_bwd_group_f16 : (split == 1 ? k_chain_bwd_group_bf16 : k_chain_bwd_group);
+        auto* const kernel = split == 2 ? k_chain_bwd_group_f16 : k_chain_bwd_group;
         PR_TRY(prepare_kernel(reinterpret_cast<const void*>(kernel), (int)sizeof(BSmem), &cus));
         const long resident = (long)cus * MLP_BLOCKS_PER_CU;
         ProfileScope scope(2, s);

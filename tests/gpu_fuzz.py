@@ -137,8 +137,8 @@ def divergence_kink_margin(cfg, scene, n, bias, perturb, absent, noise_seed=123)
 
 def backward_sweep(cases, rng, only=None):
     from tests.test_gpu import GRAD_KEYS, KINK_MARGIN, ForwardFieldMismatch, drain_settlements, _gradients as _gradients_fp32
-    # PR_FUZZ_PRECISION=f16x3: the same sweep with the split-precision training kernels (fp16-pair forward phase and backward chains,
-    # bf16-triple weight gradients) against the same oracle, tolerances and classifications
+    # PR_FUZZ_PRECISION=f16x3: the same sweep with the split-precision training kernels (fp16-pair forward phase, backward chains and
+    # weight gradients) against the same oracle, tolerances and classifications
     precision = os.environ.get("PR_FUZZ_PRECISION", "fp32")
 
     def _gradients(*a, **kw):

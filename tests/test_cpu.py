@@ -180,7 +180,7 @@ def test_library_exports_every_declared_symbol(built_library):
     assert built_library.pr_abi_version() == 5
 
 
-def test_product_kernels_have_no_flat_memory_operations(built_library):
+def test_library_kernels_have_no_flat_memory_operations(built_library):
     """A device pointer that reaches a kernel through a table loses its address space; hipcc then emits flat loads / stores and, since a
     flat access may be an LDS access, waits for EVERY outstanding request in front of the first use of any loaded value - inside a
     software-pipelined K loop that is a full L2 round trip per step (the training forward, both head phases and the
@@ -195,7 +195,7 @@ def test_product_kernels_have_no_flat_memory_operations(built_library):
     kernels = [k for k in counts if "k_" in k]
     assert len(kernels) >= 60, len(kernels)                       # the disassembly found the library's kernels
     for wanted in ("k_mlp_mfma_group", "k_mlp_mfma_train_group_split", "k_mlp_head_group", "k_chain_bwd_group_f16", "k_head_bwd_group",
-                   "k_gemm_tn_all_bf16", "k_gemm_tn_all_f16", "k_mlp_split_group", "k_composite"):
+                   "k_gemm_tn_all_f16", "k_mlp_split_group", "k_composite"):
         assert any(wanted in k for k in kernels), wanted
     flat = {k: v for k, v in counts.items() if v["flat_load"] or v["flat_store"]}
     assert not flat, flat
@@ -222,6 +222,22 @@ def test_k_loops_never_wait_for_every_outstanding_request(built_library):
             assert loops[k], k
             for loop in loops[k]:
                 assert not any("vmcnt(0)" in w for w in loop["waits"]), (k, loop)
+
+
+def test_hip_sources_have_only_instrumentation_and_test_path_switches():
+    """A preprocessor conditional in csrc/ either instruments a kernel (timers, traces: same results) or forces one of the product's
+    own run-time paths at small sizes; A/B variants and work-skipping builds live in git history, not in the sources."""
+    allowed = {"PR_MLP_TIMING", "PR_CHAIN_TIMING", "PR_HEAD_TIMING", "PR_MLP_TRACE", "PR_BWD_LAYERWISE", "__HIPCC__"}
+    found = {}
+    for path in sorted(glob.glob(os.path.join(ROOT, "playableenvironments_amd", "csrc", "*"))):
+        for line in open(path):
+            m = re.match(r"\s*#\s*(?:if|ifdef|ifndef|elif)\b(.*)", line)
+            if not m:
+                continue
+            expr = re.sub(r"//.*|/\*.*?\*/", "", m.group(1))
+            for name in set(re.findall(r"[A-Za-z_]\w*", expr)) - {"defined"}:
+                found.setdefault(name, os.path.basename(path))
+    assert set(found) <= allowed, {k: v for k, v in found.items() if k not in allowed}
 
 
 def test_plain_c_client_links_and_calls_the_abi(built_library, tmp_path):
@@ -281,16 +297,17 @@ def _model_struct_host(cfg_model, positions):
     return comp, comp._model_struct(comp.object_models_coarse[0], positions)
 
 
-def test_packed_and_workspace_sizes_on_host(built_library):
+def test_fp16_pair_packing_and_workspace_sizes_on_host(built_library):
     cfg = configs.tennis_config()
     comp, s = _model_struct_host(cfg["model"]["object_models"][2], 32)
     size = C.c_size_t()
     assert built_library.pr_packed_size(C.byref(s), C.byref(size)) == 0
     # fragment-ordered copy = the padded weights for the forward kernels, plus every matrix once more as W^T fragments for
-    # the backward chains (biases and the small heads are not repeated), plus - split-precision training, round 4 - the W^T
-    # fragments and the forward segments of phase 1 once more as bf16 triples (1.5 x the fp32 fragments each)
+    # the backward passes (biases and the small heads are not repeated), plus - split-precision training - the backward chains'
+    # W^T fragments and the forward segments of phase 1 once more as fp16 (hi, lo) pairs (the size of the fp32 fragments each;
+    # head layers 3 and 6 have none: the head phases' products stay fp32)
     raw = sum(p.numel() for n, p in comp.named_parameters() if "affine_transform" not in n) * 4
-    assert 4.2 * raw <= size.value <= 5.4 * raw, size.value / raw
+    assert 3.6 * raw <= size.value <= 4.2 * raw, size.value / raw
     call = _lib.Call()
     call.frames, call.rays, call.objects = 1, 1000, 1
     for f in ("ray_origins", "ray_directions", "w2o", "style", "deformation", "object_in_scene"):

@@ -560,7 +560,7 @@ def _gradients(cfg, scene, n, bias, perturb, canonical=False, frozen=(), keys=GR
     """(oracle autograd, HIP backward) gradients of a random linear functional of the output fields ``keys``; ``rays``: also
     with respect to the camera rays (ray_origins, ray_directions).  ``exact``: a third entry per tensor - the oracle's
     autograd in float64 on the same weights, inputs and replayed noise (the arbiter of ill-conditioned cases)."""
-    # precision "f16x3": the split-precision BACKWARD (bf16 triples, PR_FLAG_SPLIT_BACKWARD) behind the exact fp32 forward
+    # precision "f16x3": the split-precision training products (fp16 pairs, PR_FLAG_SPLIT_BACKWARD) on the fp32-packed weights
     comp = build(cfg, alpha_bias=bias, precision=precision).train(training)
     inputs = composer_inputs(cfg, scene, pixels=grid_pixels(scene["image_size"][0], scene["image_size"][1], n))
     o, d, nrm, w2o, sty, dfm, ins = inputs

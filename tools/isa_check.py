@@ -4,7 +4,7 @@ stores (a flat access in a software-pipelined loop makes hipcc w
     python tools/isa_check.py [path/to/libplayrender.so]          # table of the kernels that still have flat accesses
 
 Reads the gfx950 code objects out of the library's .hip_fatbin section (uncompressed clang offload bundles) and disassembles them with
-/opt/rocm/lib/llvm/bin/llvm-objdump.  Used by tests/test_cpu.py::test_product_kernels_have_no_flat_memory_operations."""
+/opt/rocm/lib/llvm/bin/llvm-objdump.  Used by tests/test_cpu.py::test_library_kernels_have_no_flat_memory_operations."""
 import os
 import re
 import struct

@@ -1,5 +1,6 @@
 """Debugging (GPU box): worst gradient errors of a split-precision training call against the oracle's autograd over a few scenes, for
-A/B runs of the weight scale of the fp16-pair forward (-DPR_TRAIN_SPLIT_SCALE=k):
+A/B runs of the weight scale of the fp16 pairs (TRAIN_SPLIT_WEIGHT_SCALE_LOG2 in csrc/mlp_tile.h: build a variant with another value
+into build/variants/ and point PR_PERF_LIB at it):
     [PR_PERF_LIB=build/variants/libplayrender_scale5.so] python tools/perf/dbg_split_scale.py"""
 import os
 import sys
