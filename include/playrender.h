@@ -484,10 +484,47 @@ int pr_roi_pool_backward(int32_t images, int32_t channels, int32_t height, int32
                          const int32_t* argmax, float* grad_input, void* stream);
 
 /*
+ * Point queries of ONE object model's fields: density, style-modulated feature and ray-bender displacement at explicit
+ * OBJECT-frame positions of its box - RayBendingStyleNerfModel.forward in evaluation mode (running BatchNorm statistics;
+ * model/nerf_models/ray_bending_style_nerf_model.py:137-219): closed-interval box test on the given position, boolean compaction
+ * in flat order, ray bender (+ clamp, + canonical pose), second box test on the bent position, backbone, density head, style
+ * feature head; (0 | empty_space_alpha | 0) for every point that is not evaluated.  The skybox model (kind == 1) reads the ray
+ * origin of the group and the direction of the point, returns density 10 and still obeys the box test on `positions`.
+ * The evaluation is the renderer's fused MLP kernel on compact records built from the positions (the query runs as frames = G,
+ * rays = M, one position per ray); unlike a render the feature head runs on EVERY in-box point (no sigma gate: the model returns
+ * features where the density is not positive too).  With features == NULL the feature head is not run at all (8 of the 11 matrix
+ * products of a point remain; a skybox density-only query evaluates nothing).  model->positions is ignored.  World-frame
+ * positions are the caller's to transform (w2o).  No gradients.
+ */
+typedef struct pr_query_t {
+    int32_t groups;              /* G: one style / deformation row (and, skybox, one ray origin) per group */
+    int32_t points;              /* M points per group; G * M < 2^31 */
+    uint32_t flags;              /* PR_FLAG_CANONICAL_POSE or 0; anything else: PR_ERR_INVALID */
+    int32_t precision;           /* PR_PRECISION_*: what `packed` was packed with */
+    const float* positions;      /* (G,M,3) OBJECT-frame positions */
+    const float* ray_origins;    /* (G,3)   kind == 1 (skybox) only, object frame; else NULL */
+    const float* ray_directions; /* (G,M,3) kind == 1 only, need not be normalised; else NULL */
+    const float* style;          /* (G,S) */
+    const float* deformation;    /* (G,D) */
+    float* features;             /* out (G,M,F), or NULL = density-only query: the feature head is NOT run */
+    float* sigma;                /* out (G,M) raw density; empty_space_alpha outside the box */
+    float* displacement;         /* out (G,M,3) or NULL; zeros outside the box / without a bender */
+    int32_t* slot;               /* out (G,M) or NULL: compact row of the point, -1 = outside the box (as sample_slot) */
+    int32_t* counters;           /* out [2] or NULL: rows sent through the backbone, rows sent through the feature head */
+} pr_query_t;
+/* Workspace bytes of the query (host computation, no device work). */
+int pr_query_workspace_size(const pr_query_t* q, const pr_object_model_t* model, size_t* bytes);
+/* `packed`: pr_pack_model(model, q->precision, ...).  `workspace`: 256-byte aligned, pr_query_workspace_size bytes.  Kernel launches on
+ * `stream` only (every fill is a kernel): capturable into a HIP graph. */
+int pr_query_field(const pr_query_t* q, const pr_object_model_t* model, const void* packed,
+                   void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Kernel timing for bench.py: while enabled, the launches of the dominant kernels are bracketed by
  * hipEventRecord on the launch stream.  Categories: 0 = fused MLP (k_mlp_mfma / k_mlp_split / k_mlp_head),
  * 1 = forward compositing (k_composite), 2 = backward dX products (k_gemm_nn), 3 = backward dW products
- * (k_gemm_tn + its reduction), 4 = backward compositing (k_composite_bwd); the rest are reserved.
+ * (k_gemm_tn + its reduction), 4 = backward compositing (k_composite_bwd), 5 = the front and back end of pr_query_field
+ * (k_query_count + block scan + k_query_fill, k_query_scatter; its MLP launch counts as 0); the rest are reserved.
  * pr_profile_collect synchronises the recorded events, returns the summed milliseconds and launch
  * counts per category (host arrays of PR_PROFILE_CATEGORIES) and clears the list.
  */

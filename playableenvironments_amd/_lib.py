@@ -146,6 +146,14 @@ class InputGrads(C.Structure):
                 ("model_fine", ModelGrads * PR_MAX_OBJECTS), ("ray_origins", C.c_void_p), ("ray_directions", C.c_void_p)]
 
 
+class Query(C.Structure):
+    """pr_query_t (include/playrender.h): a point query of one object model's fields."""
+    _fields_ = [("groups", C.c_int32), ("points", C.c_int32), ("flags", C.c_uint32), ("precision", C.c_int32),
+                ("positions", C.c_void_p), ("ray_origins", C.c_void_p), ("ray_directions", C.c_void_p), ("style", C.c_void_p),
+                ("deformation", C.c_void_p), ("features", C.c_void_p), ("sigma", C.c_void_p), ("displacement", C.c_void_p),
+                ("slot", C.c_void_p), ("counters", C.c_void_p)]
+
+
 # every exported symbol of include/playrender.h : (restype, argtypes)
 class SceneSetup(C.Structure):
     """pr_scene_setup_t (include/playrender.h)."""
@@ -180,6 +188,8 @@ SYMBOLS = {
                                       C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pr_roi_pool_backward": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                                        C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pr_query_workspace_size": (C.c_int, [C.POINTER(Query), C.POINTER(ObjectModel), C.POINTER(C.c_size_t)]),
+    "pr_query_field": (C.c_int, [C.POINTER(Query), C.POINTER(ObjectModel), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_profile_enable": (C.c_int, [C.c_int]),
     "pr_profile_collect": (C.c_int, [C.POINTER(C.c_double), c_int32_p]),
     "pr_probe_mfma_f32": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_void_p]),
@@ -220,7 +230,12 @@ def load() -> C.CDLL:
             "or make -C playableenvironments_amd/csrc).  There is no CPU fallback.")
     lib = C.CDLL(path)
     for name, (res, args) in SYMBOLS.items():
-        fn = getattr(lib, name)
+        try:
+            fn = getattr(lib, name)
+        except AttributeError:
+            # a library built from older sources: the same advice as for an ABI mismatch, not a bare AttributeError
+            raise RuntimeError(f"{path} does not export {name}: it was built from older sources "
+                               "(rebuild: make -C playableenvironments_amd/csrc)") from None
         fn.restype = res
         fn.argtypes = args
     if lib.pr_abi_version() != 5:

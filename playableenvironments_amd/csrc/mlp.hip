@@ -666,7 +666,9 @@ __device__ unsigned long long g_mlp_trace[1024][12];
 // objects in order, EVERY tile is claimed from the object's counter, and a workgroup that finds an object's tiles
 // exhausted moves on to the next object at once: small objects do not pay a launch of their own (a launch lasts at
 // least one tile time and ends with idle CUs) and the tail of one object overlaps the start of the next.
-template <bool TRAIN, bool GROUP, bool SPLIT = false>
+// SIGMA_ONLY = true (density-only point queries, k_mlp_sigma): a tile ends behind the density head - no head layers, no feature
+// rows; the 8 backbone products of the 11 of a sample remain.
+template <bool TRAIN, bool GROUP, bool SPLIT = false, bool SIGMA_ONLY = false>
 __device__ __forceinline__ void mlp_tile_loop(const MlpParams& p) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     Smem& S = *reinterpret_cast<Smem*>(smem_raw);
@@ -835,7 +837,9 @@ __device__ __forceinline__ void mlp_tile_loop(const MlpParams& p) {
         if (tid == 0) S.next_tile = GROUP ? claimed : (dynamic_tiles ? (int)gridDim.x + claimed : tile + (int)gridDim.x);   // read at the end of the tile
         PR_PHASE(7);
         // ---- style-modulated feature head -------------------------------------------------------
-        if (!TRAIN && p.gate) {
+        if (SIGMA_ONLY) {
+            __syncthreads();   // S.next_tile is published; the next tile's prologue overwrites flags / X
+        } else if (!TRAIN && p.gate) {
             __syncthreads();   // the liveness bits are complete
             pending = gated_head(S, p, tile_base, pending, enc);
             PR_PHASE(8);
@@ -860,13 +864,15 @@ __device__ __forceinline__ void mlp_tile_loop(const MlpParams& p) {
             PR_PHASE(14);
         }
     }
-    if (!TRAIN && p.gate) gated_head_flush(S, p, pending, enc);
+    if (!TRAIN && !SIGMA_ONLY && p.gate) gated_head_flush(S, p, pending, enc);
     if (TRAIN) flush_column_stats(cstats, p, p.layers[p.n_backbone].nblk);
     PR_PHASE_FLUSH();
 }
 
 __global__ __launch_bounds__(MLP_THREADS, MLP_BLOCKS_PER_CU) void k_mlp_mfma(MlpParams p) { mlp_tile_loop<false, false>(p); }
 __global__ __launch_bounds__(MLP_THREADS, MLP_BLOCKS_PER_CU) void k_mlp_mfma_train(MlpParams p) { mlp_tile_loop<true, false>(p); }
+// density-only point queries (pr_query_field without a feature output): the same tile loop up to the density head
+__global__ __launch_bounds__(MLP_THREADS, MLP_BLOCKS_PER_CU) void k_mlp_sigma(MlpParams p) { mlp_tile_loop<false, false, false, true>(p); }
 // Several objects, one launch.  One copy of the tile loop per job slot: the parameters of a slot are kernel arguments at
 // constant offsets, exactly as in k_mlp_mfma (a table indexed at run time would turn every parameter into a memory load
 // and every pointer into a flat pointer - measured: 3 % slower).
@@ -1251,6 +1257,21 @@ int launch_mlp(const MlpParams& p, int max_rows, bool naive, const pr_object_mod
         fprintf(stderr, "\n");
     }
 #endif
+    return PR_OK;
+}
+
+int launch_mlp_sigma(const MlpParams& p, int max_rows, hipStream_t s) {
+    if (max_rows <= 0) return PR_OK;
+    PR_REQUIRE(p.phase == 0 && !p.gate, "density-only MLP launch: fused evaluation parameters without the gated head only");
+    const int max_tiles = (max_rows + TILE_M - 1) / TILE_M;
+    int cu_count = 0;
+    PR_TRY(prepare_kernel(reinterpret_cast<const void*>(k_mlp_sigma), (int)sizeof(Smem), &cu_count));
+    int resident = cu_count * MLP_BLOCKS_PER_CU;
+    if (resident > MAX_RESIDENT_TILES) resident = MAX_RESIDENT_TILES;
+    const int grid = max_tiles < resident ? max_tiles : resident;
+    ProfileScope scope(0, s);
+    hipLaunchKernelGGL(k_mlp_sigma, dim3(grid), dim3(MLP_THREADS), sizeof(Smem), s, p);
+    PR_LAUNCH_CHECK();
     return PR_OK;
 }
 

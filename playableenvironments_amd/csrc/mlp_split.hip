@@ -494,7 +494,8 @@ __device__ __forceinline__ void gated_head_flush_h(SmemH& S, const MlpParams& p,
 
 // GROUP: one of several objects evaluated by the same launch (k_mlp_split_group), as in mlp.hip: every tile is claimed from
 // the object's counter and a workgroup that finds an object's tiles exhausted moves on to the next object.
-template <bool GROUP, int TERMS>
+// SIGMA_ONLY (density-only point queries, k_mlp_split_sigma): a tile ends behind the density head.
+template <bool GROUP, int TERMS, bool SIGMA_ONLY = false>
 __device__ __forceinline__ void split_tile_loop(const MlpParams& p) {
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
     SmemH& S = *reinterpret_cast<SmemH*>(smem_raw);
@@ -596,6 +597,10 @@ __device__ __forceinline__ void split_tile_loop(const MlpParams& p) {
         }
 
         if (tid == 0) S.next_tile = GROUP ? claimed : (dynamic_tiles ? (int)gridDim.x + claimed : tile + (int)gridDim.x);   // read at the end of the tile
+        if (SIGMA_ONLY) {
+            __syncthreads();   // S.next_tile is published; the next tile's prologue overwrites flags / the planes
+            continue;
+        }
         if (p.gate) {
             __syncthreads();   // the liveness bits are complete
             pending = gated_head_h<TERMS>(S, p, tile_base, pending);
@@ -630,7 +635,7 @@ __device__ __forceinline__ void split_tile_loop(const MlpParams& p) {
         }
         __syncthreads();
     }
-    if (p.gate) gated_head_flush_h<TERMS>(S, p, pending);
+    if (!SIGMA_ONLY && p.gate) gated_head_flush_h<TERMS>(S, p, pending);
 }
 
 __device__ __forceinline__ void claim_matrix_priority() {
@@ -665,6 +670,29 @@ __global__ __launch_bounds__(STHREADS, SBLOCKS_PER_CU) void k_mlp_f16_group(MlpP
     if (count > 1) split_tile_loop<true, 1>(j1);
     if (count > 2) split_tile_loop<true, 1>(j2);
     if (count > 3) split_tile_loop<true, 1>(j3);
+}
+
+// density-only point queries: the single-object kernels without the feature head
+template <int TERMS>
+__global__ __launch_bounds__(STHREADS, SBLOCKS_PER_CU) void k_mlp_split_sigma(MlpParams p) {
+    claim_matrix_priority();
+    split_tile_loop<false, TERMS, true>(p);
+}
+
+int launch_mlp_split_sigma(const MlpParams& p, int max_rows, int terms, hipStream_t s) {
+    if (max_rows <= 0) return PR_OK;
+    PR_REQUIRE(p.phase == 0 && !p.gate, "density-only MLP launch: fused evaluation parameters without the gated head only");
+    auto* const kernel = terms == 1 ? k_mlp_split_sigma<1> : k_mlp_split_sigma<3>;
+    const int max_tiles = (max_rows + STILE_M - 1) / STILE_M;
+    int cu_count = 0;
+    PR_TRY(prepare_kernel(reinterpret_cast<const void*>(kernel), (int)sizeof(SmemH), &cu_count));
+    int resident = cu_count * SBLOCKS_PER_CU;
+    if (resident > MAX_RESIDENT_TILES) resident = MAX_RESIDENT_TILES;
+    const int grid = max_tiles < resident ? max_tiles : resident;
+    ProfileScope scope(0, s);
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(STHREADS), sizeof(SmemH), s, p);
+    PR_LAUNCH_CHECK();
+    return PR_OK;
 }
 
 int launch_mlp_split_group(const MlpParams* host_jobs, const int* max_rows, int count, int terms, hipStream_t s) {

@@ -375,6 +375,10 @@ int launch_mlp_group(const MlpParams* host_jobs, const int* max_rows, int count,
 // PR_PRECISION_F16X3 (terms = 3) / PR_PRECISION_F16 (terms = 1), eval only
 int launch_mlp_split(const MlpParams& p, int max_rows, int terms, hipStream_t s);
 int launch_mlp_split_group(const MlpParams* host_jobs, const int* max_rows, int count, int terms, hipStream_t s);
+// density-only variants (point queries without a feature output): a tile ends behind the density head - k_mlp_sigma /
+// k_mlp_split_sigma<terms>; fused evaluation parameters (phase 0), gate == 0, p.feat is not written
+int launch_mlp_sigma(const MlpParams& p, int max_rows, hipStream_t s);
+int launch_mlp_split_sigma(const MlpParams& p, int max_rows, int terms, hipStream_t s);
 
 // BatchNorm1d(affine=False) in training mode: batch mean / biased variance from the accumulated sums,
 // running statistics updated in place with momentum 0.1 and the unbiased variance, num_batches_tracked += 1

@@ -4,9 +4,12 @@ These modules own the ``nn.Parameter`` / buffer storages under exactly the names
 uses (``object_models_coarse.2.nerf_model.backbone_layers.4.weight``,
 ``...features_head.1.ada_in.normalization.running_mean``, ``ray_bender.positional_encoder.current_step``
 ...), so reference checkpoints load with ``load_state_dict`` and the trainers'
-``model.parameters()`` see the same tensors.  They deliberately have NO ``forward``: all arithmetic
-of these networks runs in the fused HIP kernel (csrc/mlp.hip), which reads the parameter storages
-in place.  Initialisation follows the reference constructors (cited per class).
+``model.parameters()`` see the same tensors.  All arithmetic of these networks runs in the fused HIP
+kernel (csrc/mlp.hip), which reads the parameter storages in place: the renderer drives it from rays,
+and ``RayBendingStyleNerfModel.forward`` - the one ``forward`` here, with the reference's signature -
+drives it from explicit positions (a point query, field_query.py).  The inner ``nerf_model`` /
+``ray_bender`` modules have no ``forward`` of their own.  Initialisation follows the reference
+constructors (cited per class).
 """
 from __future__ import annotations
 
@@ -357,6 +360,18 @@ class RayBendingStyleNerfModel(Tracked, nn.Module):
 
     def set_step(self, current_step: int):
         self.ray_bender.set_step(current_step)
+
+    def forward(self, ray_positions: torch.Tensor, ray_origins: torch.Tensor, ray_directions: torch.Tensor, style: torch.Tensor,
+                deformation: torch.Tensor, video_indexes: torch.Tensor = None, canonical_pose: bool = False):
+        """The reference's call (model/nerf_models/ray_bending_style_nerf_model.py:137-219) as a point query on the HIP path
+        (``pr_query_field``): ``ray_positions (..., P, 3)`` in the OBJECT frame, ``ray_origins`` / ``ray_directions (..., 3)`` (read by
+        skybox models only; one origin per group of points that share a code), ``style (..., S)`` / ``deformation (..., D)`` with
+        leading dimensions of size 1 where they broadcast -> ``(features (..., P, F), alphas (..., P), displacements (..., P, 3), {})``.
+        ``video_indexes`` is accepted and ignored, as by every model the reference ships.  Evaluation mode, ``torch.no_grad()``,
+        device tensors; exact fp32 arithmetic.  The weights are packed on every call: inside a loop prefer
+        ``ObjectComposer.query_object``, which caches the packing (and follows the composer's ``precision``)."""
+        from . import field_query
+        return field_query.module_forward(self, ray_positions, ray_origins, ray_directions, style, deformation, canonical_pose)
 
 
 OBJECT_MODEL_CLASSES = {"model.nerf_models.ray_bending_style_nerf_model": RayBendingStyleNerfModel}

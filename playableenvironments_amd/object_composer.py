@@ -18,7 +18,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, field_query
 from .modules import OBJECT_MODEL_CLASSES, REGISTRATION_EPOCH as _REGISTRATION_EPOCH, ModuleList, RayBendingStyleNerfModel, Tracked, \
     tree_is_tracked
 
@@ -190,13 +190,7 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
     return None if t is None else t.data_ptr()
 
 
-def _linear(layer: Optional[nn.Linear]) -> _lib.Linear:
-    s = _lib.Linear()
-    if layer is not None:
-        s.weight = layer.weight.data_ptr()
-        s.bias = layer.bias.data_ptr() if layer.bias is not None else None
-        s.out_features, s.in_features = layer.weight.shape
-    return s
+_linear = field_query.linear_struct
 
 
 GRAD_KEYS = ("integrated_features", "opacity", "depth", "integrated_displacements_magnitude", "weights", "integrated_divergence")
@@ -663,52 +657,9 @@ class ObjectComposer(Tracked, nn.Module):
         return s
 
     def _build_model_struct(self, model: RayBendingStyleNerfModel, positions: int) -> _lib.ObjectModel:
-        cfg = model.model_config
-        nerf, bender = model.nerf_model, model.ray_bender
-        s = _lib.ObjectModel()
-        s.kind = nerf.kind
-        s.has_bender = 1 if bender.has_weights else 0
-        s.positions = positions
-        s.style_features = cfg["style_features"]
-        s.deformation_features = cfg["deformation_features"]
-        s.output_features = nerf.output_features
-        s.layers_width = nerf.layers_width
-        s.backbone_count = nerf.backbone_layers_count
-        s.skip_layer_idx = nerf.skip_layer_idx
-        s.octaves = nerf.octaves
-        box = [float(v) for row in cfg["bounding_box"] for v in row]
-        for i in range(6):
-            s.bbox[i] = box[i]
-        s.empty_space_alpha = float(cfg["empty_space_alpha"])
-        s.z_near_min = float(cfg["z_near_min"])
-        s.z_far_max = float(cfg["z_far_max"])
-        head = nerf.features_head
-        s.bn_eps = float(head[1].ada_in.normalization.eps)
-        for i, layer in enumerate(nerf.backbone_layers):
-            s.backbone[i] = _linear(layer)
-        s.alpha_head = _linear(nerf.alpha_head if nerf.kind == 0 else None)
-        s.head0 = _linear(head[0])
-        s.affine1 = _linear(head[1].affine_transform)
-        s.bn1_mean = head[1].ada_in.normalization.running_mean.data_ptr()
-        s.bn1_var = head[1].ada_in.normalization.running_var.data_ptr()
-        s.bn1_batches = head[1].ada_in.normalization.num_batches_tracked.data_ptr()
-        s.head3 = _linear(head[3])
-        s.affine4 = _linear(head[4].affine_transform)
-        s.bn4_mean = head[4].ada_in.normalization.running_mean.data_ptr()
-        s.bn4_var = head[4].ada_in.normalization.running_var.data_ptr()
-        s.bn4_batches = head[4].ada_in.normalization.num_batches_tracked.data_ptr()
-        s.head6 = _linear(head[6])
-        if bender.has_weights:
-            s.bender_width = bender.layers_width
-            s.bender_count = bender.layers_count
-            s.bender_skip = bender.skip_layer_idx
-            s.bender_octaves = bender.positional_encoder.octaves_count
-            for i, v in enumerate(self._annealing_weights(bender.positional_encoder)):
-                s.bender_octave_weights[i] = v
-            for i, layer in enumerate(bender.backbone_layers):
-                s.bender[i] = _linear(layer)
-            s.bender_out = _linear(bender.output_head)
-        return s
+        bender = model.ray_bender
+        weights = self._annealing_weights(bender.positional_encoder) if bender.has_weights else None
+        return field_query.build_model_struct(model, positions, weights)
 
     def _annealing_weights(self, encoder) -> list:
         """Host copy of the bender's octave weights, refreshed only when ``current_step`` changed (reading the
@@ -805,6 +756,102 @@ class ObjectComposer(Tracked, nn.Module):
             # evaluated by torch so that it is bit-identical to the reference's torch.linspace
             self._linspace[key] = torch.linspace(0.0, 1.0, count, device=device)
         return self._linspace[key]
+
+    # ------------------------------------------------------------------ point queries
+    def query_object(self, object_idx: int, positions: torch.Tensor, style: torch.Tensor, deformation: torch.Tensor, *,
+                     fine: bool = False, ray_origins: Optional[torch.Tensor] = None, ray_directions: Optional[torch.Tensor] = None,
+                     canonical_pose: bool = False, features: bool = True, return_slot: bool = False) -> Dict[str, torch.Tensor]:
+        """The fields of the model of object instance ``object_idx`` at explicit OBJECT-frame positions (``pr_query_field``): what the
+        reference's ``object_models_coarse[i](...)`` returns, in evaluation mode, on the renderer's MLP kernel at the composer's
+        ``precision``.  World-frame points are the caller's to transform (``transformation_matrix_w2o``).
+
+        ``positions (G, M, 3)`` with ``style (G, S)``, ``deformation (G, D)`` - one code per group of M points - or ``positions (M, 3)``
+        with ``style (S,)`` / ``(1, S)`` (one group; the results then have no group axis).  Skybox models additionally take
+        ``ray_origins (G, 3)`` (one origin per group) and ``ray_directions (G, M, 3)`` (need not be normalised), both in the object frame.
+        ``fine``: query the fine model.  ``features=False``: a density-only query - the feature head is not run (about 0.8 of the
+        cost; a skybox model then evaluates nothing).
+
+        Returns ``features (G, M, F)`` (absent with ``features=False``; zero rows outside the box), ``sigma (G, M)`` raw density
+        (``empty_space_alpha`` outside the box), ``displacements (G, M, 3)`` of the ray bender (zeros outside the box / without a
+        bender), ``evaluated`` - an int32 device tensor [points sent through the backbone, points sent through the feature head], not
+        read back - and, with ``return_slot``, ``slot (G, M)`` int32: the compact row of each point in flat order, -1 outside the box
+        (a query that had to be split along M to fit the workspace budget numbers the rows per piece).  Unlike a render the feature
+        head runs on every in-box point, also where the density is not positive.
+
+        Evaluation mode only (``.eval()``), under ``torch.no_grad()``: gradients of a query are not implemented and a call that
+        would silently detach them raises."""
+        single = positions.dim() == 2
+        if single:
+            positions = positions.unsqueeze(0)
+            style = style.reshape(1, -1)
+            deformation = deformation.reshape(1, -1)
+            ray_origins = None if ray_origins is None else ray_origins.reshape(1, 3)
+            ray_directions = None if ray_directions is None else ray_directions.unsqueeze(0)
+        if positions.dim() != 3 or positions.size(-1) != 3:
+            raise ValueError(f"positions must be (G, M, 3) or (M, 3), got {list(positions.shape)}")
+        helper = self.object_id_helper
+        models = self.object_models_fine if fine else self.object_models_coarse
+        model = models[helper.model_idx_by_object_idx(object_idx)]
+        if model is None:
+            raise KeyError("fine")
+        field_query.require_queryable(self, (positions, style, deformation, ray_origins, ray_directions), self._parameter_list(model))
+        G, M = positions.size(0), positions.size(1)
+        cfg = model.model_config
+        S, D = cfg["style_features"], cfg["deformation_features"]
+        if list(style.shape) != [G, S] or list(deformation.shape) != [G, D]:
+            raise ValueError(f"style / deformation must be ({G}, {S}) / ({G}, {D}), got {list(style.shape)} / {list(deformation.shape)}")
+        skybox = model.nerf_model.kind == 1
+        if skybox:
+            if ray_origins is None or ray_directions is None:
+                raise ValueError("a skybox model is a function of the ray: pass ray_origins (G, 3) and ray_directions (G, M, 3)")
+            if list(ray_origins.shape) != [G, 3] or list(ray_directions.shape) != [G, M, 3]:
+                raise ValueError(f"ray_origins / ray_directions must be ({G}, 3) / ({G}, {M}, 3), got {list(ray_origins.shape)} / "
+                                 f"{list(ray_directions.shape)}")
+        dev = positions.device
+        prep = lambda t: t.detach().to(device=dev, dtype=torch.float32).contiguous()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            count = cfg["positions_count_coarse"] + (cfg["positions_count_fine"] if fine else 0)      # (the renderer's struct of this model)
+            struct = self._model_struct(model, count)
+            packed = self._packed_weights(model, struct, stream)
+
+            def workspace_of(need: int) -> torch.Tensor:
+                if self._workspace is None or self._workspace.numel() < need or self._workspace.device != dev:
+                    self._workspace = None
+                    self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+                return self._workspace
+
+            out = field_query.run_query(struct, packed, self._precision_code(), prep(positions), prep(style), prep(deformation),
+                                        prep(ray_origins) if skybox else None, prep(ray_directions) if skybox else None,
+                                        canonical_pose=bool(canonical_pose), features=bool(features), return_slot=bool(return_slot),
+                                        budget_of=lambda need: self._workspace_budget(dev, need), workspace_of=workspace_of)
+        if single:
+            out = {k: (v if k == "evaluated" else v[0]) for k, v in out.items()}
+        return out
+
+    def density_grid(self, object_idx: int, resolution, style: torch.Tensor, deformation: torch.Tensor, *, fine: bool = False,
+                     canonical_pose: bool = False):
+        """Raw density of object ``object_idx`` at the voxel centres of its model's bounding box: ``(sigma (G, nx, ny, nz), centres
+        (nx, ny, nz, 3))`` for ``style (G, S)`` / ``deformation (G, D)``; ``resolution`` = n or (nx, ny, nz).  A density-only query
+        (``query_object(..., features=False)``): what an occupancy mask or a mesh extraction starts from.  Skybox models have no
+        density field of their own (their density is the constant 10): they are refused."""
+        helper = self.object_id_helper
+        model = (self.object_models_fine if fine else self.object_models_coarse)[helper.model_idx_by_object_idx(object_idx)]
+        if model is None:
+            raise KeyError("fine")
+        if model.nerf_model.kind == 1:
+            raise ValueError("a skybox model has no density field (its density is 10 everywhere inside its box)")
+        n = [int(resolution)] * 3 if isinstance(resolution, int) else [int(v) for v in resolution]
+        if len(n) != 3 or min(n) < 1:
+            raise ValueError(f"resolution must be a positive integer or three of them, got {resolution!r}")
+        dev = style.device
+        box = torch.as_tensor(model.model_config["bounding_box"], dtype=torch.float32, device=dev)
+        axes = [box[a, 0] + (torch.arange(n[a], dtype=torch.float32, device=dev) + 0.5) * ((box[a, 1] - box[a, 0]) / n[a]) for a in range(3)]
+        centres = torch.stack(torch.meshgrid(*axes, indexing="ij"), dim=-1)
+        G = style.size(0)
+        out = self.query_object(object_idx, centres.reshape(1, -1, 3).expand(G, -1, 3), style, deformation, fine=fine,
+                                canonical_pose=canonical_pose, features=False)
+        return out["sigma"].reshape([G] + n), centres
 
     # ------------------------------------------------------------------ forward
     def forward(self, ray_origins: torch.Tensor, ray_directions: torch.Tensor, focal_normals: torch.Tensor,
