@@ -277,6 +277,49 @@ int pr_render_forward(const pr_call_t* call, const pr_object_t* objects,
                       void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Empty-space skipping for evaluation renders.  A grid divides the model's bounding box into cells[0] x cells[1] x cells[2] cells
+ * and holds one bit per cell and frame: bit (cell & 31) of word bits[n * words + (cell >> 5)], cell = (c_x * cells[1] + c_y) *
+ * cells[2] + c_z.  A sample at object-frame position x = o + d t (the unbent position the box test uses) is kept iff it passes
+ * the closed-interval box test and the bit of its cell is 1, with, in fp32 and without contraction,
+ *     u_a = (x_a - lo_a) * s_a,   s_a = (float)cells[a] / (hi_a - lo_a),   c_a = min(cells[a] - 1, (int)u_a).
+ * A culled sample is treated exactly like a sample outside the box: slot -1, density empty_space_alpha, feature row 0,
+ * displacement 0; it keeps its depth and takes part in compositing, the overlap fix and the resampler's CDF.  The grid of the
+ * coarse model culls the coarse pass, the grid of the fine model the merged coarse + resampled positions of the fine pass.
+ * bits == NULL: the object is not culled at that level.  A grid on a skybox model (kind == 1) or on a model whose box has an
+ * empty axis (hi <= lo) is refused.
+ */
+typedef struct pr_occupancy_grid_t {
+    const uint32_t* bits;            /* (N, words) device, or NULL */
+    int32_t cells[3];
+    int32_t words;                   /* words between frames, >= ceil(cells[0] * cells[1] * cells[2] / 32) */
+} pr_occupancy_grid_t;
+
+typedef struct pr_occupancy_t {
+    pr_occupancy_grid_t coarse[PR_MAX_OBJECTS];
+    pr_occupancy_grid_t fine[PR_MAX_OBJECTS];     /* read only when pr_call_t.use_fine != 0 */
+} pr_occupancy_t;
+
+/*
+ * pr_render_forward with occupancy grids (occupancy == NULL: exactly pr_render_forward).  Unperturbed evaluation calls only: with
+ * any grid set, PR_FLAG_PERTURB, an integrate-noise pointer, PR_FLAG_TRAIN_BN, PR_FLAG_SAVE_FOR_BACKWARD and PR_FLAG_NAIVE_MLP
+ * are refused (PR_ERR_INVALID).  pr_workspace_size is unchanged (culling only shrinks the row counts); evaluated_samples /
+ * head_samples report the counts after culling.  The bits are read when the kernels run: a call recorded into a HIP graph sees
+ * what pr_occupancy_build last wrote into them.
+ */
+int pr_render_forward_culled(const pr_call_t* call, const pr_object_t* objects, const pr_occupancy_t* occupancy,
+                             const pr_outputs_t* coarse, const pr_outputs_t* fine,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Builds occupancy bits from a density lattice: sigma (groups, cells[0] * s, cells[1] * s, cells[2] * s) with supersample factor
+ * s >= 1.  A cell is occupied iff any of its s^3 lattice values is > threshold; the occupied set is then grown by `dilate` >= 0
+ * cells over the full (2 dilate + 1)^3 neighbourhood, clipped at the box.  bits (groups, ceil(cells[0] * cells[1] * cells[2] / 32)):
+ * every word is written (tail bits 0) by ONE kernel launch - no memset, capturable into a HIP graph.
+ */
+int pr_occupancy_build(const float* sigma, int32_t groups, const int32_t* cells /* host, 3 */, int32_t supersample,
+                       float threshold, int32_t dilate, uint32_t* bits, void* stream);
+
+/*
  * Backward pass of pr_render_forward (what torch.autograd does for the reference's op graph when
  * training/trainer_backpropagated_autoencoder.py:349 calls total_loss.backward()).  The forward call must
  * have run with PR_FLAG_SAVE_FOR_BACKWARD (with or without PR_FLAG_TRAIN_BN) on the same `call`, `objects` and

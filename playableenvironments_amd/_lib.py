@@ -154,6 +154,16 @@ class Query(C.Structure):
                 ("slot", C.c_void_p), ("counters", C.c_void_p)]
 
 
+class OccupancyGrid(C.Structure):
+    """pr_occupancy_grid_t (include/playrender.h)."""
+    _fields_ = [("bits", C.c_void_p), ("cells", C.c_int32 * 3), ("words", C.c_int32)]
+
+
+class Occupancy(C.Structure):
+    """pr_occupancy_t (include/playrender.h)."""
+    _fields_ = [("coarse", OccupancyGrid * PR_MAX_OBJECTS), ("fine", OccupancyGrid * PR_MAX_OBJECTS)]
+
+
 # every exported symbol of include/playrender.h : (restype, argtypes)
 class SceneSetup(C.Structure):
     """pr_scene_setup_t (include/playrender.h)."""
@@ -176,6 +186,9 @@ SYMBOLS = {
     "pr_workspace_size": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(C.c_size_t)]),
     "pr_render_forward": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(Outputs), C.POINTER(Outputs),
                                     C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pr_render_forward_culled": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(Occupancy), C.POINTER(Outputs), C.POINTER(Outputs),
+                                           C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pr_occupancy_build": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p]),
     "pr_backward_workspace_size": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(C.c_size_t)]),
     "pr_render_backward": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(OutputGrads), C.POINTER(OutputGrads),
                                      C.POINTER(InputGrads), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),

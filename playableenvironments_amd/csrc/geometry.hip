@@ -108,9 +108,10 @@ __device__ __forceinline__ void ray_bounds(const ObjRay& ray, const float* lo, c
 struct WaveRay {
     float o[3], d[3];
     int valid;
+    int frame;      // read by the occupancy lookup only
 };
 
-__device__ __forceinline__ WaveRay broadcast_ray(const ObjRay& ray, bool valid, int src) {
+__device__ __forceinline__ WaveRay broadcast_ray(const ObjRay& ray, bool valid, int frame, int src) {
     WaveRay w;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -118,6 +119,7 @@ __device__ __forceinline__ WaveRay broadcast_ray(const ObjRay& ray, bool valid, 
         w.d[a] = __shfl(ray.d[a], src, 64);
     }
     w.valid = __shfl((int)valid, src, 64);
+    w.frame = __shfl(frame, src, 64);
     return w;
 }
 
@@ -150,9 +152,10 @@ __device__ __forceinline__ void place_coarse_body(const PlaceParams& p) {
     const long total = (long)p.frames * p.rays;
     ObjRay ray = {};
     bool valid = false;
+    int frame = 0;
     float z_near = 0.f, z_far = 0.f;
     if (g < total) {
-        const int n = (int)(g / p.rays);
+        const int n = frame = (int)(g / p.rays);
         const float* m = p.w2o + ((size_t)n * p.objects + p.object_index) * 12;
         ray = object_ray(m, p.ray_origins + (size_t)n * 3, p.ray_directions + (size_t)g * 3);
         valid = p.in_scene[(size_t)n * p.objects + p.object_index] != 0;
@@ -165,7 +168,7 @@ __device__ __forceinline__ void place_coarse_body(const PlaceParams& p) {
     for (int r0 = 0; r0 < 64 && wave_first + r0 < total; r0 += L.per_pass) {
         const int r = r0 + L.sub;
         const bool live = wave_first + r < total;
-        const WaveRay w = broadcast_ray(ray, valid, r);
+        const WaveRay w = broadcast_ray(ray, valid, frame, r);
         const float zn = __shfl(z_near, r, 64), zf = __shfl(z_far, r, 64);
         const size_t base = (size_t)(wave_first + r) * P;
         // t_i = near * (1 - s_i) + far * s_i
@@ -192,7 +195,7 @@ __device__ __forceinline__ void place_coarse_body(const PlaceParams& p) {
                 const float x = __fadd_rn(w.o[0], __fmul_rn(w.d[0], t));
                 const float y = __fadd_rn(w.o[1], __fmul_rn(w.d[1], t));
                 const float z = __fadd_rn(w.o[2], __fmul_rn(w.d[2], t));
-                inside = in_box(x, y, z, p.lo, p.hi);   // absent objects too: the reference evaluates their samples (near = far = 0, clamped) and
+                inside = sample_kept(x, y, z, p.lo, p.hi, p.occ, w.frame);   // absent objects too: the reference evaluates their samples (near = far = 0, clamped) and
                                                         // only overrides their densities afterwards (object_composer.py:546-547)
             }
             ray_count += __popcll(L.mine(__ballot(inside)));
@@ -204,7 +207,8 @@ __device__ __forceinline__ void place_coarse_body(const PlaceParams& p) {
     if (threadIdx.x == 0) p.block_sums[blockIdx.x] = block_total;
 }
 
-__global__ __launch_bounds__(256) void k_place_coarse(PlaceParams p) { place_coarse_body(p); }
+// (waves_per_eu: the grid's fields take the kernel past 96 SGPRs otherwise, which costs the eighth wave per SIMD)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void k_place_coarse(PlaceParams p) { place_coarse_body(p); }
 // the objects of a call in one launch: blockIdx.y = object
 struct PlaceGroup { PlaceParams p[PR_MAX_OBJECTS]; };
 __global__ __launch_bounds__(256) void k_place_coarse_group(PlaceGroup g) { place_coarse_body(g.p[blockIdx.y]); }
@@ -262,8 +266,9 @@ __device__ __forceinline__ void fill_body(const FillParams& p) {
     const int P = p.positions;
     ObjRay ray = {};
     bool valid = false;
+    int frame = 0;
     if (g < total) {
-        const int n = (int)(g / p.rays);
+        const int n = frame = (int)(g / p.rays);
         const float* m = p.w2o + ((size_t)n * p.objects + p.object_index) * 12;
         ray = object_ray(m, p.ray_origins + (size_t)n * 3, p.ray_directions + (size_t)g * 3);
         valid = p.in_scene[(size_t)n * p.objects + p.object_index] != 0;
@@ -274,7 +279,7 @@ __device__ __forceinline__ void fill_body(const FillParams& p) {
     auto walk = [&](auto&& per_ray) {
         for (int r0 = 0; r0 < 64 && wave_first + r0 < total; r0 += L.per_pass) {
             const int r = r0 + L.sub;
-            per_ray(r0, r, wave_first + r < total, broadcast_ray(ray, valid, r), (size_t)(wave_first + r) * P);
+            per_ray(r0, r, wave_first + r < total, broadcast_ray(ray, valid, frame, r), (size_t)(wave_first + r) * P);
         }
     };
     auto inside_at = [&](bool live, const WaveRay& w, size_t base, int i, float* x, float* y, float* z) {
@@ -283,7 +288,7 @@ __device__ __forceinline__ void fill_body(const FillParams& p) {
         *x = __fadd_rn(w.o[0], __fmul_rn(w.d[0], t));
         *y = __fadd_rn(w.o[1], __fmul_rn(w.d[1], t));
         *z = __fadd_rn(w.o[2], __fmul_rn(w.d[2], t));
-        return in_box(*x, *y, *z, p.lo, p.hi);    // (absent objects included, see k_place_coarse)
+        return sample_kept(*x, *y, *z, p.lo, p.hi, p.occ, w.frame);    // (absent objects included, see k_place_coarse)
     };
     int count = 0;
     walk([&](int r0, int r, bool live, const WaveRay& w, size_t base) {
@@ -493,7 +498,7 @@ __global__ __launch_bounds__(64) void k_resample(ResampleParams p, int sort_size
         const float x = __fadd_rn(ray.o[0], __fmul_rn(ray.d[0], t));
         const float y = __fadd_rn(ray.o[1], __fmul_rn(ray.d[1], t));
         const float z = __fadd_rn(ray.o[2], __fmul_rn(ray.d[2], t));
-        if (in_box(x, y, z, p.lo, p.hi)) ++count;      // (absent objects included, see k_place_coarse)
+        if (sample_kept(x, y, z, p.lo, p.hi, p.occ, n)) ++count;      // (absent objects included, see k_place_coarse)
     }
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) count += __shfl_down(count, d, 64);

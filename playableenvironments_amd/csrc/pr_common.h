@@ -298,6 +298,16 @@ static inline NoiseRef perturb_noise(const float* ptr, const pr_call_t& c, int k
 // ---------------------------------------------------------------------------------------------
 // Stage launchers (each enqueues on `stream`, returns pr_status)
 // ---------------------------------------------------------------------------------------------
+// Occupancy bitfield of one object instance and model level (pr_occupancy_grid_t + the model's box; occupancy.hip).  bits == NULL:
+// the object is not culled and the kept-sample predicate is the box test alone.
+struct OccGrid {
+    const uint32_t* bits;         // (N, words) one bit per cell, cell = (cx * n[1] + cy) * n[2] + cz, bit (cell & 31) of word (cell >> 5)
+    int n[3];
+    int words;                    // words between frames
+    float scale[3];               // float(n_a) / (hi_a - lo_a), rounded once on the host
+};
+int make_occ_grid(const pr_occupancy_grid_t* g, const pr_object_model_t& m, int object, const char* level, OccGrid* out);
+
 struct PlaceParams {
     int frames, rays, positions, objects, object_index;
     const float* ray_origins;     // (N,3)
@@ -312,6 +322,7 @@ struct PlaceParams {
     float* sigma;                 // (N,R,P) out, filled with empty_alpha
     float* dispmag;               // (N,R,P) out zeros or NULL
     int32_t* block_sums;          // (ceil(N*R/256)) in-box counts per block of 256 rays
+    OccGrid occ;                  // empty-space skipping (evaluation calls), or bits == NULL
 };
 int launch_place_coarse(const PlaceParams& p, hipStream_t s);
 
@@ -327,6 +338,7 @@ struct FillParams {
     float* rec_pos;               // (cap,3)
     int32_t* rec_flat;            // (cap)
     int32_t* slot;                // (N,R,P) compact row or -1
+    OccGrid occ;
 };
 int launch_fill(const FillParams& p, hipStream_t s);
 int launch_placement_group(const PlaceParams* pp, const FillParams* fp, int32_t* const* totals, int count, hipStream_t s);
@@ -352,6 +364,7 @@ struct ResampleParams {
     float* sigma_fine;            // (N,R,Pc+Pf) out, filled with empty_alpha
     float* dispmag_fine;          // or NULL
     int32_t* block_sums;
+    OccGrid occ;                  // grid of the FINE model: culls the merged coarse + resampled positions
 };
 int launch_resample(const ResampleParams& p, hipStream_t s);
 
@@ -498,6 +511,7 @@ int prepare_kernel(const void* kernel, int lds_bytes, int* cu_count);
 // zero `bytes` bytes (a multiple of 4, 4-byte aligned) with a kernel on `s`
 int launch_zero_fill(void* dst, size_t bytes, hipStream_t s);
 int validate_call(const pr_call_t& c, const pr_object_t* objs);
+int validate_occupancy(const pr_call_t& c, const pr_object_t* objs, const pr_occupancy_t* occ);
 bool group_active(const pr_call_t& c);
 bool group_train_active(const pr_call_t& c);
 bool gate_active(const pr_call_t& c);
@@ -758,6 +772,21 @@ __device__ __forceinline__ ObjRay object_ray(const float* __restrict__ m /*3x4*/
 
 __device__ __forceinline__ bool in_box(const float x, const float y, const float z, const float* lo, const float* hi) {
     return x >= lo[0] && x <= hi[0] && y >= lo[1] && y <= hi[1] && z >= lo[2] && z <= hi[2];
+}
+
+// The kept-sample predicate of the renderer's three cull sites (k_place_coarse's count, k_fill, k_resample's count - they must
+// agree, the compaction offsets are sums of it): the closed-interval box test and, with a grid, the bit of the sample's cell.
+// u_a = (x_a - lo_a) * s_a in fp32 without contraction, truncated and clamped to n_a - 1 (u_a >= 0 inside the box; x_a == hi_a
+// lands in the last cell): what occupancy.cell_index restates in torch.
+__device__ __forceinline__ bool sample_kept(const float x, const float y, const float z, const float* lo, const float* hi,
+                                            const OccGrid& g, int frame) {
+    if (!in_box(x, y, z, lo, hi)) return false;
+    if (!g.bits) return true;
+    const int cx = min(g.n[0] - 1, (int)__fmul_rn(__fsub_rn(x, lo[0]), g.scale[0]));
+    const int cy = min(g.n[1] - 1, (int)__fmul_rn(__fsub_rn(y, lo[1]), g.scale[1]));
+    const int cz = min(g.n[2] - 1, (int)__fmul_rn(__fsub_rn(z, lo[2]), g.scale[2]));
+    const int cell = (cx * g.n[1] + cy) * g.n[2] + cz;
+    return (g.bits[(size_t)frame * g.words + (cell >> 5)] >> (cell & 31)) & 1u;
 }
 #endif
 

@@ -288,8 +288,8 @@ void bbox_split(const pr_object_model_t& m, float* lo, float* hi, float* size) {
     }
 }
 
-static int render(const pr_call_t& c, const pr_object_t* objs, const pr_outputs_t* outs[2], char* ws, const Plan& plan,
-                  hipStream_t s) {
+static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupancy_t* occupancy, const pr_outputs_t* outs[2], char* ws,
+                  const Plan& plan, hipStream_t s) {
     const int ntypes = c.use_fine ? 2 : 1;
     const int K = c.objects;
     int32_t* block_sums_all = reinterpret_cast<int32_t*>(ws + plan.block_sums);
@@ -420,6 +420,10 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_outputs_
             float* adain = reinterpret_cast<float*>(ws + tp.adain[k]);
             const bool save = (c.flags & PR_FLAG_SAVE_FOR_BACKWARD) != 0;
             const SavedPlan& sv = tp.saved[k];
+            // empty-space skipping: the grid of this object and model type (bits == NULL without one) - the same grid at the
+            // count and the fill site of the type
+            OccGrid occ;
+            PR_TRY(make_occ_grid(occupancy ? (t ? &occupancy->fine[k] : &occupancy->coarse[k]) : nullptr, m, k, t ? "fine" : "coarse", &occ));
             if (save) {
                 rec_pos = reinterpret_cast<float*>(ws + sv.rec_pos);
                 rec_flat = reinterpret_cast<int32_t*>(ws + sv.rec_flat);
@@ -440,6 +444,7 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_outputs_
                 pp.linspace = c.linspace_coarse[k];
                 pp.jitter = perturb_noise(c.noise_coarse.jitter[k], c, NOISE_JITTER, 0, k);
                 pp.t = t_arr; pp.sigma = sigma; pp.dispmag = dispmag; pp.block_sums = block_sums;
+                pp.occ = occ;
                 if (pass == 0) place_jobs[k] = pp;
                 else if (!placed) PR_TRY(launch_place_coarse(pp, s));
             } else {
@@ -458,6 +463,7 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_outputs_
                 rp.u_fixed = c.linspace_fine[k];
                 rp.u_random = perturb_noise(c.noise_coarse.pdf[k], c, NOISE_PDF, 0, k);
                 rp.t_fine = t_arr; rp.sigma_fine = sigma; rp.dispmag_fine = dispmag; rp.block_sums = block_sums;
+                rp.occ = occ;
                 PR_TRY(launch_resample(rp, s));
             }
             if (pass == 1 && !placed) PR_TRY(launch_scan(block_sums, block_offsets, totals + k, plan.nblocks256, s));
@@ -470,6 +476,7 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_outputs_
             fp.in_scene = c.object_in_scene;
             bbox_split(m, fp.lo, fp.hi, nullptr);
             fp.t = t_arr; fp.block_offsets = block_offsets; fp.rec_pos = rec_pos; fp.rec_flat = rec_flat; fp.slot = slot;
+            fp.occ = occ;
             if (pass == 0) {
                 fill_jobs[k] = fp;
                 total_ptrs[k] = totals + k;
@@ -732,7 +739,14 @@ extern "C" int pr_workspace_size(const pr_call_t* call, const pr_object_t* objec
 
 extern "C" int pr_render_forward(const pr_call_t* call, const pr_object_t* objects, const pr_outputs_t* coarse,
                                  const pr_outputs_t* fine, void* workspace, size_t workspace_bytes, void* stream) {
+    return pr_render_forward_culled(call, objects, nullptr, coarse, fine, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pr_render_forward_culled(const pr_call_t* call, const pr_object_t* objects, const pr_occupancy_t* occupancy,
+                                        const pr_outputs_t* coarse, const pr_outputs_t* fine, void* workspace, size_t workspace_bytes,
+                                        void* stream) {
     PR_REQUIRE(call && objects && workspace, "pr_render_forward: NULL argument");
+    PR_TRY(pr::validate_occupancy(*call, objects, occupancy));
     PR_TRY(pr::validate_call(*call, objects));
     pr::Plan plan;
     PR_TRY(pr::make_plan(*call, objects, &plan));
@@ -742,7 +756,7 @@ extern "C" int pr_render_forward(const pr_call_t* call, const pr_object_t* objec
     }
     PR_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
     const pr_outputs_t* outs[2] = {coarse, fine};
-    return pr::render(*call, objects, outs, static_cast<char*>(workspace), plan, (hipStream_t)stream);
+    return pr::render(*call, objects, occupancy, outs, static_cast<char*>(workspace), plan, (hipStream_t)stream);
 }
 
 namespace pr {

@@ -10,6 +10,7 @@ from __future__ import annotations
 
 import ctypes as C
 import math
+import operator
 import threading
 import warnings
 import weakref
@@ -18,7 +19,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from . import _lib, field_query
+from . import _lib, field_query, occupancy as _occupancy
 from .modules import OBJECT_MODEL_CLASSES, REGISTRATION_EPOCH as _REGISTRATION_EPOCH, ModuleList, RayBendingStyleNerfModel, Tracked, \
     tree_is_tracked
 
@@ -458,6 +459,11 @@ class ObjectComposer(Tracked, nn.Module):
         #: ``extra_outputs`` only).  On a shipped 256x256 tennis frame the per-object maps are 4/5 of the compositing kernel's
         #: 344 MB of output.  Ignored (everything is produced) by differentiable / training calls.
         self.object_entry_fields: Optional[Tuple[str, ...]] = None
+        #: empty-space skipping: ``None`` (default), or an ``occupancy.Occupancy`` (``build_occupancy`` / ``occupancy_from_mask``) -
+        #: evaluation renders then treat every sample whose cell bit is 0 exactly like a sample outside the object's box
+        #: (``pr_render_forward_culled``): it never reaches the MLP.  Not handed to perturbed, training or differentiable calls, nor
+        #: to ``forward_expected_positions``.  The grid's frame count must be the call's.
+        self.occupancy: Optional[_occupancy.Occupancy] = None
         #: callables invoked by the autograd node of a differentiable call with the flat fp32 buffer that every parameter gradient
         #: of the call is a view of, right after ``pr_render_backward`` is enqueued (parallel.OverlappedGradientAllReduce starts the
         #: gradient all-reduce from here, so that it overlaps the rest of ``backward()``)
@@ -597,7 +603,7 @@ class ObjectComposer(Tracked, nn.Module):
         ``nn.Module._replicate_for_data_parallel`` would otherwise share dictionaries that hold device-0 pointers between the
         replicas' threads.  A replica lives for one call: it packs the broadcast weights it is given and never caches lists."""
         replica = super()._replicate_for_data_parallel()
-        fresh = dict(gradient_hooks=[], _packed={}, _param_lists={}, _structs={}, _tracked={}, _annealing={}, _linspace={}, _workspace=None,
+        fresh = dict(occupancy=None, gradient_hooks=[], _packed={}, _param_lists={}, _structs={}, _tracked={}, _annealing={}, _linspace={}, _workspace=None,
                      _budget_ok=0, _pending_bn_check=None, last_normalised_samples={}, last_noise_seed=None)
         replica.__dict__.update(fresh)
         # (the replica's backward pass reports parameter gradients to the ORIGINAL: its packed copies / recorded frames are what an
@@ -609,7 +615,7 @@ class ObjectComposer(Tracked, nn.Module):
         # copy.deepcopy / pickle (EMA helpers, swa_utils.AveragedModel): the caches hold ctypes structures with raw pointers
         # (not picklable) and device scratch that a copy must not share
         state = dict(self.__dict__)
-        state.update(gradient_hooks=[], _packed={}, _param_lists={}, _structs={}, _tracked={}, _annealing={}, _linspace={}, _workspace=None, _budget_ok=0,
+        state.update(occupancy=None, gradient_hooks=[], _packed={}, _param_lists={}, _structs={}, _tracked={}, _annealing={}, _linspace={}, _workspace=None, _budget_ok=0,
                      _pending_bn_check=None, last_normalised_samples={}, last_noise_seed=None, _host_step=None)
         state.pop("_replica_of", None)
         return state
@@ -835,23 +841,117 @@ class ObjectComposer(Tracked, nn.Module):
         (nx, ny, nz, 3))`` for ``style (G, S)`` / ``deformation (G, D)``; ``resolution`` = n or (nx, ny, nz).  A density-only query
         (``query_object(..., features=False)``): what an occupancy mask or a mesh extraction starts from.  Skybox models have no
         density field of their own (their density is the constant 10): they are refused."""
-        helper = self.object_id_helper
-        model = (self.object_models_fine if fine else self.object_models_coarse)[helper.model_idx_by_object_idx(object_idx)]
-        if model is None:
-            raise KeyError("fine")
-        if model.nerf_model.kind == 1:
-            raise ValueError("a skybox model has no density field (its density is 10 everywhere inside its box)")
+        self._occupancy_model(object_idx, "fine" if fine else "coarse")        # (KeyError("fine") / skybox refusal first, as before)
         n = [int(resolution)] * 3 if isinstance(resolution, int) else [int(v) for v in resolution]
         if len(n) != 3 or min(n) < 1:
             raise ValueError(f"resolution must be a positive integer or three of them, got {resolution!r}")
-        dev = style.device
-        box = torch.as_tensor(model.model_config["bounding_box"], dtype=torch.float32, device=dev)
-        axes = [box[a, 0] + (torch.arange(n[a], dtype=torch.float32, device=dev) + 0.5) * ((box[a, 1] - box[a, 0]) / n[a]) for a in range(3)]
-        centres = torch.stack(torch.meshgrid(*axes, indexing="ij"), dim=-1)
+        centres = self._grid_centres(object_idx, n, fine, style.device)
         G = style.size(0)
         out = self.query_object(object_idx, centres.reshape(1, -1, 3).expand(G, -1, 3), style, deformation, fine=fine,
                                 canonical_pose=canonical_pose, features=False)
         return out["sigma"].reshape([G] + n), centres
+
+    def _grid_centres(self, object_idx: int, n, fine: bool, dev) -> torch.Tensor:
+        """Voxel centres ``(nx, ny, nz, 3)`` of the box of object ``object_idx``'s model (``density_grid``, ``Occupancy.update``)."""
+        model = self._occupancy_model(object_idx, "fine" if fine else "coarse")
+        box = torch.as_tensor(model.model_config["bounding_box"], dtype=torch.float32, device=dev)
+        axes = [box[a, 0] + (torch.arange(n[a], dtype=torch.float32, device=dev) + 0.5) * ((box[a, 1] - box[a, 0]) / n[a]) for a in range(3)]
+        return torch.stack(torch.meshgrid(*axes, indexing="ij"), dim=-1)
+
+    # ------------------------------------------------------------------ occupancy grids
+    def _occupancy_model(self, object_idx: int, level: str):
+        """The model behind a density lattice or an occupancy grid; refuses what has no density field."""
+        helper = self.object_id_helper
+        try:
+            object_idx = operator.index(object_idx)        # (numpy / torch integers are taken like Python ones)
+        except TypeError:
+            raise ValueError(f"object index {object_idx!r} is not an integer") from None
+        if not 0 <= object_idx < helper.objects_count:
+            raise ValueError(f"object index {object_idx!r} out of range 0..{helper.objects_count - 1}")
+        if level not in _occupancy.LEVELS:
+            raise ValueError(f"unknown level {level!r} (expected 'coarse' or 'fine')")
+        model = (self.object_models_fine if level == "fine" else self.object_models_coarse)[helper.model_idx_by_object_idx(object_idx)]
+        if model is None:
+            raise KeyError("fine")
+        if model.nerf_model.kind == 1:
+            raise ValueError("a skybox model has no density field (its density is 10 everywhere inside its box)")
+        return model
+
+    def _occupancy_levels(self, object_idx: int):
+        fine = self.object_models_fine[self.object_id_helper.model_idx_by_object_idx(object_idx)]
+        return _occupancy.LEVELS if fine is not None else _occupancy.LEVELS[:1]
+
+    def build_occupancy(self, style: torch.Tensor, deformation: torch.Tensor, *, resolution=32, supersample: int = 2,
+                        threshold: float = 0.0, dilate: int = 1, objects=None, canonical_pose: bool = False) -> "_occupancy.Occupancy":
+        """Occupancy grids from the objects' own density fields, for ``composer.occupancy = ...``.  ``style (..., S, K)`` /
+        ``deformation (..., D, K)`` in ``forward``'s layout (one grid per frame of the leading dimensions).  For every chosen
+        object (``objects=None``: every object that is not a skybox), every frame, the coarse model and - where there is one - the
+        fine model: ``density_grid`` at ``resolution * supersample`` points per axis, then ``pr_occupancy_build``: a cell is occupied
+        iff any of its ``supersample ** 3`` lattice values is ``> threshold``, and the occupied set is grown by ``dilate`` cells.
+        A lattice samples the field: structure thinner than a lattice step can be missed (``dilate`` and ``supersample`` are the
+        margins).  Evaluation mode, under ``torch.no_grad()``."""
+        n = _occupancy._cells_of(resolution)
+        if int(supersample) < 1 or int(dilate) < 0:
+            raise ValueError(f"supersample must be >= 1 and dilate >= 0, got {supersample} / {dilate}")
+        helper = self.object_id_helper
+        if objects is None:
+            chosen = [k for k in range(helper.objects_count)
+                      if self.object_models_coarse[helper.model_idx_by_object_idx(k)].nerf_model.kind != 1]
+        else:
+            chosen = [int(k) for k in objects]
+        if style.size(-1) != helper.objects_count or deformation.size(-1) != helper.objects_count:
+            raise ValueError(f"style / deformation carry {style.size(-1)} / {deformation.size(-1)} objects, the composer has {helper.objects_count}")
+        frames = int(math.prod(style.shape[:-2])) if style.dim() > 2 else 1
+        dev = style.device
+        for k in chosen:
+            for level in self._occupancy_levels(k):        # (refuses skybox models and boxes with an empty axis)
+                _occupancy.cell_scale(self._occupancy_model(k, level).model_config["bounding_box"], n)
+        if dev.type != "cuda":
+            raise RuntimeError("the HIP renderer needs device tensors (there is no CPU fallback)")
+        grids = {}
+        for k in chosen:
+            for level in self._occupancy_levels(k):
+                grids[(k, level)] = {"bits": torch.empty((frames, _occupancy.words_of(n)), dtype=torch.int32, device=dev), "cells": n}
+        occ = _occupancy.Occupancy(self, frames, grids, build=dict(resolution=n, supersample=int(supersample), threshold=float(threshold),
+                                                                   dilate=int(dilate), canonical_pose=bool(canonical_pose)))
+        return occ.update(style, deformation)
+
+    def occupancy_from_mask(self, masks: Dict) -> "_occupancy.Occupancy":
+        """Occupancy grids from caller-supplied voxel masks (known scene layouts): ``{object_idx: bool (N, nx, ny, nz)}`` sets the
+        coarse and - where the object has one - the fine grid; ``{(object_idx, "coarse" | "fine"): ...}`` one level.  ``True`` =
+        the cell may hold matter.  Objects that are not named are not culled."""
+        grids = {}
+        frames = None
+        for key, mask in masks.items():
+            k, levels = (key[0], (key[1],)) if isinstance(key, tuple) else (key, None)
+            if levels is None:
+                self._occupancy_model(k, "coarse")
+                levels = self._occupancy_levels(k)
+            if not torch.is_tensor(mask) or mask.dtype != torch.bool or mask.dim() != 4:
+                raise ValueError(f"object {k}: an occupancy mask is a bool tensor (N, nx, ny, nz)")
+            if frames is None:
+                frames = mask.size(0)
+            if mask.size(0) != frames:
+                raise ValueError(f"object {k}: the mask holds {mask.size(0)} frame(s), the masks before it {frames}")
+            for level in levels:
+                model = self._occupancy_model(k, level)
+                _occupancy.cell_scale(model.model_config["bounding_box"], tuple(mask.shape[1:]))
+                grids[(k, level)] = {"bits": _occupancy.pack_bits(mask), "cells": tuple(int(v) for v in mask.shape[1:])}
+        if frames is None:
+            raise ValueError("occupancy_from_mask needs at least one mask")
+        return _occupancy.Occupancy(self, frames, grids)
+
+    def _occupancy_for_call(self, frames, ids, use_fine, perturb, save, object_ids, style_nks, deformation_nkd, canonical_pose, dev):
+        """``pr_occupancy_t`` of an evaluation call, or None: the grid applies to unperturbed evaluation calls under no_grad."""
+        occ = self.occupancy
+        if occ is None or perturb or save or self.training or object_ids is not None or self.use_naive_mlp or torch.is_grad_enabled():
+            return None
+        if not isinstance(occ, _occupancy.Occupancy):
+            raise TypeError(f"ObjectComposer.occupancy must be an occupancy.Occupancy or None, got {type(occ).__name__}")
+        struct = occ.call_struct(frames, ids, use_fine, dev)
+        if occ.follow:
+            occ.update_prepared(style_nks, deformation_nkd, canonical_pose)
+        return struct
 
     # ------------------------------------------------------------------ forward
     def forward(self, ray_origins: torch.Tensor, ray_directions: torch.Tensor, focal_normals: torch.Tensor,
@@ -1133,6 +1233,8 @@ class ObjectComposer(Tracked, nn.Module):
                     get(f"int_{ty}_{k}", (N, R, ptot[ty][k]), True)
                 get(f"int_{ty}_global", (N, R, sum(ptot[ty])), True)
 
+        culled = self._occupancy_for_call(N, ids, use_fine, perturb, _save, _object_ids, sty, dfm, canonical_pose, dev)
+
         # ---- ray chunking against the workspace budget -----------------------------------------
         def build_call(r0: int, r1: int):
             call = _lib.Call()
@@ -1283,10 +1385,16 @@ class ObjectComposer(Tracked, nn.Module):
                     res["_samples"] = ex
                 outs[ty] = res
                 structs[ty] = o
-            _lib.check(lib.pr_render_forward(C.byref(call), objs, C.byref(structs["coarse"]),
-                                             C.byref(structs["fine"]) if use_fine else None,
-                                             workspace.data_ptr(), workspace.numel(), stream),
-                       "pr_render_forward")
+            if culled is not None:
+                _lib.check(lib.pr_render_forward_culled(C.byref(call), objs, C.byref(culled), C.byref(structs["coarse"]),
+                                                        C.byref(structs["fine"]) if use_fine else None,
+                                                        workspace.data_ptr(), workspace.numel(), stream),
+                           "pr_render_forward_culled")
+            else:
+                _lib.check(lib.pr_render_forward(C.byref(call), objs, C.byref(structs["coarse"]),
+                                                 C.byref(structs["fine"]) if use_fine else None,
+                                                 workspace.data_ptr(), workspace.numel(), stream),
+                           "pr_render_forward")
             pieces.append(outs)
             if _save:
                 state = dict(call=call, objs=objs, keep=keep + packed_keep + [origins, w2o, sty, dfm, present], workspace=workspace,
