@@ -89,6 +89,16 @@ typedef enum pr_status {
                                        selects fp16-pair products for phase 1 of a train-mode forward pass too.  The call
                                        stays PR_PRECISION_FP32 (fp32-packed weights, which carry both split forms as well).  Products
                                        that have no split kernel run the exact fp32 one. */
+#define PR_FLAG_DEFER_PROJECTION 2048u /* deferred projection: features_head.6 is a Linear with nothing behind it and its rows are only ever
+                                       summed under the compositing weights, so sum_i w_i (W6 h_i + b6) = W6 (sum_i w_i h_i) + b6 sum_i w_i.
+                                       With this flag the MLP kernels stop behind features_head.4 and write [h, 1] rows (W/2 + 1 floats,
+                                       padded to a multiple of 4; the 1 is 0 on the rows the network wrote as zeros), compositing pools
+                                       those rows per object under the object's own and under the global weights, and one matrix product
+                                       per ray applies [W6 | b6].  Every field except integrated_features and the decoder maps is
+                                       bit-identical; those two differ by fp32 re-association.  Honoured for PR_PRECISION_FP32 evaluation
+                                       calls only - ignored with PR_FLAG_SAVE_FOR_BACKWARD, PR_FLAG_TRAIN_BN, PR_FLAG_SIGMOID_FEATURES
+                                       (the sigmoid sits between the projection and the sum) and PR_FLAG_NAIVE_MLP.  Perturbed calls
+                                       are eligible.  The workspace grows by the pooled rows (pr_workspace_size accounts for them). */
 #define PR_FLAG_DIVERGENCE_GRAD 256u /* pr_backward_workspace_size / pr_render_backward: gradients of integrated_divergence are
                                        given (pr_entry_grads_t.integrated_divergence); the backward pass then differentiates the
                                        Hutchinson estimate e^T (d delta / dx) e through the ray bender (the reference's double

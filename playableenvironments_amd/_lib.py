@@ -20,6 +20,7 @@ PR_FLAG_NAIVE_MLP = 8
 PR_FLAG_TRAIN_BN = 16
 PR_FLAG_SAVE_FOR_BACKWARD = 32
 PR_FLAG_GATE_HEAD = 64
+PR_FLAG_DEFER_PROJECTION = 2048
 PR_FLAG_DEVICE_NOISE = 128
 PR_FLAG_DIVERGENCE_GRAD = 256
 PR_FLAG_SIGMOID_FEATURES = 512

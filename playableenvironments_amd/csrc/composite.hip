@@ -103,6 +103,29 @@ __device__ __forceinline__ float block_sum(float v, float* scratch, int wave, in
     return total;
 }
 
+// The per-wave channel sums `acc` (lane l owns the channels l + 64 c) added in wave order and stored by wave 0 as the F floats at dst.
+template <int CW>
+__device__ __forceinline__ void store_channel_sums(float (&acc)[MAX_FCHUNK], float* dst, int F, float* scratch, int wave, int lane) {
+    if (CW > 1) {
+#pragma unroll
+        for (int c = 0; c < MAX_FCHUNK; ++c) {      // one 64-channel chunk at a time: 1 KB of scratch
+            if (64 * c >= F) break;
+            __syncthreads();
+            scratch[wave * 64 + lane] = acc[c];
+            __syncthreads();
+            if (wave == 0)
+                for (int w = 1; w < CW; ++w) acc[c] = __fadd_rn(acc[c], scratch[w * 64 + lane]);
+        }
+    }
+    if (wave == 0) {
+#pragma unroll
+        for (int c = 0; c < MAX_FCHUNK; ++c) {
+            const int ch = lane + 64 * c;
+            if (ch < F) dst[ch] = acc[c];
+        }
+    }
+}
+
 // CW waves per ray.  Lists of a few hundred entries per ray keep the LDS footprint of a ray at tens of KB, i.e. a
 // handful of rays per CU: with one wave per ray the latency-bound phases (staging, scans, merge) and the number of
 // feature rows in flight were what set the kernel's time.  Wave w integrates the objects w, w + CW, ...; staging, the
@@ -304,6 +327,7 @@ __global__ __launch_bounds__(64 * CW) void k_composite(CompositeParams p) {
     // then consumed ROWS_IN_FLIGHT rows at a time.  Every wave accumulates all F channels of its part; the parts are added
     // in wave order.
     const int F = p.F;
+    const bool defer = p.pooled != nullptr;
     int* lrow = reinterpret_cast<int*>(sm.key);   // the ranks and the depths are dead by now
     float* lw1 = sm.tt;
     float accg[MAX_FCHUNK];
@@ -394,48 +418,21 @@ __global__ __launch_bounds__(64 * CW) void k_composite(CompositeParams p) {
                 accg[c] = __fadd_rn(accg[c], 0.5f * bare2);
             }
         }
-        if (o.out.integrated_features) {
-            if (CW > 1) {
+        // deferred projection (p.pooled): the rows are hidden rows [h | 1]; the sums of THIS object under its own and under the
+        // global weights go to the pooled blocks 2 k and 2 k + 1, launch_projection applies [W6 | b6] of the object's model
+        if (o.out.integrated_features)
+            store_channel_sums<CW>(acco, defer ? p.pooled + ((size_t)(2 * k) * gridDim.x + g) * F : o.out.integrated_features + (size_t)g * F, F,
+                                   scratch, wave, lane);
+        if (defer) {
+            if (p.global.integrated_features || p.decoder.groups > 0)
+                store_channel_sums<CW>(accg, p.pooled + ((size_t)(2 * k + 1) * gridDim.x + g) * F, F, scratch, wave, lane);
 #pragma unroll
-                for (int c = 0; c < MAX_FCHUNK; ++c) {      // one 64-channel chunk at a time: 1 KB of scratch
-                    if (64 * c >= F) break;
-                    __syncthreads();
-                    scratch[wave * 64 + lane] = acco[c];
-                    __syncthreads();
-                    if (wave == 0)
-                        for (int w = 1; w < CW; ++w) acco[c] = __fadd_rn(acco[c], scratch[w * 64 + lane]);
-                }
-            }
-            if (wave == 0) {
-#pragma unroll
-                for (int c = 0; c < MAX_FCHUNK; ++c) {
-                    const int ch = lane + 64 * c;
-                    if (ch < F) o.out.integrated_features[(size_t)g * F + ch] = acco[c];
-                }
-            }
+            for (int c = 0; c < MAX_FCHUNK; ++c) accg[c] = 0.f;
         }
         off += P;
     }
-    if (p.global.integrated_features) {
-        if (CW > 1) {
-#pragma unroll
-            for (int c = 0; c < MAX_FCHUNK; ++c) {
-                if (64 * c >= F) break;
-                __syncthreads();
-                scratch[wave * 64 + lane] = accg[c];
-                __syncthreads();
-                if (wave == 0)
-                    for (int w = 1; w < CW; ++w) accg[c] = __fadd_rn(accg[c], scratch[w * 64 + lane]);
-            }
-        }
-        if (wave == 0) {
-#pragma unroll
-            for (int c = 0; c < MAX_FCHUNK; ++c) {
-                const int ch = lane + 64 * c;
-                if (ch < F) p.global.integrated_features[(size_t)g * F + ch] = accg[c];
-            }
-        }
-    }
+    if (defer) return;       // (the global features and the decoder maps are written by the projection kernel)
+    if (p.global.integrated_features) store_channel_sums<CW>(accg, p.global.integrated_features + (size_t)g * F, F, scratch, wave, lane);
     if (p.decoder.groups > 0) {
         // decoder layout: this ray is cell (r / width, r % width) of its group's grid; its channels go to the channels-first
         // map of the group (neighbouring rays = neighbouring workgroups fill neighbouring columns of every plane)
@@ -481,8 +478,8 @@ int launch_composite(const CompositeParams& p, hipStream_t s) {
         for (int i = 0; i < p.decoder.groups; ++i) {
             PR_REQUIRE(p.decoder.rays[i] > 0 && p.decoder.width[i] > 0 && p.decoder.rays[i] % p.decoder.width[i] == 0,
                        "decoder layout: group %d has %d rays in rows of %d", i, p.decoder.rays[i], p.decoder.width[i]);
-            PR_REQUIRE(p.decoder.channel_begin[i] >= 0 && p.decoder.channel_begin[i] < p.decoder.channel_end[i] && p.decoder.channel_end[i] <= p.F,
-                       "decoder layout: group %d channel range [%d, %d) outside 0..%d", i, p.decoder.channel_begin[i], p.decoder.channel_end[i], p.F);
+            PR_REQUIRE(p.decoder.channel_begin[i] >= 0 && p.decoder.channel_begin[i] < p.decoder.channel_end[i] && p.decoder.channel_end[i] <= (p.pooled ? p.out_features : p.F),
+                       "decoder layout: group %d channel range [%d, %d) outside 0..%d", i, p.decoder.channel_begin[i], p.decoder.channel_end[i], p.pooled ? p.out_features : p.F);
             PR_REQUIRE(p.decoder.map[i] != nullptr, "decoder layout: group %d has no map", i);
             sum += p.decoder.rays[i];
         }
@@ -498,6 +495,117 @@ int launch_composite(const CompositeParams& p, hipStream_t s) {
         PR_TRY(prepare_kernel(reinterpret_cast<const void*>(&k_composite<1>), 156 * 1024, nullptr));
         hipLaunchKernelGGL(k_composite<1>, dim3((unsigned)total), dim3(64), lds, s, p);
     }
+    PR_LAUNCH_CHECK();
+    return PR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Deferred projection (PR_FLAG_DEFER_PROJECTION): features_head.6 once per ray, behind the compositing sums.
+//   object k:  integrated_features[ray] = [W6 | b6]_model(k) . pooled[2 k][ray]
+//   global:    integrated_features[ray] = sum_k [W6 | b6]_model(k) . pooled[2 k + 1][ray]      (one accumulator chain, object order)
+// A workgroup owns 64 rays and all output channels: wave w the 32-column blocks w and w + 4 for both 32-row blocks, like the MLP
+// tile.  The pooled rows of one object are staged in LDS (zero-padded to the K step), the packed [W6 | b6 | 0] rows come from L2
+// (100 KB per model, shared by every workgroup), 16 bytes of K per lane and load: lane (r, half) holds k = 8 q + 4 half + e of row /
+// column r, for both operands of v_mfma_f32_32x32x2_f32.  The decoder layout of the global features is emitted here for these calls.
+// ---------------------------------------------------------------------------------------------
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+constexpr int PJ_ROWS = 64;
+constexpr int PJ_KMAX = MAX_WIDTH / 2 + 8;        // projection_k(W / 2) <= this
+constexpr int PJ_LDA = PJ_KMAX + 4;
+
+__global__ __launch_bounds__(256) void k_project_features(CompositeParams p) {
+    __shared__ __attribute__((aligned(16))) float SA[PJ_ROWS * PJ_LDA];
+    const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, half = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const long total = (long)p.frames * p.rays;
+    const long row0 = (long)blockIdx.x * PJ_ROWS;
+    const int HW = p.F, PK = p.proj_k, F = p.out_features;
+    const int nblk = (F + 31) / 32;
+    const int k4 = PK >> 2;
+    const bool want_global = p.global.integrated_features != nullptr || p.decoder.groups > 0;
+    for (int set = 0; set <= p.objects; ++set) {          // the objects' own features, then the global ones
+        const bool global = set == p.objects;
+        float* out = global ? p.global.integrated_features : p.obj[set].out.integrated_features;
+        if (global ? !want_global : out == nullptr) continue;
+        f32x16 acc[2][2];
+#pragma unroll
+        for (int a = 0; a < 2; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
+        const int kfirst = global ? 0 : set, klast = global ? p.objects - 1 : set;
+        for (int k = kfirst; k <= klast; ++k) {
+            const float* A = p.pooled + ((size_t)(2 * k + (global ? 1 : 0)) * total + row0) * HW;
+            __syncthreads();     // the previous product has finished reading the tile
+            for (int idx = tid; idx < PJ_ROWS * k4; idx += 256) {
+                const int row = idx / k4, c = (idx - row * k4) * 4;
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (row0 + row < total && c < HW) v = *reinterpret_cast<const float4*>(A + (size_t)row * HW + c);
+                *reinterpret_cast<float4*>(SA + row * PJ_LDA + c) = v;
+            }
+            __syncthreads();
+            const float* W = p.proj_w[k];
+            const float* a0 = SA + r * PJ_LDA + 4 * half;
+#pragma unroll
+            for (int blk = 0; blk < 2; ++blk) {
+                const int cb = wave + 4 * blk;
+                if (cb >= nblk) continue;
+                const auto* wp = as_global(reinterpret_cast<const f32x4_t*>(W + (size_t)(cb * 32 + r) * PK + 4 * half));
+                for (int q = 0; q < k4; q += 2) {
+                    const f32x4_t w = wp[q];
+                    const float4 x0 = *reinterpret_cast<const float4*>(a0 + 4 * q);
+                    const float4 x1 = *reinterpret_cast<const float4*>(a0 + 32 * PJ_LDA + 4 * q);
+                    acc[blk][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.x, w.x, acc[blk][0], 0, 0, 0);
+                    acc[blk][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.x, w.x, acc[blk][1], 0, 0, 0);
+                    acc[blk][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.y, w.y, acc[blk][0], 0, 0, 0);
+                    acc[blk][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.y, w.y, acc[blk][1], 0, 0, 0);
+                    acc[blk][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.z, w.z, acc[blk][0], 0, 0, 0);
+                    acc[blk][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.z, w.z, acc[blk][1], 0, 0, 0);
+                    acc[blk][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.w, w.w, acc[blk][0], 0, 0, 0);
+                    acc[blk][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.w, w.w, acc[blk][1], 0, 0, 0);
+                }
+            }
+        }
+        // accumulator element i of lane (r, half): tile row (i & 3) + 8 (i >> 2) + 4 half (+ 32 for the second row block), column r
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk) {
+            const int col = (wave + 4 * blk) * 32 + r;
+            if (col >= F) continue;
+#pragma unroll
+            for (int rb = 0; rb < 2; ++rb) {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const long g = row0 + 32 * rb + (i & 3) + 8 * (i >> 2) + 4 * half;
+                    if (g >= total) continue;
+                    const float v = acc[blk][rb][i];
+                    if (out) out[(size_t)g * F + col] = v;
+                    if (global && p.decoder.groups > 0) {
+                        // decoder layout: this ray is cell (r / width, r % width) of its group's grid (see k_composite)
+                        const int frame = (int)(g / p.rays);
+                        int rr = (int)(g - (long)frame * p.rays);
+                        int grp = 0;
+                        while (grp < p.decoder.groups - 1 && rr >= p.decoder.rays[grp]) rr -= p.decoder.rays[grp++];
+                        const int c0 = p.decoder.channel_begin[grp], c1 = p.decoder.channel_end[grp];
+                        const size_t cells = (size_t)p.decoder.rays[grp];
+                        float* map = p.decoder.map[grp] + (size_t)frame * (c1 - c0) * cells + rr;
+                        if (col >= c0 && col < c1) map[(size_t)(col - c0) * cells] = v;
+                    }
+                }
+            }
+        }
+    }
+}
+
+int launch_projection(const CompositeParams& p, hipStream_t s) {
+    PR_REQUIRE(p.pooled != nullptr, "deferred projection without pooled rows");
+    PR_REQUIRE(p.proj_k >= p.F && p.proj_k <= PJ_KMAX && (p.proj_k & 7) == 0 && (p.F & 3) == 0, "deferred projection: row of %d floats, K %d",
+               p.F, p.proj_k);
+    PR_REQUIRE(p.out_features >= 1 && p.out_features <= 256, "deferred projection: output_features %d", p.out_features);
+    for (int k = 0; k < p.objects; ++k) PR_REQUIRE(p.proj_w[k] != nullptr, "deferred projection: object %d has no packed matrix", k);
+    const long total = (long)p.frames * p.rays;
+    ProfileScope scope(1, s);
+    hipLaunchKernelGGL(k_project_features, dim3((unsigned)((total + PJ_ROWS - 1) / PJ_ROWS)), dim3(256), 0, s, p);
     PR_LAUNCH_CHECK();
     return PR_OK;
 }

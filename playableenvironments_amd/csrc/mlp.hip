@@ -154,6 +154,8 @@ int compute_layout(const pr_object_model_t& m, const ModelDims& d, PackedLayout*
         if (i == m.skip_layer_idx) l->n_seg3[i][1] = take2(d.Wpad / 32, d.enc_pad);
     }
     l->h0_3 = take2(d.Wpad / 32, d.Wpad);
+    l->h6p_off = off;
+    off += d.Fpad * projection_k(d.W2);
     l->total = off;
     return PR_OK;
 }
@@ -167,8 +169,9 @@ int compute_layout(const pr_object_model_t& m, const ModelDims& d, PackedLayout*
 struct PackJob {
     const float* src;
     float* dst;
+    const float* src2;   // kind 3: the bias
     int kind;       // 0 = fp32 fragment-ordered matrix segment, 1 = padded vector / raw row copy,
-                    // 2 = fp16 hi/lo split fragments (same byte size as kind 0)
+                    // 2 = fp16 hi/lo split fragments (same byte size as kind 0), 3 = rows [W | b | 0] of length kq
     int in_total;   // row stride of src
     int col_off;
     int k_real, n_real, kq, nblk;
@@ -231,6 +234,7 @@ __global__ __launch_bounds__(256) void k_pack(PackJobs jobs) {
             // rows of length kq (padded) from rows of length k_real; n_real rows
             const int row = idx / j.kq, c = idx % j.kq;
             if (j.src && row < j.n_real && c < j.k_real) v = j.src[(size_t)row * j.in_total + j.col_off + c];
+            if (j.kind == 3 && row < j.n_real && c == j.k_real) v = j.src2[row];
         }
         j.dst[idx] = v;
     }
@@ -367,6 +371,11 @@ static int build_pack_jobs(const pr_object_model_t& m, const ModelDims& d, const
     PR_TRY(add_seg(js, m.head3, 0, d.W, d.Wpad, d.W2pad, base + l.h3_off));
     PR_TRY(add_seg(js, m.head6, 0, d.W2, d.W2pad, d.Fpad, base + l.h6_off));
     PR_TRY(add_vec(js, m.head6.bias, 1, d.F, d.F, d.Fpad, base + l.h6_bias_off));
+    // [W6 | b6] as plain fp32 rows in every packing: the per-ray product of the deferred projection (launch_projection)
+    PR_TRY(add_vec(js, m.head6.weight, d.Fpad, d.W2, d.W2, projection_k(d.W2), base + l.h6p_off));
+    js->job[js->n - 1].kind = 3;
+    js->job[js->n - 1].n_real = d.F;
+    js->job[js->n - 1].src2 = m.head6.bias;
     if (js->seg_kind != 0) return PR_OK;      // the backward pass runs on the fp32 packing only
     if (m.has_bender) {
         for (int j = 1; j < m.bender_count; ++j)
@@ -522,7 +531,7 @@ int launch_adain_fold_group(const FoldParams* jobs, int count, hipStream_t s) {
 // The three feature-head layers on the 64 rows in X whose destinations are in S.dest, then the write-out.
 __device__ __forceinline__ void head_on_tile(Smem& S, const MlpParams& p, EncRegs& enc, int valid_rows) {
     for (int l = p.n_backbone; l < p.n_layers; ++l) run_layer(p.layers[l], S, p, 0, 0, enc);
-    write_rows_indirect(S, p.feat, p.F, p.F);
+    write_rows_indirect(S, p.feat, p.F, p.F, p.ones_col);
     if (threadIdx.x == 0 && p.head_count) atomicAdd(p.head_count, valid_rows);
     __syncthreads();   // the next prologue overwrites flags / X
 }
@@ -841,12 +850,20 @@ __device__ __forceinline__ void mlp_tile_loop(const MlpParams& p) {
             __syncthreads();   // S.next_tile is published; the next tile's prologue overwrites flags / X
         } else if (!TRAIN && p.gate) {
             __syncthreads();   // the liveness bits are complete
+            if (!(p.empty_alpha <= 0.f)) {
+                // a sample that left the box in the ray bender keeps the density empty_alpha: with a positive one it is composited,
+                // with the zero feature row the ungated kernel writes for it (never live: its density is not the network's)
+                for (int idx = tid; idx < TILE_M * p.F; idx += MLP_THREADS) {
+                    const int row = idx / p.F;
+                    if ((S.flags[row] & 3) == 1) p.feat[(size_t)(tile_base + row) * p.F + (idx - row * p.F)] = 0.f;
+                }
+            }
             pending = gated_head(S, p, tile_base, pending, enc);
             PR_PHASE(8);
         } else if (!TRAIN) {
             for (int l = p.n_backbone; l < p.n_layers; ++l) run_layer(p.layers[l], S, p, tile_base, 0, enc);
             PR_PHASE(15);
-            write_tile_rows(S, p.feat, p.F, p.F, tile_base, /*zero_dead=*/true);
+            write_tile_rows(S, p.feat, p.F, p.F, tile_base, /*zero_dead=*/true, p.ones_col);
             __syncthreads();   // the next tile's prologue overwrites flags / X
             PR_PHASE(8);
         } else {

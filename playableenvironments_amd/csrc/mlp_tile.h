@@ -831,9 +831,24 @@ __device__ __forceinline__ void row_dots(const Smem& S, int s, W w, int width, i
     }
 }
 
+// Deferred projection: the chunk at columns c .. c + 3 of a hidden row [h | 1 | 0 ..] - column `ones_col` carries the bias of the
+// projected layer, what lies behind it is padding (X holds older activations there).
+template <class V>
+__device__ __forceinline__ V homogeneous_chunk(V v, int c, int ones_col) {
+    if (c + 3 >= ones_col) {
+        v.x = c < ones_col ? v.x : (c == ones_col ? 1.0f : 0.f);
+        v.y = c + 1 < ones_col ? v.y : (c + 1 == ones_col ? 1.0f : 0.f);
+        v.z = c + 2 < ones_col ? v.z : (c + 2 == ones_col ? 1.0f : 0.f);
+        v.w = c + 3 < ones_col ? v.w : (c + 3 == ones_col ? 1.0f : 0.f);
+    }
+    return v;
+}
+
 // Tile rows staged in X -> HBM with coalesced 16-byte stores (width % 4 == 0) or scalar stores.
 // zero_dead: rows that failed the second AABB test are written as zeros (feature rows).
-__device__ __forceinline__ void write_tile_rows(const Smem& S, float* dst, int width, int stride, int tile_base, bool zero_dead) {
+// ones_col > 0: hidden rows of the deferred projection (homogeneous_chunk; width % 4 == 0).
+__device__ __forceinline__ void write_tile_rows(const Smem& S, float* dst, int width, int stride, int tile_base, bool zero_dead,
+                                                int ones_col = 0) {
     const int tid = threadIdx.x;
     const float* src = S.X;
     const int ld = LDX;
@@ -869,6 +884,7 @@ __device__ __forceinline__ void write_tile_rows(const Smem& S, float* dst, int w
 #pragma unroll
             for (int q = 0; q < BATCH; ++q) {
                 if (fl[q] & 1) {
+                    if (ones_col) v[q] = homogeneous_chunk(v[q], c[q], ones_col);
                     if (zero_dead && !(fl[q] & 2)) v[q] = f32x4_nt{0.f, 0.f, 0.f, 0.f};
                     // streamed once, read next by another kernel: keep the rows from evicting the weight fragments in L2
                     __builtin_nontemporal_store(v[q], reinterpret_cast<f32x4_nt*>(dst + (size_t)(tile_base + row[q]) * stride + c[q]));
@@ -885,7 +901,7 @@ __device__ __forceinline__ void write_tile_rows(const Smem& S, float* dst, int w
 }
 
 // Feature rows staged in X -> HBM rows S.dest[row] (rows with dest < 0 are skipped); see write_tile_rows.
-__device__ __forceinline__ void write_rows_indirect(const Smem& S, float* dst, int width, int stride) {
+__device__ __forceinline__ void write_rows_indirect(const Smem& S, float* dst, int width, int stride, int ones_col = 0) {
     const int tid = threadIdx.x;
     if ((width & 3) == 0 && (stride & 3) == 0) {
         const int w4 = width >> 2;
@@ -896,6 +912,7 @@ __device__ __forceinline__ void write_rows_indirect(const Smem& S, float* dst, i
                 const float4 v = *reinterpret_cast<const float4*>(S.X + row * LDX + c);
                 typedef float f32x4_nt __attribute__((ext_vector_type(4)));
                 f32x4_nt nt = {v.x, v.y, v.z, v.w};
+                if (ones_col) nt = homogeneous_chunk(nt, c, ones_col);
                 __builtin_nontemporal_store(nt, reinterpret_cast<f32x4_nt*>(dst + (size_t)d * stride + c));
             }
         }

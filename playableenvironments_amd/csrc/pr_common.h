@@ -124,6 +124,7 @@ struct PackedLayout {
     int n_bias_off[PR_MAX_LAYERS];
     int sigma_off;                     // raw copy (Wpad) + bias at [Wpad]
     int h0_off, h3_off, h6_off, h6_bias_off;
+    int h6p_off;                       // [W6 | b6 | 0] rows, (Fpad, projection_k(W2)): the per-ray product of the deferred projection
     // backward pass (fp32 packing only): W^T as fragment-ordered segments, out[m][n] = sum_k G[m][k] W[k][col_off + n]
     int t_b_act[PR_MAX_LAYERS], t_b_skip, t_b_first;   // bender chain: W_l[:, :BW]^T (l >= 1), W_skip[:, BW:]^T, W_0^T
     int t_n_act[PR_MAX_LAYERS], t_n_skip, t_n_first;   // NeRF backbone chain
@@ -149,6 +150,11 @@ struct ModelDims {
     int bin, bin_pad; // bender input = benc + D
     int BW, BWpad;
 };
+
+// Deferred projection (PR_FLAG_DEFER_PROJECTION): a feature row is [h (W2) | 1 | 0 ..], hidden_row_floats wide; the packed
+// [W6 | b6] rows are padded to the K step of the projection kernel (8).
+__host__ __device__ static inline int hidden_row_floats(int W2) { return round_up(W2 + 1, 4); }
+__host__ __device__ static inline int projection_k(int W2) { return round_up(W2 + 1, 8); }
 
 int compute_dims(const pr_object_model_t& m, ModelDims* d);
 int compute_layout(const pr_object_model_t& m, const ModelDims& d, PackedLayout* l);
@@ -193,7 +199,8 @@ struct MlpParams {
     int W, Wpad;
     const float* adain;          // table base for this object; row = frame
     int adain_stride;            // floats between frames
-    int F;
+    int F;                       // floats of a feature row (deferred projection: hidden_row_floats(W / 2))
+    int ones_col;                // deferred projection: column W / 2 of a row is 1 (0 on zeroed rows), the ones behind it 0; 0 = off
     // train-mode BatchNorm (batch statistics sit between the head matmuls -> three phases, see mlp.hip)
     int phase;                   // 0 = eval (everything fused); 1 = ... -> raw h1; 2 = h1 -> raw h2; 3 = h2 -> features
     float* h_out;                // phase 1/2: raw (pre-BN) head activations, (cap, h_out_width)
@@ -466,8 +473,15 @@ struct CompositeParams {
     CompositeObject obj[PR_MAX_OBJECTS];
     pr_entry_t global;
     pr_decoder_layout_t decoder;   // global features additionally as channels-first maps per ray group (groups = 0: off)
+    // deferred projection: F is the width of a hidden row, the weighted row sums are kept per object - pooled[(2 k + j)] is the
+    // (frames * rays, F) block of object k under its own (j = 0) or the global (j = 1) weights - and launch_projection finishes
+    float* pooled;                 // NULL: off
+    int out_features;              // deferred projection: the real F of the models
+    const float* proj_w[PR_MAX_OBJECTS];   // deferred projection: packed [W6 | b6] rows of object k's model, row stride proj_k
+    int proj_k;
 };
 int launch_composite(const CompositeParams& p, hipStream_t s);
+int launch_projection(const CompositeParams& p, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // Workspace plan of one call (render.hip); pr_render_backward recomputes it from the same call
@@ -498,6 +512,7 @@ struct Plan {
     size_t block_sums, block_offsets;
     size_t rec_pos, rec_flat;
     size_t pend_act, pend_meta;   // pending stacks of the sigma-gated head (gate_active calls only)
+    size_t pooled;                // pooled hidden rows of the deferred projection (defer_active calls only)
     // train-mode BatchNorm scratch (shared by all objects, they are processed one after the other)
     size_t h1, h2, row_flags, stats, stat_count, batch_stats;
     size_t div_t0, div_ta, div_tb;   // divergence tangent scratch
@@ -515,6 +530,7 @@ int validate_occupancy(const pr_call_t& c, const pr_object_t* objs, const pr_occ
 bool group_active(const pr_call_t& c);
 bool group_train_active(const pr_call_t& c);
 bool gate_active(const pr_call_t& c);
+bool defer_active(const pr_call_t& c, const pr_object_t* objs);
 bool group_active(const pr_call_t& c);
 int make_plan(const pr_call_t& c, const pr_object_t* objs, Plan* plan);
 void bbox_split(const pr_object_model_t& m, float* lo, float* hi, float* size);

@@ -158,6 +158,22 @@ bool gate_active(const pr_call_t& c) {
     return !c.noise_coarse.integrate_global && !c.noise_fine.integrate_global;
 }
 
+// The deferred projection (features_head.6 applied per ray, behind the compositing sums) needs the projected layer to be linear in
+// the composited rows and the fused fp32 evaluation kernels: no sigmoid between the layer and the sum, no phased (training /
+// differentiable) launches, not the scalar debugging kernel, not the split-precision tiers (their kernels write full rows).  Every
+// object model has the three-layer head (pr_object_model_t holds no other); the pooled rows of a ray have one width, so the models
+// of the call share layers_width.  Noise changes the weights only: perturbed calls are eligible.
+bool defer_active(const pr_call_t& c, const pr_object_t* objs) {
+    if (!(c.flags & PR_FLAG_DEFER_PROJECTION)) return false;
+    if (c.flags & (PR_FLAG_SAVE_FOR_BACKWARD | PR_FLAG_TRAIN_BN | PR_FLAG_SIGMOID_FEATURES | PR_FLAG_NAIVE_MLP)) return false;
+    if (c.precision != PR_PRECISION_FP32) return false;
+    for (int k = 0; k < c.objects; ++k) {
+        if (objs[k].coarse.layers_width != objs[0].coarse.layers_width) return false;
+        if (c.use_fine && objs[k].fine.layers_width != objs[0].coarse.layers_width) return false;
+    }
+    return true;
+}
+
 int make_plan(const pr_call_t& c, const pr_object_t* objs, Plan* plan) {
     memset(plan, 0, sizeof(*plan));
     size_t off = 0;
@@ -201,7 +217,7 @@ int make_plan(const pr_call_t& c, const pr_object_t* objs, Plan* plan) {
             tp.dispmag[k] = m.has_bender ? take(sizeof(float) * cap) : (size_t)-1;
             tp.adain[k] = take(sizeof(float) * (size_t)c.frames * adain_row_floats(d));
             tp.feat[k] = feat_bytes[t];  // relative to the feature arena
-            feat_bytes[t] += align_up(sizeof(float) * cap * m.output_features);
+            feat_bytes[t] += align_up(sizeof(float) * cap * (defer_active(c, objs) ? hidden_row_floats(d.W2) : m.output_features));
             if (c.flags & PR_FLAG_SAVE_FOR_BACKWARD) {
                 // everything the backward pass re-reads, per object instance (compact rows, worst-case capacity)
                 SavedPlan& sv = tp.saved[k];
@@ -241,6 +257,11 @@ int make_plan(const pr_call_t& c, const pr_object_t* objs, Plan* plan) {
     if (gate_active(c)) {   // per-workgroup stacks of pending live rows (sigma-gated head)
         plan->pend_act = take(sizeof(float) * (size_t)MAX_RESIDENT_TILES * TILE_M * MAX_WIDTH);
         plan->pend_meta = take(sizeof(int32_t) * (size_t)MAX_RESIDENT_TILES * TILE_M * 2);
+    }
+    if (defer_active(c, objs)) {   // per object the row sums under its own and under the global weights (shared by the model types)
+        ModelDims d0;
+        PR_TRY(compute_dims(objs[0].coarse, &d0));
+        plan->pooled = take(sizeof(float) * 2 * (size_t)c.objects * nr * hidden_row_floats(d0.W2));
     }
     if (c.flags & (PR_FLAG_TRAIN_BN | PR_FLAG_SAVE_FOR_BACKWARD)) {   // the phased launch structure (see render())
         plan->h1 = take(sizeof(float) * max_cap * MAX_WIDTH);
@@ -303,6 +324,7 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
     int32_t* rec_flat = reinterpret_cast<int32_t*>(ws + plan.rec_flat);
     const bool naive = (c.flags & PR_FLAG_NAIVE_MLP) != 0;
     const bool gate = gate_active(c);
+    const bool defer = defer_active(c, objs);
     const bool grouped = group_active(c);
     MlpParams jobs[PR_MAX_OBJECTS];
     int job_rows[PR_MAX_OBJECTS];
@@ -512,6 +534,11 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
             mp.deformation_stride = K * m.deformation_features;
             mp.adain = adain; mp.adain_stride = fo.row_floats;
             mp.sigma = sigma; mp.dispmag = dispmag; mp.feat = feat;
+            if (defer) {     // the kernels stop behind features_head.4 and write [h | 1] rows
+                mp.n_layers = mp.n_backbone + 2;
+                mp.F = hidden_row_floats(d.W2);
+                mp.ones_col = d.W2;
+            }
             if (gate) {
                 mp.gate = 1;
                 mp.pend_act = reinterpret_cast<float*>(ws + plan.pend_act);
@@ -683,6 +710,14 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
         for (int k = 0; k < K; ++k) {
             const pr_object_model_t& m = t ? objs[k].fine : objs[k].coarse;
             PR_REQUIRE(m.output_features == cp.F, "all objects must share output_features");
+            if (defer) {
+                ModelDims d;
+                PackedLayout l;
+                PR_TRY(compute_dims(m, &d));
+                PR_TRY(compute_layout(m, d, &l));
+                cp.proj_w[k] = static_cast<const float*>(t ? objs[k].packed_fine : objs[k].packed_coarse) + l.h6p_off;
+                cp.proj_k = projection_k(d.W2);
+            }
             CompositeObject& o = cp.obj[k];
             o.t = reinterpret_cast<const float*>(ws + tp.t[k]);
             o.sigma = reinterpret_cast<const float*>(ws + tp.sigma[k]);
@@ -700,7 +735,13 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
             cp.global = out->global;
             cp.decoder = out->decoder;
         }
+        if (defer) {
+            cp.out_features = cp.F;
+            cp.F = hidden_row_floats(objs[0].coarse.layers_width / 2);
+            cp.pooled = reinterpret_cast<float*>(ws + plan.pooled);
+        }
         PR_TRY(launch_composite(cp, s));
+        if (defer) PR_TRY(launch_projection(cp, s));
 
         // ---- optional exports -------------------------------------------------------------------
         if (out) {

@@ -165,14 +165,14 @@ class FrameGraph:
 
     def _signature(self):
         """Everything the captured launches baked in besides the input buffers: parameter storages and values, the
-        arithmetic precision (selects the kernel and the packed layout), the sigma gate, the annealing step of the ray benders
+        arithmetic precision (selects the kernel and the packed layout), the sigma gate, the deferred projection, the annealing step of the ray benders
         (their octave weights are kernel arguments) and the occupancy grid (its bit pointers are kernel arguments; with ``follow``
         the recording also holds the grid's build launches)."""
         composer = self.model.object_composer
         # state_epoch counts set_step / load_state_dict / .to() calls (reading the step buffers back would synchronise)
         owner = composer if self.mode == "scene_encodings" else self.model       # (observations: the encoders' weights too)
         return (tuple((p.data_ptr(), p._version) for p in owner.parameters()), composer.precision,
-                bool(composer.gate_feature_head), composer.state_epoch, composer.weights_epoch,
+                bool(composer.gate_feature_head), bool(composer.defer_feature_projection), composer.state_epoch, composer.weights_epoch,
                 None if composer.object_entry_fields is None else tuple(composer.object_entry_fields),
                 None if composer.occupancy is None else composer.occupancy.signature())
 

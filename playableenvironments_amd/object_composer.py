@@ -432,6 +432,11 @@ class ObjectComposer(Tracked, nn.Module):
         #: is <= 0 - their compositing weight is exactly 0, so the results are bit-identical.  Ignored (by the library) for
         #: perturbed, training and differentiable calls.
         self.gate_feature_head = True
+        #: deferred projection (PR_FLAG_DEFER_PROJECTION): evaluation renders composite the hidden rows behind features_head.4 and
+        #: apply features_head.6 once per ray instead of once per sample.  ``integrated_features`` / ``decoder_features`` differ from
+        #: the per-sample path by fp32 re-association, every other field is bit-identical.  Ignored (by the library) for training
+        #: and differentiable calls, the f16x3 / f16 tiers, ``apply_activation`` and the scalar debugging kernel.
+        self.defer_feature_projection = True
         #: device tensors (K,) per model type: samples that entered the BatchNorm batch statistics of the last training call
         self.last_normalised_samples: Dict[str, torch.Tensor] = {}
         #: where the random draws of perturbed / training calls come from when no explicit ``_noise`` is replayed:
@@ -1174,6 +1179,8 @@ class ObjectComposer(Tracked, nn.Module):
                                   "training.", UserWarning, stacklevel=2)
         if self.gate_feature_head:
             flags |= _lib.PR_FLAG_GATE_HEAD      # honoured by the library for unperturbed evaluation calls only
+        if self.defer_feature_projection:
+            flags |= _lib.PR_FLAG_DEFER_PROJECTION      # honoured by the library for fp32 evaluation calls without a sigmoid only
 
         # ---- noise -----------------------------------------------------------------------------
         types = ["coarse"] + (["fine"] if use_fine else [])
