@@ -321,6 +321,52 @@ int pr_render_forward_culled(const pr_call_t* call, const pr_object_t* objects, 
                              void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Retained per-sample state, for evaluation frames on a camera that stands still.  The per-sample state of an object - t, sigma,
+ * slot, dispmag and the compact feature rows of both levels - is a function of the camera rays, the object's own w2o / style /
+ * deformation / presence rows, its weights and BatchNorm running statistics and its occupancy bits, and of nothing else; the
+ * compositing kernel only reads it.  With a pr_retained_t the arrays of the objects in object_mask live in `cache` instead of the
+ * workspace, next to a copy of everything they depend on.  The first launch of the call compares those copies with the call's inputs
+ * BITWISE (32-bit words: a NaN equals the same NaN) on the device; an object whose key, the camera key and the host digest all match
+ * skips placement, compaction, resampling and the MLP (its jobs return at once, its row count is forced to 0) and only compositing
+ * reads its cached arrays - the result is bit for bit what the call would have recomputed.  Every other retained object is rendered
+ * by the same kernels as without retention, writing into the cache, and the last launches of the call store its key.  An object
+ * that is not reused is marked invalid before anything overwrites its arrays.  No host read-back: a call recorded into a HIP graph
+ * holds both outcomes.  Every fill and flag write is a kernel (no memset node).
+ *
+ * What the device cannot see is the caller's: host_key must change whenever the VALUES of the retained objects' packed weights
+ * change.  The library adds a digest of what it sees on the host (honoured flags, precision, N, R, K, use_fine, positions, the scalar
+ * fields of the models incl. box, depth range and octave weights, occupancy cell counts, object_mask); another digest: nothing reused.
+ *
+ * Cache layout (private; every region 256-byte aligned; pr_retained_size is their sum): a 256-byte header; ray_origins (N,3) and
+ * ray_directions (N,R,3); per retained object w2o (N,12), presence (N words), style (N,S), deformation (N,D); per level bn1 mean /
+ * var (W), bn4 mean / var (W/2) and - unless the model is a skybox - N x 8192 words of occupancy bits (a grid on a retained object
+ * may have at most 64^3 = 262144 cells); per level t, sigma, slot (N R P_k words each), dispmag (the same, models with a bender) and
+ * the feature rows (N R P_k rows of output_features floats, or of W/2 + 1 rounded up to 4 when the deferred projection is active).
+ * pr_workspace_size is unchanged: the workspace regions of retained objects go unused.
+ *
+ * evaluated_samples / head_samples report THIS call's MLP work: 0 for a reused object.  Refused (PR_ERR_INVALID, before any device
+ * work): PR_FLAG_PERTURB or an integrate-noise pointer, PR_FLAG_TRAIN_BN, PR_FLAG_SAVE_FOR_BACKWARD, PR_FLAG_NAIVE_MLP, a mask bit
+ * at or beyond `objects`, a misaligned or too small cache, a sample_delta export of a retained object (the dense displacement is not
+ * cached).
+ */
+typedef struct pr_retained_t {
+    uint32_t object_mask;   /* bit k: object k of the call is retained */
+    uint32_t reserved_;
+    uint64_t host_key;      /* caller's epoch of what the device cannot see: packed weight values of the retained objects' models */
+    void*    cache;         /* device, 256-byte aligned, pr_retained_size bytes, owned by the caller, untouched between calls */
+    size_t   cache_bytes;
+    int32_t* reused;        /* out (K) device or NULL: 1 = the object's cached state was used by this call, 0 = it was rendered */
+} pr_retained_t;
+/* Bytes of the cache for this call and mask (host computation, no device work). */
+int pr_retained_size(const pr_call_t* call, const pr_object_t* objects, uint32_t object_mask, size_t* bytes);
+/* Marks a cache invalid: one kernel launch on `stream`.  Required once before the first use. */
+int pr_retained_reset(void* cache, size_t cache_bytes, void* stream);
+/* pr_render_forward_culled with retention (retained == NULL: exactly pr_render_forward_culled; occupancy may be NULL). */
+int pr_render_forward_retained(const pr_call_t* call, const pr_object_t* objects, const pr_occupancy_t* occupancy,
+                               const pr_retained_t* retained, const pr_outputs_t* coarse, const pr_outputs_t* fine,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Builds occupancy bits from a density lattice: sigma (groups, cells[0] * s, cells[1] * s, cells[2] * s) with supersample factor
  * s >= 1.  A cell is occupied iff any of its s^3 lattice values is > threshold; the occupied set is then grown by `dilate` >= 0
  * cells over the full (2 dilate + 1)^3 neighbourhood, clipped at the box.  bits (groups, ceil(cells[0] * cells[1] * cells[2] / 32)):

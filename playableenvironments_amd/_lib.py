@@ -165,6 +165,12 @@ class Occupancy(C.Structure):
     _fields_ = [("coarse", OccupancyGrid * PR_MAX_OBJECTS), ("fine", OccupancyGrid * PR_MAX_OBJECTS)]
 
 
+class Retained(C.Structure):
+    """pr_retained_t (include/playrender.h)."""
+    _fields_ = [("object_mask", C.c_uint32), ("reserved_", C.c_uint32), ("host_key", C.c_uint64), ("cache", C.c_void_p),
+                ("cache_bytes", C.c_size_t), ("reused", C.c_void_p)]
+
+
 # every exported symbol of include/playrender.h : (restype, argtypes)
 class SceneSetup(C.Structure):
     """pr_scene_setup_t (include/playrender.h)."""
@@ -189,6 +195,10 @@ SYMBOLS = {
                                     C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_render_forward_culled": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(Occupancy), C.POINTER(Outputs), C.POINTER(Outputs),
                                            C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pr_retained_size": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.c_uint32, C.POINTER(C.c_size_t)]),
+    "pr_retained_reset": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pr_render_forward_retained": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(Occupancy), C.POINTER(Retained),
+                                             C.POINTER(Outputs), C.POINTER(Outputs), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_occupancy_build": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p]),
     "pr_backward_workspace_size": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(C.c_size_t)]),
     "pr_render_backward": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(OutputGrads), C.POINTER(OutputGrads),

@@ -147,6 +147,7 @@ struct RayLanes {
 
 __device__ __forceinline__ void place_coarse_body(const PlaceParams& p) {
     __shared__ int lds[4];
+    if (p.skip && *p.skip) return;     // (wave-uniform: the object's retained arrays are reused)
     const int lane = threadIdx.x & 63;
     const long g = (long)blockIdx.x * 256 + threadIdx.x;
     const long total = (long)p.frames * p.rays;
@@ -260,6 +261,7 @@ int launch_scan(const int32_t* sums, int32_t* offsets, int32_t* total, int n, hi
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ void fill_body(const FillParams& p) {
     __shared__ int lds[4];
+    if (p.skip && *p.skip) return;     // (wave-uniform: the object's retained arrays are reused)
     const int lane = threadIdx.x & 63;
     const long g = (long)blockIdx.x * 256 + threadIdx.x;
     const long total = (long)p.frames * p.rays;
@@ -389,6 +391,7 @@ __device__ __forceinline__ void bitonic_sort_f32(float* key, int n /*pow2*/, int
 
 __global__ __launch_bounds__(64) void k_resample(ResampleParams p, int sort_size) {
     extern __shared__ float sm[];
+    if (p.skip && *p.skip) return;     // (uniform over the workgroup: the object's retained arrays are reused)
     const int Pc = p.pc, Pf = p.pf;
     float* tc = sm;             // [Pc]
     float* al = tc + Pc;        // [Pc] alpha, then weights

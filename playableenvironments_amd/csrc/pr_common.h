@@ -330,6 +330,7 @@ struct PlaceParams {
     float* dispmag;               // (N,R,P) out zeros or NULL
     int32_t* block_sums;          // (ceil(N*R/256)) in-box counts per block of 256 rays
     OccGrid occ;                  // empty-space skipping (evaluation calls), or bits == NULL
+    const int32_t* skip;          // device flag or NULL: != 0 = the object's cached state is reused, the job returns at once (retain.hip)
 };
 int launch_place_coarse(const PlaceParams& p, hipStream_t s);
 
@@ -346,6 +347,7 @@ struct FillParams {
     int32_t* rec_flat;            // (cap)
     int32_t* slot;                // (N,R,P) compact row or -1
     OccGrid occ;
+    const int32_t* skip;          // as PlaceParams::skip
 };
 int launch_fill(const FillParams& p, hipStream_t s);
 int launch_placement_group(const PlaceParams* pp, const FillParams* fp, int32_t* const* totals, int count, hipStream_t s);
@@ -372,6 +374,7 @@ struct ResampleParams {
     float* dispmag_fine;          // or NULL
     int32_t* block_sums;
     OccGrid occ;                  // grid of the FINE model: culls the merged coarse + resampled positions
+    const int32_t* skip;          // as PlaceParams::skip
 };
 int launch_resample(const ResampleParams& p, hipStream_t s);
 
@@ -520,6 +523,46 @@ struct Plan {
     size_t bytes;
     int nblocks256;
 };
+// ---------------------------------------------------------------------------------------------
+// Retained per-sample state (pr_render_forward_retained, retain.hip): the arrays of the chosen objects live in a caller-owned
+// cache next to a copy of everything they are a function of; the device decides per call whether an object's arrays are reused.
+// ---------------------------------------------------------------------------------------------
+constexpr int RETAIN_OCC_WORDS = 8192;      // occupancy key capacity per frame and level (64^3 cells)
+struct RetainHeader {                        // first 256 bytes of the cache
+    uint32_t valid;                          // 1: the camera key and the digest describe a committed frame
+    uint32_t digest[2];
+    uint32_t pad_;
+    uint32_t obj_valid[PR_MAX_OBJECTS];      // 1: object k's key and arrays describe a committed frame
+    int32_t reuse[PR_MAX_OBJECTS];           // this call's decision: what PlaceParams::skip & co point at
+    uint32_t mismatch[PR_MAX_OBJECTS + 1];   // scratch of the probe: [0] camera, [1 + k] object k; zero between calls
+};
+struct RetainObjectPlan {
+    size_t w2o, presence, style, deformation;
+    size_t bn[2][4];                         // [level][bn1 mean, bn1 var, bn4 mean, bn4 var]
+    size_t occ[2];                           // (N, RETAIN_OCC_WORDS) per level; (size_t)-1 for a skybox model
+    size_t t[2], sigma[2], slot[2], dispmag[2], feat[2];
+};
+struct RetainPlan {
+    size_t origins, directions;
+    RetainObjectPlan obj[PR_MAX_OBJECTS];
+    size_t bytes;
+};
+struct RetainCtx {                           // one call's view of the cache (host)
+    RetainPlan plan;
+    char* base;
+    RetainHeader* hdr;
+    uint32_t mask;
+    uint64_t digest;
+    int32_t* reused;
+    const pr_occupancy_t* occupancy;
+};
+int make_retain_plan(const pr_call_t& c, const pr_object_t* objs, uint32_t mask, RetainPlan* plan);
+int validate_retained(const pr_call_t& c, const pr_object_t* objs, const pr_occupancy_t* occ, const pr_retained_t* r,
+                      const pr_outputs_t* coarse, const pr_outputs_t* fine, RetainCtx* ctx);
+int launch_retain_probe(const pr_call_t& c, const pr_object_t* objs, const RetainCtx& rc, hipStream_t s);
+int launch_retain_gate(const RetainCtx& rc, int32_t* totals, int first, int count, hipStream_t s);
+int launch_retain_commit(const pr_call_t& c, const pr_object_t* objs, const RetainCtx& rc, hipStream_t s);
+
 // Once per (kernel, device): raises the kernel's dynamic LDS limit on the CURRENT device; *cu_count (optional) receives
 // that device's number of compute units.  Function attributes are per device: a process may drive several.
 int prepare_kernel(const void* kernel, int lds_bytes, int* cu_count);

@@ -309,10 +309,34 @@ void bbox_split(const pr_object_model_t& m, float* lo, float* hi, float* size) {
     }
 }
 
-static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupancy_t* occupancy, const pr_outputs_t* outs[2], char* ws,
-                  const Plan& plan, hipStream_t s) {
+// The per-sample arrays of object k at level t: in the workspace, or - a retained object - in the caller's cache.
+struct SampleArrays { float* t; float* sigma; int32_t* slot; float* dispmag; float* feat; };
+static SampleArrays sample_arrays(const Plan& plan, char* ws, const RetainCtx* rc, int t, int k, bool has_bender) {
+    SampleArrays a;
+    if (rc && ((rc->mask >> k) & 1u)) {
+        const RetainObjectPlan& o = rc->plan.obj[k];
+        a.t = reinterpret_cast<float*>(rc->base + o.t[t]);
+        a.sigma = reinterpret_cast<float*>(rc->base + o.sigma[t]);
+        a.slot = reinterpret_cast<int32_t*>(rc->base + o.slot[t]);
+        a.dispmag = has_bender ? reinterpret_cast<float*>(rc->base + o.dispmag[t]) : nullptr;
+        a.feat = reinterpret_cast<float*>(rc->base + o.feat[t]);
+        return a;
+    }
+    const TypePlan& tp = plan.type[t];
+    a.t = reinterpret_cast<float*>(ws + tp.t[k]);
+    a.sigma = reinterpret_cast<float*>(ws + tp.sigma[k]);
+    a.slot = reinterpret_cast<int32_t*>(ws + tp.slot[k]);
+    a.dispmag = has_bender ? reinterpret_cast<float*>(ws + tp.dispmag[k]) : nullptr;
+    a.feat = reinterpret_cast<float*>(ws + tp.feat[k]);
+    return a;
+}
+
+static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupancy_t* occupancy, const RetainCtx* rc,
+                  const pr_outputs_t* outs[2], char* ws, const Plan& plan, hipStream_t s) {
     const int ntypes = c.use_fine ? 2 : 1;
     const int K = c.objects;
+    // retention: the first launches compare the cached keys with this call's inputs and set the reuse flags
+    if (rc) PR_TRY(launch_retain_probe(c, objs, *rc, s));
     int32_t* block_sums_all = reinterpret_cast<int32_t*>(ws + plan.block_sums);
     int32_t* block_offsets_all = reinterpret_cast<int32_t*>(ws + plan.block_offsets);
     // coarse placement / block scan / compaction of several objects: three launches for all of them
@@ -434,11 +458,14 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
             int32_t* block_sums = block_sums_all + (size_t)k * plan.nblocks256;
             int32_t* block_offsets = block_offsets_all + (size_t)k * plan.nblocks256;
             const bool placed = place_grouped && t == 0;     // pass 0 has placed and compacted this object
-            float* t_arr = reinterpret_cast<float*>(ws + tp.t[k]);
-            float* sigma = reinterpret_cast<float*>(ws + tp.sigma[k]);
-            int32_t* slot = reinterpret_cast<int32_t*>(ws + tp.slot[k]);
-            float* dispmag = m.has_bender ? reinterpret_cast<float*>(ws + tp.dispmag[k]) : nullptr;
-            float* feat = reinterpret_cast<float*>(ws + tp.feat[k]);
+            const SampleArrays arr = sample_arrays(plan, ws, rc, t, k, m.has_bender != 0);
+            float* t_arr = arr.t;
+            float* sigma = arr.sigma;
+            int32_t* slot = arr.slot;
+            float* dispmag = arr.dispmag;
+            float* feat = arr.feat;
+            // a retained object's jobs return at once when its cached state is reused (NULL: never)
+            const int32_t* skip = (rc && ((rc->mask >> k) & 1u)) ? &rc->hdr->reuse[k] : nullptr;
             float* adain = reinterpret_cast<float*>(ws + tp.adain[k]);
             const bool save = (c.flags & PR_FLAG_SAVE_FOR_BACKWARD) != 0;
             const SavedPlan& sv = tp.saved[k];
@@ -467,10 +494,10 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
                 pp.jitter = perturb_noise(c.noise_coarse.jitter[k], c, NOISE_JITTER, 0, k);
                 pp.t = t_arr; pp.sigma = sigma; pp.dispmag = dispmag; pp.block_sums = block_sums;
                 pp.occ = occ;
+                pp.skip = skip;
                 if (pass == 0) place_jobs[k] = pp;
                 else if (!placed) PR_TRY(launch_place_coarse(pp, s));
             } else {
-                const TypePlan& cp = plan.type[0];
                 ResampleParams rp;
                 memset(&rp, 0, sizeof(rp));
                 rp.frames = c.frames; rp.rays = c.rays; rp.objects = K; rp.object_index = k;
@@ -479,13 +506,15 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
                 rp.in_scene = c.object_in_scene;
                 bbox_split(m, rp.lo, rp.hi, nullptr);
                 rp.empty_alpha = m.empty_space_alpha;
-                rp.t_coarse = reinterpret_cast<const float*>(ws + cp.t[k]);
-                rp.sigma_coarse = reinterpret_cast<const float*>(ws + cp.sigma[k]);
+                const SampleArrays coarse_arr = sample_arrays(plan, ws, rc, 0, k, objs[k].coarse.has_bender != 0);
+                rp.t_coarse = coarse_arr.t;
+                rp.sigma_coarse = coarse_arr.sigma;
                 rp.alpha_noise = perturb_noise(c.noise_coarse.alpha[k], c, NOISE_ALPHA, 0, k);
                 rp.u_fixed = c.linspace_fine[k];
                 rp.u_random = perturb_noise(c.noise_coarse.pdf[k], c, NOISE_PDF, 0, k);
                 rp.t_fine = t_arr; rp.sigma_fine = sigma; rp.dispmag_fine = dispmag; rp.block_sums = block_sums;
                 rp.occ = occ;
+                rp.skip = skip;
                 PR_TRY(launch_resample(rp, s));
             }
             if (pass == 1 && !placed) PR_TRY(launch_scan(block_sums, block_offsets, totals + k, plan.nblocks256, s));
@@ -499,6 +528,7 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
             bbox_split(m, fp.lo, fp.hi, nullptr);
             fp.t = t_arr; fp.block_offsets = block_offsets; fp.rec_pos = rec_pos; fp.rec_flat = rec_flat; fp.slot = slot;
             fp.occ = occ;
+            fp.skip = skip;
             if (pass == 0) {
                 fill_jobs[k] = fp;
                 total_ptrs[k] = totals + k;
@@ -559,6 +589,7 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
                     job_rows[k] = max_tiles;
                     continue;
                 }
+                if (rc) PR_TRY(launch_retain_gate(*rc, totals, k, 1, s));
                 PR_TRY(launch_adain_fold(fo, s));
                 if (c.precision != PR_PRECISION_FP32 && !naive)
                     PR_TRY(launch_mlp_split(mp, max_tiles, c.precision == PR_PRECISION_F16 ? 1 : 3, s));
@@ -686,6 +717,7 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
         }
 
         if (grouped) {
+            if (rc) PR_TRY(launch_retain_gate(*rc, totals, 0, K, s));      // (behind the block scans of the level)
             PR_TRY(launch_adain_fold_group(fold_jobs, K, s));
             if (c.precision != PR_PRECISION_FP32)
                 PR_TRY(launch_mlp_split_group(jobs, job_rows, K, c.precision == PR_PRECISION_F16 ? 1 : 3, s));
@@ -719,14 +751,15 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
                 cp.proj_k = projection_k(d.W2);
             }
             CompositeObject& o = cp.obj[k];
-            o.t = reinterpret_cast<const float*>(ws + tp.t[k]);
-            o.sigma = reinterpret_cast<const float*>(ws + tp.sigma[k]);
-            o.slot = reinterpret_cast<const int32_t*>(ws + tp.slot[k]);
-            o.dispmag = m.has_bender ? reinterpret_cast<const float*>(ws + tp.dispmag[k]) : nullptr;
+            const SampleArrays arr = sample_arrays(plan, ws, rc, t, k, m.has_bender != 0);
+            o.t = arr.t;
+            o.sigma = arr.sigma;
+            o.slot = arr.slot;
+            o.dispmag = arr.dispmag;
             o.divergence = ((c.flags & PR_FLAG_SAVE_FOR_BACKWARD) && m.has_bender)
                                ? reinterpret_cast<const float*>(ws + tp.saved[k].div) : nullptr;
             if (o.divergence) cp.any_divergence = 1;
-            o.feat = reinterpret_cast<const float*>(ws + tp.feat[k]);
+            o.feat = arr.feat;
             o.noise = perturb_noise(noise.integrate[k], c, NOISE_INTEGRATE, t, k);
             o.positions = m.positions;
             if (out) o.out = out->object[k];
@@ -747,12 +780,13 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
         if (out) {
             for (int k = 0; k < K; ++k) {
                 const size_t cap = (size_t)c.frames * c.rays * tp.positions[k];
+                const SampleArrays arr = sample_arrays(plan, ws, rc, t, k, false);      // (wherever the arrays live)
                 if (out->sample_t[k])
-                    PR_CHECK_HIP(hipMemcpyAsync(out->sample_t[k], ws + tp.t[k], sizeof(float) * cap, hipMemcpyDeviceToDevice, s));
+                    PR_CHECK_HIP(hipMemcpyAsync(out->sample_t[k], arr.t, sizeof(float) * cap, hipMemcpyDeviceToDevice, s));
                 if (out->sample_sigma[k])
-                    PR_CHECK_HIP(hipMemcpyAsync(out->sample_sigma[k], ws + tp.sigma[k], sizeof(float) * cap, hipMemcpyDeviceToDevice, s));
+                    PR_CHECK_HIP(hipMemcpyAsync(out->sample_sigma[k], arr.sigma, sizeof(float) * cap, hipMemcpyDeviceToDevice, s));
                 if (out->sample_slot[k])
-                    PR_CHECK_HIP(hipMemcpyAsync(out->sample_slot[k], ws + tp.slot[k], sizeof(int32_t) * cap, hipMemcpyDeviceToDevice, s));
+                    PR_CHECK_HIP(hipMemcpyAsync(out->sample_slot[k], arr.slot, sizeof(int32_t) * cap, hipMemcpyDeviceToDevice, s));
             }
             if (out->evaluated_samples)
                 PR_CHECK_HIP(hipMemcpyAsync(out->evaluated_samples, totals, sizeof(int32_t) * K, hipMemcpyDeviceToDevice, s));
@@ -761,6 +795,8 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
                                             hipMemcpyDeviceToDevice, s));
         }
     }
+    // retention: the last launches store the keys of the camera and of every retained object this call rendered
+    if (rc) PR_TRY(launch_retain_commit(c, objs, *rc, s));
     return PR_OK;
 }
 
@@ -786,9 +822,17 @@ extern "C" int pr_render_forward(const pr_call_t* call, const pr_object_t* objec
 extern "C" int pr_render_forward_culled(const pr_call_t* call, const pr_object_t* objects, const pr_occupancy_t* occupancy,
                                         const pr_outputs_t* coarse, const pr_outputs_t* fine, void* workspace, size_t workspace_bytes,
                                         void* stream) {
+    return pr_render_forward_retained(call, objects, occupancy, nullptr, coarse, fine, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pr_render_forward_retained(const pr_call_t* call, const pr_object_t* objects, const pr_occupancy_t* occupancy,
+                                          const pr_retained_t* retained, const pr_outputs_t* coarse, const pr_outputs_t* fine,
+                                          void* workspace, size_t workspace_bytes, void* stream) {
     PR_REQUIRE(call && objects && workspace, "pr_render_forward: NULL argument");
     PR_TRY(pr::validate_occupancy(*call, objects, occupancy));
     PR_TRY(pr::validate_call(*call, objects));
+    static thread_local pr::RetainCtx ctx;
+    if (retained) PR_TRY(pr::validate_retained(*call, objects, occupancy, retained, coarse, fine, &ctx));
     pr::Plan plan;
     PR_TRY(pr::make_plan(*call, objects, &plan));
     if (workspace_bytes < plan.bytes) {
@@ -797,7 +841,7 @@ extern "C" int pr_render_forward_culled(const pr_call_t* call, const pr_object_t
     }
     PR_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
     const pr_outputs_t* outs[2] = {coarse, fine};
-    return pr::render(*call, objects, occupancy, outs, static_cast<char*>(workspace), plan, (hipStream_t)stream);
+    return pr::render(*call, objects, occupancy, retained ? &ctx : nullptr, outs, static_cast<char*>(workspace), plan, (hipStream_t)stream);
 }
 
 namespace pr {

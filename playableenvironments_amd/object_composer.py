@@ -19,7 +19,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from . import _lib, field_query, occupancy as _occupancy
+from . import _lib, field_query, occupancy as _occupancy, retention as _retention
 from .modules import OBJECT_MODEL_CLASSES, REGISTRATION_EPOCH as _REGISTRATION_EPOCH, ModuleList, RayBendingStyleNerfModel, Tracked, \
     tree_is_tracked
 
@@ -469,6 +469,11 @@ class ObjectComposer(Tracked, nn.Module):
         #: (``pr_render_forward_culled``): it never reaches the MLP.  Not handed to perturbed, training or differentiable calls, nor
         #: to ``forward_expected_positions``.  The grid's frame count must be the call's.
         self.occupancy: Optional[_occupancy.Occupancy] = None
+        #: retention of chosen objects' per-sample state across evaluation frames: ``None`` (default), or a ``retention.Retained``
+        #: (``retain_objects``) - an object whose inputs did not move since the previous call with the same camera is not placed,
+        #: resampled or sent through the MLP again (``pr_render_forward_retained``; the device decides, results are bit-identical).
+        #: Used on the calls the occupancy grid is used on; not by calls that are split along the rays.
+        self.retained: Optional[_retention.Retained] = None
         #: callables invoked by the autograd node of a differentiable call with the flat fp32 buffer that every parameter gradient
         #: of the call is a view of, right after ``pr_render_backward`` is enqueued (parallel.OverlappedGradientAllReduce starts the
         #: gradient all-reduce from here, so that it overlaps the rest of ``backward()``)
@@ -608,7 +613,7 @@ class ObjectComposer(Tracked, nn.Module):
         ``nn.Module._replicate_for_data_parallel`` would otherwise share dictionaries that hold device-0 pointers between the
         replicas' threads.  A replica lives for one call: it packs the broadcast weights it is given and never caches lists."""
         replica = super()._replicate_for_data_parallel()
-        fresh = dict(occupancy=None, gradient_hooks=[], _packed={}, _param_lists={}, _structs={}, _tracked={}, _annealing={}, _linspace={}, _workspace=None,
+        fresh = dict(occupancy=None, retained=None, gradient_hooks=[], _packed={}, _param_lists={}, _structs={}, _tracked={}, _annealing={}, _linspace={}, _workspace=None,
                      _budget_ok=0, _pending_bn_check=None, last_normalised_samples={}, last_noise_seed=None)
         replica.__dict__.update(fresh)
         # (the replica's backward pass reports parameter gradients to the ORIGINAL: its packed copies / recorded frames are what an
@@ -620,7 +625,7 @@ class ObjectComposer(Tracked, nn.Module):
         # copy.deepcopy / pickle (EMA helpers, swa_utils.AveragedModel): the caches hold ctypes structures with raw pointers
         # (not picklable) and device scratch that a copy must not share
         state = dict(self.__dict__)
-        state.update(occupancy=None, gradient_hooks=[], _packed={}, _param_lists={}, _structs={}, _tracked={}, _annealing={}, _linspace={}, _workspace=None, _budget_ok=0,
+        state.update(occupancy=None, retained=None, gradient_hooks=[], _packed={}, _param_lists={}, _structs={}, _tracked={}, _annealing={}, _linspace={}, _workspace=None, _budget_ok=0,
                      _pending_bn_check=None, last_normalised_samples={}, last_noise_seed=None, _host_step=None)
         state.pop("_replica_of", None)
         return state
@@ -958,6 +963,40 @@ class ObjectComposer(Tracked, nn.Module):
             occ.update_prepared(style_nks, deformation_nkd, canonical_pose)
         return struct
 
+    # ------------------------------------------------------------------ retention
+    def retain_objects(self, objects=None) -> "_retention.Retained":
+        """A ``retention.Retained`` for ``composer.retained = ...``: ``objects`` (default: the static objects, the first
+        ``static_objects_count``) keep their per-sample state between evaluation calls.  Any object may be named, the skybox
+        included."""
+        if objects is None:
+            objects = range(self.object_id_helper.static_objects_count)
+        return _retention.Retained(self, objects)
+
+    def _retention_for_call(self, perturb, save, object_ids) -> Optional["_retention.Retained"]:
+        """The ``Retained`` an evaluation call uses, or None: retention applies to the calls the occupancy grid applies to."""
+        r = self.retained
+        if r is None or perturb or save or self.training or object_ids is not None or self.use_naive_mlp or torch.is_grad_enabled():
+            return None
+        if not isinstance(r, _retention.Retained):
+            raise TypeError(f"ObjectComposer.retained must be a retention.Retained or None, got {type(r).__name__}")
+        if self.occupancy is not None:
+            r.check_occupancy(self.occupancy)       # (a grid too large for the cache's key is refused here, not inside the render)
+        return r
+
+    def _retained_weights_key(self, r: "_retention.Retained") -> tuple:
+        """What the packed weights of the retained objects' models were made from - the key ``_packed_weights_many`` compares, per
+        model, plus ``state_epoch`` (a replayed training graph moves the values on the device without moving the version counters
+        and bumps it): ``Retained.host_key`` advances whenever THIS call finds another key than the previous call that used the
+        ``Retained``, wherever the weights changed or were re-packed in between (also while it was detached)."""
+        helper = self.object_id_helper
+        models = []
+        for k in r.objects:
+            m = helper.model_idx_by_object_idx(k)
+            models.append(self.object_models_coarse[m])
+            if self.object_models_fine[m] is not None:
+                models.append(self.object_models_fine[m])
+        return (self.state_epoch, self.weights_epoch) + tuple(tuple((p.data_ptr(), p._version) for p in self._parameter_list(m)) for m in models)
+
     # ------------------------------------------------------------------ forward
     def forward(self, ray_origins: torch.Tensor, ray_directions: torch.Tensor, focal_normals: torch.Tensor,
                 transformation_matrix_w2o: torch.Tensor, style: torch.Tensor, deformation: torch.Tensor,
@@ -1241,6 +1280,7 @@ class ObjectComposer(Tracked, nn.Module):
                 get(f"int_{ty}_global", (N, R, sum(ptot[ty])), True)
 
         culled = self._occupancy_for_call(N, ids, use_fine, perturb, _save, _object_ids, sty, dfm, canonical_pose, dev)
+        retained = self._retention_for_call(perturb, _save, _object_ids)
 
         # ---- ray chunking against the workspace budget -----------------------------------------
         def build_call(r0: int, r1: int):
@@ -1322,6 +1362,9 @@ class ObjectComposer(Tracked, nn.Module):
                 raise RuntimeError("decoder-layout emission needs the whole call in one launch (the call was split along the rays "
                                    "to fit the workspace budget)")
 
+        if retained is not None and chunk != R:
+            retained.warn_split()
+            retained = None
         pieces = []
         for r0 in range(0, R, chunk):
             r1 = min(R, r0 + chunk)
@@ -1377,8 +1420,11 @@ class ObjectComposer(Tracked, nn.Module):
                 if _export:
                     ex = {"t": [], "sigma": [], "slot": [], "delta": []}
                     for k in range(K):
-                        ex["delta"].append(torch.empty((N, rc, ptot[ty][k], 3), **f32))
-                        o.sample_delta[k] = ex["delta"][k].data_ptr()
+                        if retained is not None and k in retained.objects:
+                            ex["delta"].append(None)          # (the dense displacement of a retained object is not cached)
+                        else:
+                            ex["delta"].append(torch.empty((N, rc, ptot[ty][k], 3), **f32))
+                            o.sample_delta[k] = ex["delta"][k].data_ptr()
                         ex["t"].append(torch.empty((N, rc, ptot[ty][k]), **f32))
                         ex["sigma"].append(torch.empty((N, rc, ptot[ty][k]), **f32))
                         ex["slot"].append(torch.empty((N, rc, ptot[ty][k]), dtype=torch.int32, device=dev))
@@ -1392,7 +1438,17 @@ class ObjectComposer(Tracked, nn.Module):
                     res["_samples"] = ex
                 outs[ty] = res
                 structs[ty] = o
-            if culled is not None:
+            if retained is not None:
+                key = (N, R, use_fine, int(call.precision), bool(self.defer_feature_projection), bool(self.gate_feature_head),
+                       bool(canonical_pose), None if culled is None else self.occupancy.serial)
+                retained.weights_seen(self._retained_weights_key(retained))
+                rstruct = retained.call_struct(lib, call, objs, K, key, dev, stream)
+                _lib.check(lib.pr_render_forward_retained(C.byref(call), objs, None if culled is None else C.byref(culled),
+                                                          C.byref(rstruct), C.byref(structs["coarse"]),
+                                                          C.byref(structs["fine"]) if use_fine else None,
+                                                          workspace.data_ptr(), workspace.numel(), stream),
+                           "pr_render_forward_retained")
+            elif culled is not None:
                 _lib.check(lib.pr_render_forward_culled(C.byref(call), objs, C.byref(culled), C.byref(structs["coarse"]),
                                                         C.byref(structs["fine"]) if use_fine else None,
                                                         workspace.data_ptr(), workspace.numel(), stream),
