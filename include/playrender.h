@@ -335,7 +335,7 @@ int pr_render_forward_culled(const pr_call_t* call, const pr_object_t* objects, 
  *
  * What the device cannot see is the caller's: host_key must change whenever the VALUES of the retained objects' packed weights
  * change.  The library adds a digest of what it sees on the host (honoured flags, precision, N, R, K, use_fine, positions, the scalar
- * fields of the models incl. box, depth range and octave weights, occupancy cell counts, object_mask); another digest: nothing reused.
+ * fields of the models incl. box, depth range and octave weights, occupancy cell counts, object_mask, the parameters of a fine guide); another digest: nothing reused.
  *
  * Cache layout (private; every region 256-byte aligned; pr_retained_size is their sum): a 256-byte header; ray_origins (N,3) and
  * ray_directions (N,R,3); per retained object w2o (N,12), presence (N words), style (N,S), deformation (N,D); per level bn1 mean /
@@ -365,6 +365,45 @@ int pr_retained_reset(void* cache, size_t cache_bytes, void* stream);
 int pr_render_forward_retained(const pr_call_t* call, const pr_object_t* objects, const pr_occupancy_t* occupancy,
                                const pr_retained_t* retained, const pr_outputs_t* coarse, const pr_outputs_t* fine,
                                void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Fine guide: the fine pass of the objects in object_mask evaluates a merged (coarse + resampled) sample only where the coarse pass
+ * found density near it.  For one ray let tc[0 .. Pc - 1] be the coarse depths and s[i] the raw coarse density as the resampler reads
+ * it (the coarse model's sigma, or empty_space_alpha for an object that is absent from the frame); coarse sample i is LIVE iff
+ * s[i] > threshold.  A merged sample at depth t has j = max(0, #{i : tc[i] <= t} - 1) (comparisons only) and is kept iff some i in
+ * [j - guard, j + 1 + guard] (clipped to [0, Pc - 1]) is live AND it passes the box test and the fine occupancy bit, if any.  A
+ * sample the guide drops is treated exactly like a sample outside the box: slot -1, density empty_space_alpha, feature row 0,
+ * displacement 0; it keeps its depth and takes part in compositing and the overlap fix.  The coarse pass is untouched;
+ * evaluated_samples / head_samples of the fine level report the counts after culling.  This is an APPROXIMATION that is only as good
+ * as the coarse model's agreement with the fine one (nothing about it is conservative); threshold = -inf keeps every sample.
+ *
+ * scratch holds one keep bit per merged sample - bit (i & 31) of word (i >> 5) of the ray's ceil((Pc_k + Pf_k) / 32) words - for the
+ * guided objects in ascending order, each object's (N, R, words) region rounded up to 256 bytes: pr_fine_guide_size is the sum of
+ * align256(4 * N * R * ceil((Pc_k + Pf_k) / 32)) over the objects of the mask.  Every word is written by the resampler before the
+ * compaction reads it (no memset, no atomics); the scratch holds nothing between calls and must not be shared by calls in flight.
+ * Retention: a retained object that is reused skips both kernels; object_mask, guard and the bits of threshold enter the
+ * retained cache's host digest (another guide: nothing reused).
+ *
+ * Unperturbed evaluation calls with use_fine only.  Refused (PR_ERR_INVALID, before any device work) with a non-zero object_mask:
+ * PR_FLAG_PERTURB or an integrate-noise pointer, PR_FLAG_TRAIN_BN, PR_FLAG_SAVE_FOR_BACKWARD, PR_FLAG_NAIVE_MLP, use_fine == 0, a mask
+ * bit at or beyond `objects` or on a skybox model (kind == 1), guard < 0, a NaN threshold, a misaligned or too small scratch.
+ * object_mask == 0: exactly a NULL guide.
+ */
+typedef struct pr_fine_guide_t {
+    uint32_t object_mask;   /* bit k: the fine pass of object k is guided */
+    int32_t  guard;         /* >= 0: coarse samples the live window extends to either side */
+    float    threshold;     /* a coarse sample is live iff its raw density is > threshold (0: alpha exactly 0 below) */
+    uint32_t reserved_;
+    uint32_t* scratch;      /* device, 256-byte aligned, pr_fine_guide_size bytes, caller-owned */
+    size_t   scratch_bytes;
+} pr_fine_guide_t;
+/* Bytes of the scratch for this call and mask (host computation, no device work). */
+int pr_fine_guide_size(const pr_call_t* call, const pr_object_t* objects, uint32_t object_mask, size_t* bytes);
+/* pr_render_forward_retained with a fine guide (guide == NULL: exactly pr_render_forward_retained; occupancy and retained may be
+ * NULL).  pr_workspace_size is unchanged. */
+int pr_render_forward_guided(const pr_call_t* call, const pr_object_t* objects, const pr_occupancy_t* occupancy,
+                             const pr_retained_t* retained, const pr_fine_guide_t* guide, const pr_outputs_t* coarse,
+                             const pr_outputs_t* fine, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * Builds occupancy bits from a density lattice: sigma (groups, cells[0] * s, cells[1] * s, cells[2] * s) with supersample factor
@@ -623,7 +662,9 @@ int pr_query_field(const pr_query_t* q, const pr_object_model_t* model, const vo
  * hipEventRecord on the launch stream.  Categories: 0 = fused MLP (k_mlp_mfma / k_mlp_split / k_mlp_head),
  * 1 = forward compositing (k_composite), 2 = backward dX products (k_gemm_nn), 3 = backward dW products
  * (k_gemm_tn + its reduction), 4 = backward compositing (k_composite_bwd), 5 = the front and back end of pr_query_field
- * (k_query_count + block scan + k_query_fill, k_query_scatter; its MLP launch counts as 0); the rest are reserved.
+ * (k_query_count + block scan + k_query_fill, k_query_scatter; its MLP launch counts as 0), 6 = hierarchical resampling (k_resample with
+ * the fill of its block sums), 7 = compaction launched per object (k_fill: the fine level, and the coarse level of calls that place
+ * their objects one by one).
  * pr_profile_collect synchronises the recorded events, returns the summed milliseconds and launch
  * counts per category (host arrays of PR_PROFILE_CATEGORIES) and clears the list.
  */

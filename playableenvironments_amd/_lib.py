@@ -171,6 +171,12 @@ class Retained(C.Structure):
                 ("cache_bytes", C.c_size_t), ("reused", C.c_void_p)]
 
 
+class FineGuide(C.Structure):
+    """pr_fine_guide_t (include/playrender.h)."""
+    _fields_ = [("object_mask", C.c_uint32), ("guard", C.c_int32), ("threshold", C.c_float), ("reserved_", C.c_uint32),
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
+
+
 # every exported symbol of include/playrender.h : (restype, argtypes)
 class SceneSetup(C.Structure):
     """pr_scene_setup_t (include/playrender.h)."""
@@ -199,6 +205,9 @@ SYMBOLS = {
     "pr_retained_reset": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_render_forward_retained": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(Occupancy), C.POINTER(Retained),
                                              C.POINTER(Outputs), C.POINTER(Outputs), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pr_fine_guide_size": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.c_uint32, C.POINTER(C.c_size_t)]),
+    "pr_render_forward_guided": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(Occupancy), C.POINTER(Retained),
+                                           C.POINTER(FineGuide), C.POINTER(Outputs), C.POINTER(Outputs), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_occupancy_build": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p]),
     "pr_backward_workspace_size": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(C.c_size_t)]),
     "pr_render_backward": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(OutputGrads), C.POINTER(OutputGrads),

@@ -281,34 +281,39 @@ __device__ __forceinline__ void fill_body(const FillParams& p) {
     auto walk = [&](auto&& per_ray) {
         for (int r0 = 0; r0 < 64 && wave_first + r0 < total; r0 += L.per_pass) {
             const int r = r0 + L.sub;
-            per_ray(r0, r, wave_first + r < total, broadcast_ray(ray, valid, frame, r), (size_t)(wave_first + r) * P);
+            per_ray(r0, r, wave_first + r < total, broadcast_ray(ray, valid, frame, r), wave_first + r);
         }
     };
-    auto inside_at = [&](bool live, const WaveRay& w, size_t base, int i, float* x, float* y, float* z) {
+    // fine level of a guided object: the keep bits k_resample wrote for this ray (NULL: wave-uniform, as occ.bits)
+    const PR_GLOBAL_AS uint32_t* keep = as_global(p.keep);
+    const int keep_words = p.keep_words;
+    auto inside_at = [&](bool live, const WaveRay& w, long ray_index, int i, float* x, float* y, float* z) {
         if (!live || i >= P) return false;
-        const float t = p.t[base + i];
+        const float t = p.t[(size_t)ray_index * P + i];
         *x = __fadd_rn(w.o[0], __fmul_rn(w.d[0], t));
         *y = __fadd_rn(w.o[1], __fmul_rn(w.d[1], t));
         *z = __fadd_rn(w.o[2], __fmul_rn(w.d[2], t));
+        if (keep && !((keep[(size_t)ray_index * keep_words + (i >> 5)] >> (i & 31)) & 1u)) return false;
         return sample_kept(*x, *y, *z, p.lo, p.hi, p.occ, w.frame);    // (absent objects included, see k_place_coarse)
     };
     int count = 0;
-    walk([&](int r0, int r, bool live, const WaveRay& w, size_t base) {
+    walk([&](int r0, int r, bool live, const WaveRay& w, long ray_index) {
         int ray_count = 0;
         for (int i0 = 0; i0 < P; i0 += L.P2) {
             float x, y, z;
-            ray_count += __popcll(L.mine(__ballot(inside_at(live, w, base, i0 + L.idx, &x, &y, &z))));
+            ray_count += __popcll(L.mine(__ballot(inside_at(live, w, ray_index, i0 + L.idx, &x, &y, &z))));
         }
         L.collect(ray_count, r0, lane, &count);
     });
     int block_total;
     const int first_slot = p.block_offsets[blockIdx.x] + block_exclusive_scan_256(count, lds, &block_total);
-    walk([&](int r0, int r, bool live, const WaveRay& w, size_t base) {
+    walk([&](int r0, int r, bool live, const WaveRay& w, long ray_index) {
+        const size_t base = (size_t)ray_index * P;
         int slot = __shfl(first_slot, r, 64);
         for (int i0 = 0; i0 < P; i0 += L.P2) {
             const int i = i0 + L.idx;
             float x = 0.f, y = 0.f, z = 0.f;
-            const bool inside = inside_at(live, w, base, i, &x, &y, &z);
+            const bool inside = inside_at(live, w, ray_index, i, &x, &y, &z);
             const unsigned long long mask = L.mine(__ballot(inside));
             if (inside) {
                 const int mine = slot + __popcll(mask & ((1ull << L.idx) - 1ull));
@@ -359,6 +364,7 @@ int launch_placement_group(const PlaceParams* pp, const FillParams* fp, int32_t*
 int launch_fill(const FillParams& p, hipStream_t s) {
     const long total = (long)p.frames * p.rays;
     const int blocks = (int)((total + 255) / 256);
+    ProfileScope scope(7, s);
     hipLaunchKernelGGL(k_fill, dim3(blocks), dim3(256), 0, s, p);
     PR_LAUNCH_CHECK();
     return PR_OK;
@@ -397,7 +403,11 @@ __global__ __launch_bounds__(64) void k_resample(ResampleParams p, int sort_size
     float* al = tc + Pc;        // [Pc] alpha, then weights
     float* mids = al + Pc;      // [Pc]
     float* cdf = mids + Pc;     // [Pc]
-    float* key = cdf + Pc;      // [sort_size]
+    float* key = cdf + Pc;      // [sort_size], then the merged list [sort_size]
+    // fine guide (p.keep != NULL, uniform over the grid): behind the merged list, live[i] = the coarse sample's raw density is above
+    // the threshold, near[j] = some live sample in [j - guard, j + 1 + guard] (launch_resample sizes the LDS accordingly)
+    int* live = reinterpret_cast<int*>(key + 2 * sort_size);    // [Pc]
+    int* near = live + Pc;                                       // [Pc]
     const int lane = threadIdx.x;
     const long g = blockIdx.x;
     const int n = (int)(g / p.rays);
@@ -412,6 +422,7 @@ __global__ __launch_bounds__(64) void k_resample(ResampleParams p, int sort_size
     __syncthreads();
     for (int i = lane; i < Pc; i += 64) {
         float raw = valid ? p.sigma_coarse[cbase + i] : p.empty_alpha;
+        if (p.keep) live[i] = raw > p.threshold ? 1 : 0;
         if (noise_present(p.alpha_noise)) raw = __fadd_rn(raw, noise_normal(p.alpha_noise, g, Pc, i));
         const float dt = (i < Pc - 1) ? __fsub_rn(tc[i + 1], tc[i]) : 1e10f;
         const float dist = __fmul_rn(dt, norm);
@@ -420,6 +431,16 @@ __global__ __launch_bounds__(64) void k_resample(ResampleParams p, int sort_size
         if (i < Pc - 1) mids[i] = __fdiv_rn(__fadd_rn(tc[i + 1], tc[i]), 2.0f);
     }
     __syncthreads();
+    if (p.keep) {
+        // once per ray, so that a merged sample costs one search and one load (guard <= Pc: launch_resample)
+        for (int j = lane; j < Pc; j += 64) {
+            const int first = j - p.guard < 0 ? 0 : j - p.guard;
+            const int last = j + 1 + p.guard > Pc - 1 ? Pc - 1 : j + 1 + p.guard;
+            int any = 0;
+            for (int i = first; i <= last; ++i) any |= live[i];
+            near[j] = any;
+        }
+    }
     if (lane == 0) {
         // weights = alpha * cumprod([1, 1 - alpha + 1e-10][:-1])
         float trans = 1.0f;
@@ -493,15 +514,48 @@ __global__ __launch_bounds__(64) void k_resample(ResampleParams p, int sort_size
     }
     const size_t fbase = (size_t)g * Pm;
     int count = 0;
-    for (int i = lane; i < Pm; i += 64) {
-        const float t = merged[i];
+    // writes merged sample i and says whether it is evaluated: fill_body's inside_at decides the same from the same depth
+    auto emit = [&](int i, float t, bool guided) {
         p.t_fine[fbase + i] = t;
         p.sigma_fine[fbase + i] = p.empty_alpha;
         if (p.dispmag_fine) p.dispmag_fine[fbase + i] = 0.f;
         const float x = __fadd_rn(ray.o[0], __fmul_rn(ray.d[0], t));
         const float y = __fadd_rn(ray.o[1], __fmul_rn(ray.d[1], t));
         const float z = __fadd_rn(ray.o[2], __fmul_rn(ray.d[2], t));
-        if (sample_kept(x, y, z, p.lo, p.hi, p.occ, n)) ++count;      // (absent objects included, see k_place_coarse)
+        return guided && sample_kept(x, y, z, p.lo, p.hi, p.occ, n);      // (absent objects included, see k_place_coarse)
+    };
+    if (!p.keep) {
+        for (int i = lane; i < Pm; i += 64)
+            if (emit(i, merged[i], true)) ++count;
+    } else {
+        // j = max(0, #{i : tc[i] <= t} - 1): a binary search where the coarse depths ascend (they do by construction; a ray whose
+        // depths do not - NaN rays, rounding on a degenerate segment - counts them one by one, which is the definition)
+        bool ascending = true;
+        for (int i = lane; i + 1 < Pc; i += 64) ascending = ascending && (tc[i] <= tc[i + 1]);
+        const bool search = __ballot(ascending) == ~0ull;
+        PR_GLOBAL_AS uint32_t* row = as_global(p.keep) + (size_t)g * p.keep_words;
+        for (int i0 = 0; i0 < Pm; i0 += 64) {       // (whole-wave steps: two keep words each)
+            const int i = i0 + lane;
+            bool guided = false;
+            if (i < Pm) {
+                const float t = merged[i];
+                int below = 0;          // #{i : tc[i] <= t}
+                if (search) {
+                    int hi = Pc;
+                    while (below < hi) {
+                        const int mid = (below + hi) >> 1;
+                        if (tc[mid] <= t) below = mid + 1; else hi = mid;
+                    }
+                } else {
+                    for (int c = 0; c < Pc; ++c) below += tc[c] <= t ? 1 : 0;
+                }
+                guided = near[below > 0 ? below - 1 : 0] != 0;
+                if (emit(i, t, guided)) ++count;
+            }
+            const unsigned long long bits = __ballot(guided);      // (lanes beyond the list: 0, the tail bits of the last word)
+            const int word = (i0 >> 5) + lane;
+            if (lane < 2 && word < p.keep_words) row[word] = (uint32_t)(bits >> (32 * lane));
+        }
     }
 #pragma unroll
     for (int d = 32; d > 0; d >>= 1) count += __shfl_down(count, d, 64);
@@ -543,12 +597,19 @@ int launch_resample(const ResampleParams& p, hipStream_t s) {
     PR_REQUIRE(p.pc >= 3, "hierarchical sampling needs at least 3 coarse positions (got %d)", p.pc);
     const long total = (long)p.frames * p.rays;
     const int nblocks256 = (int)((total + 255) / 256);
+    ProfileScope scope(6, s);
     PR_TRY(launch_zero_fill(p.block_sums, sizeof(int32_t) * nblocks256, s));
     int sort_size = next_pow2(p.pc + p.pf);
     if (sort_size < 64) sort_size = 64;
-    const size_t lds = sizeof(float) * (4 * (size_t)p.pc + 2 * (size_t)sort_size);   // inputs + sort keys + merged list
+    size_t lds = sizeof(float) * (4 * (size_t)p.pc + 2 * (size_t)sort_size);   // inputs + sort keys + merged list
+    ResampleParams q = p;
+    if (q.keep) {
+        PR_REQUIRE(q.guard >= 0 && q.keep_words == (q.pc + q.pf + 31) / 32, "resample: bad guide (guard %d, %d words)", q.guard, q.keep_words);
+        if (q.guard > q.pc) q.guard = q.pc;          // (the window already spans the ray; keeps j + 1 + guard from overflowing)
+        lds += sizeof(int) * 2 * (size_t)q.pc;       // live + near flags
+    }
     PR_REQUIRE(lds <= 64 * 1024, "resample: too many positions per ray (%d + %d)", p.pc, p.pf);
-    hipLaunchKernelGGL(k_resample, dim3((unsigned)total), dim3(64), lds, s, p, sort_size);
+    hipLaunchKernelGGL(k_resample, dim3((unsigned)total), dim3(64), lds, s, q, sort_size);
     PR_LAUNCH_CHECK();
     return PR_OK;
 }

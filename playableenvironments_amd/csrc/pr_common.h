@@ -348,6 +348,8 @@ struct FillParams {
     int32_t* slot;                // (N,R,P) compact row or -1
     OccGrid occ;
     const int32_t* skip;          // as PlaceParams::skip
+    const uint32_t* keep;         // fine level of a guided object (pr_fine_guide_t): the keep bits k_resample wrote, bit (i & 31) of word
+    int keep_words;               // keep[ray * keep_words + (i >> 5)] for sample i of the ray; NULL = not guided
 };
 int launch_fill(const FillParams& p, hipStream_t s);
 int launch_placement_group(const PlaceParams* pp, const FillParams* fp, int32_t* const* totals, int count, hipStream_t s);
@@ -375,6 +377,12 @@ struct ResampleParams {
     int32_t* block_sums;
     OccGrid occ;                  // grid of the FINE model: culls the merged coarse + resampled positions
     const int32_t* skip;          // as PlaceParams::skip
+    // fine guide (pr_fine_guide_t) or keep == NULL: a merged sample at depth t with j = max(0, #{i : t_coarse[i] <= t} - 1) is kept
+    // iff a coarse sample of [j - guard, j + 1 + guard] has raw density > threshold; one bit per merged sample, every word written
+    uint32_t* keep;               // (N,R,keep_words) out
+    int keep_words;               // ceil((pc + pf) / 32)
+    int guard;                    // >= 0
+    float threshold;
 };
 int launch_resample(const ResampleParams& p, hipStream_t s);
 
@@ -557,8 +565,9 @@ struct RetainCtx {                           // one call's view of the cache (ho
     const pr_occupancy_t* occupancy;
 };
 int make_retain_plan(const pr_call_t& c, const pr_object_t* objs, uint32_t mask, RetainPlan* plan);
-int validate_retained(const pr_call_t& c, const pr_object_t* objs, const pr_occupancy_t* occ, const pr_retained_t* r,
-                      const pr_outputs_t* coarse, const pr_outputs_t* fine, RetainCtx* ctx);
+// (guide: the call's fine guide or NULL - its mask, guard and threshold bits enter the host digest)
+int validate_retained(const pr_call_t& c, const pr_object_t* objs, const pr_occupancy_t* occ, const pr_fine_guide_t* guide,
+                      const pr_retained_t* r, const pr_outputs_t* coarse, const pr_outputs_t* fine, RetainCtx* ctx);
 int launch_retain_probe(const pr_call_t& c, const pr_object_t* objs, const RetainCtx& rc, hipStream_t s);
 int launch_retain_gate(const RetainCtx& rc, int32_t* totals, int first, int count, hipStream_t s);
 int launch_retain_commit(const pr_call_t& c, const pr_object_t* objs, const RetainCtx& rc, hipStream_t s);

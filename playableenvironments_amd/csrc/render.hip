@@ -331,8 +331,51 @@ static SampleArrays sample_arrays(const Plan& plan, char* ws, const RetainCtx* r
     return a;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Fine guide (pr_fine_guide_t): the keep bits of the guided objects, one 256-byte aligned (N, R, words) region per object
+// ---------------------------------------------------------------------------------------------
+struct GuidePlan {
+    size_t at[PR_MAX_OBJECTS];       // byte offset of object k's bits ((size_t)-1: not guided)
+    int words[PR_MAX_OBJECTS];       // ceil((Pc_k + Pf_k) / 32)
+    size_t bytes;
+};
+static int make_guide_plan(const pr_call_t& c, const pr_object_t* objs, uint32_t mask, GuidePlan* plan) {
+    PR_REQUIRE((mask >> c.objects) == 0, "fine guide object_mask 0x%x names an object at or beyond objects = %d", mask, c.objects);
+    PR_REQUIRE(mask == 0 || c.use_fine, "a fine guide needs a hierarchical call: use_fine is 0");
+    size_t off = 0;
+    for (int k = 0; k < PR_MAX_OBJECTS; ++k) {
+        plan->at[k] = (size_t)-1;
+        plan->words[k] = 0;
+        if (k >= c.objects || !((mask >> k) & 1u)) continue;
+        PR_REQUIRE(objs[k].fine.kind != 1 && objs[k].coarse.kind != 1, "fine guide: object %d is a skybox model (its density is a constant)", k);
+        plan->words[k] = (objs[k].fine.positions + 31) / 32;
+        plan->at[k] = off;
+        off += align_up(sizeof(uint32_t) * (size_t)c.frames * c.rays * plan->words[k]);
+    }
+    plan->bytes = off;
+    return PR_OK;
+}
+
+// Host checks of pr_render_forward_guided: no device work, so that a refusal precedes everything else.  A guide without objects is no guide.
+static int validate_guide(const pr_call_t& c, const pr_object_t* objs, const pr_fine_guide_t* g, GuidePlan* plan) {
+    PR_REQUIRE(!(c.flags & PR_FLAG_PERTURB), "the fine guide applies to unperturbed evaluation calls only: PR_FLAG_PERTURB is set");
+    PR_REQUIRE(!(c.flags & PR_FLAG_TRAIN_BN), "the fine guide applies to evaluation calls only: PR_FLAG_TRAIN_BN is set");
+    PR_REQUIRE(!(c.flags & PR_FLAG_SAVE_FOR_BACKWARD), "the fine guide applies to evaluation calls only: PR_FLAG_SAVE_FOR_BACKWARD is set");
+    PR_REQUIRE(!(c.flags & PR_FLAG_NAIVE_MLP), "the fine guide is not supported with PR_FLAG_NAIVE_MLP");
+    bool noise = c.noise_coarse.integrate_global || c.noise_fine.integrate_global;
+    for (int k = 0; k < PR_MAX_OBJECTS; ++k) noise = noise || c.noise_coarse.integrate[k] || c.noise_fine.integrate[k];
+    PR_REQUIRE(!noise, "the fine guide applies to unperturbed evaluation calls only: an integrate-noise pointer is set");
+    PR_TRY(make_guide_plan(c, objs, g->object_mask, plan));
+    PR_REQUIRE(g->guard >= 0, "fine guide: guard %d is negative", g->guard);
+    PR_REQUIRE(g->threshold == g->threshold, "fine guide: the threshold is NaN");
+    PR_REQUIRE(g->scratch != nullptr && ((uintptr_t)g->scratch & 255) == 0, "fine guide scratch must be a 256-byte aligned device pointer");
+    PR_REQUIRE(g->scratch_bytes >= plan->bytes, "fine guide scratch too small: %zu bytes given, %zu needed", g->scratch_bytes, plan->bytes);
+    return PR_OK;
+}
+
 static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupancy_t* occupancy, const RetainCtx* rc,
-                  const pr_outputs_t* outs[2], char* ws, const Plan& plan, hipStream_t s) {
+                  const pr_fine_guide_t* guide, const GuidePlan* gplan, const pr_outputs_t* outs[2], char* ws, const Plan& plan,
+                  hipStream_t s) {
     const int ntypes = c.use_fine ? 2 : 1;
     const int K = c.objects;
     // retention: the first launches compare the cached keys with this call's inputs and set the reuse flags
@@ -471,6 +514,9 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
             const SavedPlan& sv = tp.saved[k];
             // empty-space skipping: the grid of this object and model type (bits == NULL without one) - the same grid at the
             // count and the fill site of the type
+            // fine guide: this object's keep bits at the fine level (NULL: not guided) - written by the resampler, read by the fill
+            uint32_t* keep = (guide && t == 1 && gplan->at[k] != (size_t)-1)
+                                 ? reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(guide->scratch) + gplan->at[k]) : nullptr;
             OccGrid occ;
             PR_TRY(make_occ_grid(occupancy ? (t ? &occupancy->fine[k] : &occupancy->coarse[k]) : nullptr, m, k, t ? "fine" : "coarse", &occ));
             if (save) {
@@ -515,6 +561,9 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
                 rp.t_fine = t_arr; rp.sigma_fine = sigma; rp.dispmag_fine = dispmag; rp.block_sums = block_sums;
                 rp.occ = occ;
                 rp.skip = skip;
+                if (keep) {
+                    rp.keep = keep; rp.keep_words = gplan->words[k]; rp.guard = guide->guard; rp.threshold = guide->threshold;
+                }
                 PR_TRY(launch_resample(rp, s));
             }
             if (pass == 1 && !placed) PR_TRY(launch_scan(block_sums, block_offsets, totals + k, plan.nblocks256, s));
@@ -529,6 +578,9 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
             fp.t = t_arr; fp.block_offsets = block_offsets; fp.rec_pos = rec_pos; fp.rec_flat = rec_flat; fp.slot = slot;
             fp.occ = occ;
             fp.skip = skip;
+            if (keep) {
+                fp.keep = keep; fp.keep_words = gplan->words[k];
+            }
             if (pass == 0) {
                 fill_jobs[k] = fp;
                 total_ptrs[k] = totals + k;
@@ -828,11 +880,29 @@ extern "C" int pr_render_forward_culled(const pr_call_t* call, const pr_object_t
 extern "C" int pr_render_forward_retained(const pr_call_t* call, const pr_object_t* objects, const pr_occupancy_t* occupancy,
                                           const pr_retained_t* retained, const pr_outputs_t* coarse, const pr_outputs_t* fine,
                                           void* workspace, size_t workspace_bytes, void* stream) {
+    return pr_render_forward_guided(call, objects, occupancy, retained, nullptr, coarse, fine, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pr_fine_guide_size(const pr_call_t* call, const pr_object_t* objects, uint32_t object_mask, size_t* bytes) {
+    PR_REQUIRE(call && objects && bytes, "pr_fine_guide_size: NULL argument");
+    PR_TRY(pr::validate_call(*call, objects));
+    pr::GuidePlan plan;
+    PR_TRY(pr::make_guide_plan(*call, objects, object_mask, &plan));
+    *bytes = plan.bytes;
+    return PR_OK;
+}
+
+extern "C" int pr_render_forward_guided(const pr_call_t* call, const pr_object_t* objects, const pr_occupancy_t* occupancy,
+                                        const pr_retained_t* retained, const pr_fine_guide_t* guide, const pr_outputs_t* coarse,
+                                        const pr_outputs_t* fine, void* workspace, size_t workspace_bytes, void* stream) {
     PR_REQUIRE(call && objects && workspace, "pr_render_forward: NULL argument");
     PR_TRY(pr::validate_occupancy(*call, objects, occupancy));
     PR_TRY(pr::validate_call(*call, objects));
+    if (guide && guide->object_mask == 0) guide = nullptr;
+    pr::GuidePlan gplan;
+    if (guide) PR_TRY(pr::validate_guide(*call, objects, guide, &gplan));
     static thread_local pr::RetainCtx ctx;
-    if (retained) PR_TRY(pr::validate_retained(*call, objects, occupancy, retained, coarse, fine, &ctx));
+    if (retained) PR_TRY(pr::validate_retained(*call, objects, occupancy, guide, retained, coarse, fine, &ctx));
     pr::Plan plan;
     PR_TRY(pr::make_plan(*call, objects, &plan));
     if (workspace_bytes < plan.bytes) {
@@ -841,7 +911,8 @@ extern "C" int pr_render_forward_retained(const pr_call_t* call, const pr_object
     }
     PR_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
     const pr_outputs_t* outs[2] = {coarse, fine};
-    return pr::render(*call, objects, occupancy, retained ? &ctx : nullptr, outs, static_cast<char*>(workspace), plan, (hipStream_t)stream);
+    return pr::render(*call, objects, occupancy, retained ? &ctx : nullptr, guide, &gplan, outs, static_cast<char*>(workspace), plan,
+                      (hipStream_t)stream);
 }
 
 namespace pr {

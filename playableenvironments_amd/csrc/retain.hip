@@ -69,13 +69,22 @@ static uint64_t fnv(uint64_t h, const void* data, size_t bytes) {
     return h;
 }
 
-static uint64_t host_digest(const pr_call_t& c, const pr_object_t* objs, const pr_occupancy_t* occ, const pr_retained_t& r) {
+static uint64_t host_digest(const pr_call_t& c, const pr_object_t* objs, const pr_occupancy_t* occ, const pr_fine_guide_t* guide,
+                            const pr_retained_t& r) {
     uint64_t h = 0xCBF29CE484222325ull;
     const uint32_t honoured = (c.flags & (PR_FLAG_CANONICAL_POSE | PR_FLAG_FIX_OVERLAPS | PR_FLAG_SIGMOID_FEATURES)) |
                               (gate_active(c) ? PR_FLAG_GATE_HEAD : 0u) | (defer_active(c, objs) ? PR_FLAG_DEFER_PROJECTION : 0u);
     const int32_t head[8] = {(int32_t)honoured, c.precision, c.frames, c.rays, c.objects, c.use_fine ? 1 : 0, (int32_t)r.object_mask, 0};
     h = fnv(h, head, sizeof(head));
     h = fnv(h, &r.host_key, sizeof(r.host_key));
+    // the fine guide: a retained object's fine arrays are a function of its parameters too (the threshold by its bit pattern)
+    uint32_t fg[3] = {0u, 0u, 0u};
+    if (guide && guide->object_mask) {
+        fg[0] = guide->object_mask;
+        fg[1] = (uint32_t)guide->guard;
+        memcpy(&fg[2], &guide->threshold, sizeof(float));
+    }
+    h = fnv(h, fg, sizeof(fg));
     const size_t scalars = offsetof(pr_object_model_t, backbone);   // kind .. bn_eps: dimensions, octave weights, box, depth range
     for (int k = 0; k < c.objects; ++k) {
         if (!((r.object_mask >> k) & 1u)) continue;
@@ -102,8 +111,8 @@ static int occ_key_words(const pr_occupancy_grid_t& g) {
 }
 
 // Host checks of pr_render_forward_retained: no device work, so that a refusal precedes everything else.  Fills `ctx`.
-int validate_retained(const pr_call_t& c, const pr_object_t* objs, const pr_occupancy_t* occ, const pr_retained_t* r,
-                      const pr_outputs_t* coarse, const pr_outputs_t* fine, RetainCtx* ctx) {
+int validate_retained(const pr_call_t& c, const pr_object_t* objs, const pr_occupancy_t* occ, const pr_fine_guide_t* guide,
+                      const pr_retained_t* r, const pr_outputs_t* coarse, const pr_outputs_t* fine, RetainCtx* ctx) {
     PR_REQUIRE(!(c.flags & PR_FLAG_PERTURB), "retention applies to unperturbed evaluation calls only: PR_FLAG_PERTURB is set");
     PR_REQUIRE(!(c.flags & PR_FLAG_TRAIN_BN), "retention applies to evaluation calls only: PR_FLAG_TRAIN_BN is set (the running statistics move)");
     PR_REQUIRE(!(c.flags & PR_FLAG_SAVE_FOR_BACKWARD), "retention applies to evaluation calls only: PR_FLAG_SAVE_FOR_BACKWARD is set");
@@ -135,7 +144,7 @@ int validate_retained(const pr_call_t& c, const pr_object_t* objs, const pr_occu
     ctx->base = static_cast<char*>(r->cache);
     ctx->hdr = reinterpret_cast<RetainHeader*>(r->cache);
     ctx->mask = r->object_mask;
-    ctx->digest = host_digest(c, objs, occ, *r);
+    ctx->digest = host_digest(c, objs, occ, guide, *r);
     ctx->reused = r->reused;
     ctx->occupancy = occ;
     return PR_OK;

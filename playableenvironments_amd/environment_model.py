@@ -888,7 +888,8 @@ class EnvironmentModel(Tracked, nn.Module):
                 None if composer.object_entry_fields is None else tuple(composer.object_entry_fields),
                 bool(self.fused_scene_setup), bool(composer.training), bool(composer.use_naive_mlp), float(self.focal_length_multiplier),
                 int(composer.max_workspace_bytes), None if composer.occupancy is None else composer.occupancy.signature(),
-                None if composer.retained is None else composer.retained.signature())
+                None if composer.retained is None else composer.retained.signature(),
+                None if composer.fine_guide is None else composer.fine_guide.signature())
 
     def _replayed(self, name: str, method, tensors, statics: tuple):
         """The evaluation call ``method(*tensors, *statics...)`` through a recorded graph (see ``frame_replay``).  Returns None when
@@ -920,7 +921,8 @@ class EnvironmentModel(Tracked, nn.Module):
             # (raw pointers recorded: the workspace and the packed weights stay alive with the entry)
             entry = (signature, recorded, self.object_composer._workspace, [e[1] for e in self.object_composer._packed.values()],
                      self.object_composer.occupancy, self.object_composer.retained,
-                     [] if self.object_composer.retained is None else list(self.object_composer.retained._caches.values()))
+                     [] if self.object_composer.retained is None else list(self.object_composer.retained._caches.values()),
+                     self.object_composer._guide_scratch)
             self._replays[key] = entry
         if entry[1] is False:
             return None

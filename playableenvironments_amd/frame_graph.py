@@ -162,6 +162,7 @@ class FrameGraph:
         self._occupancy = composer.occupancy          # (the recorded launches read its bit tensors through raw pointers)
         self._retained = composer.retained            # (... and write the retained objects' caches)
         self._retained_caches = [] if composer.retained is None else list(composer.retained._caches.values())
+        self._guide_scratch = composer._guide_scratch   # (... and the keep bits of a fine guide)
         if composer._workspace is not self._workspace:
             raise RuntimeError("the composer re-allocated its workspace during the capture")
 
@@ -169,8 +170,9 @@ class FrameGraph:
         """Everything the captured launches baked in besides the input buffers: parameter storages and values, the
         arithmetic precision (selects the kernel and the packed layout), the sigma gate, the deferred projection, the annealing step of the ray benders
         (their octave weights are kernel arguments), the occupancy grid (its bit pointers are kernel arguments; with ``follow``
-        the recording also holds the grid's build launches) and the retained-object caches (``composer.retained``: setting,
-        swapping or clearing it changes the launch sequence)."""
+        the recording also holds the grid's build launches), the retained-object caches (``composer.retained``: setting,
+        swapping or clearing it changes the launch sequence) and the fine guide (``composer.fine_guide``: its mask, guard and
+        threshold are kernel arguments)."""
         composer = self.model.object_composer
         # state_epoch counts set_step / load_state_dict / .to() calls (reading the step buffers back would synchronise)
         owner = composer if self.mode == "scene_encodings" else self.model       # (observations: the encoders' weights too)
@@ -178,12 +180,13 @@ class FrameGraph:
                 bool(composer.gate_feature_head), bool(composer.defer_feature_projection), composer.state_epoch, composer.weights_epoch,
                 None if composer.object_entry_fields is None else tuple(composer.object_entry_fields),
                 None if composer.occupancy is None else composer.occupancy.signature(),
-                None if composer.retained is None else composer.retained.signature())
+                None if composer.retained is None else composer.retained.signature(),
+                None if composer.fine_guide is None else composer.fine_guide.signature())
 
     def render(self, scene: Dict[str, torch.Tensor]) -> Dict:
         """Copies the inputs into the captured buffers and replays the frame."""
         if self._signature() != self._weights_version:
-            raise RuntimeError("the composer's parameters, precision, annealing step, occupancy grid or retained objects changed since the frame was captured: "
+            raise RuntimeError("the composer's parameters, precision, annealing step, occupancy grid, retained objects or fine guide changed since the frame was captured: "
                                "build a new FrameGraph")
         for k in self.keys:
             src = scene[k]

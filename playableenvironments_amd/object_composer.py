@@ -19,7 +19,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from . import _lib, field_query, occupancy as _occupancy, retention as _retention
+from . import _lib, field_query, guidance as _guidance, occupancy as _occupancy, retention as _retention
 from .modules import OBJECT_MODEL_CLASSES, REGISTRATION_EPOCH as _REGISTRATION_EPOCH, ModuleList, RayBendingStyleNerfModel, Tracked, \
     tree_is_tracked
 
@@ -474,6 +474,12 @@ class ObjectComposer(Tracked, nn.Module):
         #: resampled or sent through the MLP again (``pr_render_forward_retained``; the device decides, results are bit-identical).
         #: Used on the calls the occupancy grid is used on; not by calls that are split along the rays.
         self.retained: Optional[_retention.Retained] = None
+        #: fine guide: ``None`` (default), or a ``guidance.FineGuide`` - the fine pass of the guided objects evaluates a merged sample
+        #: only where the coarse samples around it found density above the guide's threshold (``pr_render_forward_guided``); every
+        #: other sample is treated like a sample outside the box.  An approximation, only as good as the coarse model's agreement
+        #: with the fine one.  Handed to the calls the occupancy grid is handed to, never to ``forward_expected_positions``.
+        self.fine_guide: Optional[_guidance.FineGuide] = None
+        self._guide_scratch: Optional[torch.Tensor] = None      # the keep bits of a guided call, next to the workspace
         #: callables invoked by the autograd node of a differentiable call with the flat fp32 buffer that every parameter gradient
         #: of the call is a view of, right after ``pr_render_backward`` is enqueued (parallel.OverlappedGradientAllReduce starts the
         #: gradient all-reduce from here, so that it overlaps the rest of ``backward()``)
@@ -614,7 +620,7 @@ class ObjectComposer(Tracked, nn.Module):
         replicas' threads.  A replica lives for one call: it packs the broadcast weights it is given and never caches lists."""
         replica = super()._replicate_for_data_parallel()
         fresh = dict(occupancy=None, retained=None, gradient_hooks=[], _packed={}, _param_lists={}, _structs={}, _tracked={}, _annealing={}, _linspace={}, _workspace=None,
-                     _budget_ok=0, _pending_bn_check=None, last_normalised_samples={}, last_noise_seed=None)
+                     _guide_scratch=None, _budget_ok=0, _pending_bn_check=None, last_normalised_samples={}, last_noise_seed=None)
         replica.__dict__.update(fresh)
         # (the replica's backward pass reports parameter gradients to the ORIGINAL: its packed copies / recorded frames are what an
         # evaluation render outside the wrapper - model.module.render_full_frame_* - reads after the optimiser step)
@@ -625,7 +631,7 @@ class ObjectComposer(Tracked, nn.Module):
         # copy.deepcopy / pickle (EMA helpers, swa_utils.AveragedModel): the caches hold ctypes structures with raw pointers
         # (not picklable) and device scratch that a copy must not share
         state = dict(self.__dict__)
-        state.update(occupancy=None, retained=None, gradient_hooks=[], _packed={}, _param_lists={}, _structs={}, _tracked={}, _annealing={}, _linspace={}, _workspace=None, _budget_ok=0,
+        state.update(occupancy=None, retained=None, gradient_hooks=[], _packed={}, _param_lists={}, _structs={}, _tracked={}, _annealing={}, _linspace={}, _workspace=None, _guide_scratch=None, _budget_ok=0,
                      _pending_bn_check=None, last_normalised_samples={}, last_noise_seed=None, _host_step=None)
         state.pop("_replica_of", None)
         return state
@@ -640,6 +646,7 @@ class ObjectComposer(Tracked, nn.Module):
         self._annealing.clear()
         self._linspace.clear()
         self._workspace = None
+        self._guide_scratch = None
         self.state_epoch += 1
 
     def _apply(self, fn, *args, **kwargs):      # .to() / .cuda() / .float(): new storages, possibly at recycled addresses
@@ -983,6 +990,20 @@ class ObjectComposer(Tracked, nn.Module):
             r.check_occupancy(self.occupancy)       # (a grid too large for the cache's key is refused here, not inside the render)
         return r
 
+    # ------------------------------------------------------------------ fine guide
+    def _fine_guide_for_call(self, use_fine, perturb, save, object_ids, models_coarse) -> Optional[tuple]:
+        """``(FineGuide, guided objects)`` of an evaluation call, or None: the guide applies to the hierarchical calls the occupancy
+        grid applies to.  ``models_coarse``: the coarse model of every object instance of the call."""
+        g = self.fine_guide
+        if g is None or perturb or save or self.training or object_ids is not None or self.use_naive_mlp or torch.is_grad_enabled():
+            return None
+        if not isinstance(g, _guidance.FineGuide):
+            raise TypeError(f"ObjectComposer.fine_guide must be a guidance.FineGuide or None, got {type(g).__name__}")
+        g.check()
+        eligible = [k for k, m in enumerate(models_coarse) if use_fine and m.nerf_model.kind != 1]
+        ids = g.object_ids(eligible, len(models_coarse))
+        return (g, ids) if ids else None
+
     def _retained_weights_key(self, r: "_retention.Retained") -> tuple:
         """What the packed weights of the retained objects' models were made from - the key ``_packed_weights_many`` compares, per
         model, plus ``state_epoch`` (a replayed training graph moves the values on the device without moving the version counters
@@ -1281,6 +1302,7 @@ class ObjectComposer(Tracked, nn.Module):
 
         culled = self._occupancy_for_call(N, ids, use_fine, perturb, _save, _object_ids, sty, dfm, canonical_pose, dev)
         retained = self._retention_for_call(perturb, _save, _object_ids)
+        guided = self._fine_guide_for_call(use_fine, perturb, _save, _object_ids, models_c)
 
         # ---- ray chunking against the workspace budget -----------------------------------------
         def build_call(r0: int, r1: int):
@@ -1438,11 +1460,30 @@ class ObjectComposer(Tracked, nn.Module):
                     res["_samples"] = ex
                 outs[ty] = res
                 structs[ty] = o
+            rstruct = None
             if retained is not None:
                 key = (N, R, use_fine, int(call.precision), bool(self.defer_feature_projection), bool(self.gate_feature_head),
                        bool(canonical_pose), None if culled is None else self.occupancy.serial)
                 retained.weights_seen(self._retained_weights_key(retained))
                 rstruct = retained.call_struct(lib, call, objs, K, key, dev, stream)
+            if guided is not None:
+                # the keep bits of this piece (pieces run one after the other on the stream and share the scratch, like the workspace)
+                guide, guided_ids = guided
+                gstruct = _lib.FineGuide()
+                gstruct.object_mask = sum(1 << k for k in guided_ids)
+                gstruct.guard, gstruct.threshold = int(guide.guard), float(guide.threshold)
+                size = C.c_size_t()
+                _lib.check(lib.pr_fine_guide_size(C.byref(call), objs, gstruct.object_mask, C.byref(size)), "pr_fine_guide_size")
+                if self._guide_scratch is None or self._guide_scratch.numel() < size.value or self._guide_scratch.device != dev:
+                    self._guide_scratch = None
+                    self._guide_scratch = torch.empty(size.value, dtype=torch.uint8, device=dev)
+                gstruct.scratch, gstruct.scratch_bytes = self._guide_scratch.data_ptr(), self._guide_scratch.numel()
+                _lib.check(lib.pr_render_forward_guided(C.byref(call), objs, None if culled is None else C.byref(culled),
+                                                        None if rstruct is None else C.byref(rstruct), C.byref(gstruct),
+                                                        C.byref(structs["coarse"]), C.byref(structs["fine"]) if use_fine else None,
+                                                        workspace.data_ptr(), workspace.numel(), stream),
+                           "pr_render_forward_guided")
+            elif retained is not None:
                 _lib.check(lib.pr_render_forward_retained(C.byref(call), objs, None if culled is None else C.byref(culled),
                                                           C.byref(rstruct), C.byref(structs["coarse"]),
                                                           C.byref(structs["fine"]) if use_fine else None,
