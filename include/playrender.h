@@ -99,6 +99,16 @@ typedef enum pr_status {
                                        calls only - ignored with PR_FLAG_SAVE_FOR_BACKWARD, PR_FLAG_TRAIN_BN, PR_FLAG_SIGMOID_FEATURES
                                        (the sigmoid sits between the projection and the sum) and PR_FLAG_NAIVE_MLP.  Perturbed calls
                                        are eligible.  The workspace grows by the pooled rows (pr_workspace_size accounts for them). */
+#define PR_FLAG_GEOMETRY_ONLY 4096u  /* geometry-only render (depth, opacity, weights, object mattes): the MLP of every object and level stops
+                                       behind the density head (after the ray bender and the backbone), no feature row, pending stack or
+                                       pooled row exists, compositing ends behind the global weights and the scalar fields.  Every field
+                                       the call returns is bit for bit what the full render returns.  pr_workspace_size leaves out the
+                                       feature arena, the pending stacks and the pooled rows.  PR_FLAG_GATE_HEAD, PR_FLAG_DEFER_PROJECTION
+                                       and PR_FLAG_SIGMOID_FEATURES are ignored.  Honoured by every render entry point; refused
+                                       (PR_ERR_INVALID, before any device work): a non-NULL integrated_features pointer in any entry of
+                                       either level, decoder.groups > 0, PR_FLAG_TRAIN_BN, PR_FLAG_SAVE_FOR_BACKWARD, PR_FLAG_NAIVE_MLP, a
+                                       non-NULL pr_retained_t.  Perturbation, occupancy grids and the fine guide keep their rules.
+                                       head_samples is 0 for every object; skybox models (constant density) run no MLP launch. */
 #define PR_FLAG_DIVERGENCE_GRAD 256u /* pr_backward_workspace_size / pr_render_backward: gradients of integrated_divergence are
                                        given (pr_entry_grads_t.integrated_divergence); the backward pass then differentiates the
                                        Hutchinson estimate e^T (d delta / dx) e through the ray bender (the reference's double
@@ -404,6 +414,24 @@ int pr_fine_guide_size(const pr_call_t* call, const pr_object_t* objects, uint32
 int pr_render_forward_guided(const pr_call_t* call, const pr_object_t* objects, const pr_occupancy_t* occupancy,
                              const pr_retained_t* retained, const pr_fine_guide_t* guide, const pr_outputs_t* coarse,
                              const pr_outputs_t* fine, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * Geometry-only render (PR_FLAG_GEOMETRY_ONLY, required here: PR_ERR_INVALID without it): pr_render_forward_guided without a
+ * `retained` argument plus two optional per-level outputs (each pr_geometry_t pointer and each of its fields may be NULL):
+ *   visibility (N,R,K): visibility[n][r][k] = sum of the GLOBAL merged-list weights of the entries that belong to object k - the
+ *     object's alpha matte under occlusion; sum_k visibility = the global opacity up to fp32 association.  Samples the overlap fix
+ *     masked count for their object with weight 0.
+ *   front_object (N,R): the lowest k whose visibility is the ray's maximum, -1 when no visibility is > 0 (a NaN is never greater).
+ * Every fill is a kernel: the call can be recorded into a HIP graph.
+ */
+typedef struct pr_geometry_t {
+    float* visibility;      /* (N,R,K) or NULL */
+    int32_t* front_object;  /* (N,R) or NULL */
+} pr_geometry_t;
+int pr_render_geometry(const pr_call_t* call, const pr_object_t* objects, const pr_occupancy_t* occupancy,
+                       const pr_fine_guide_t* guide, const pr_outputs_t* coarse, const pr_outputs_t* fine,
+                       const pr_geometry_t* geometry_coarse, const pr_geometry_t* geometry_fine,
+                       void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * Builds occupancy bits from a density lattice: sigma (groups, cells[0] * s, cells[1] * s, cells[2] * s) with supersample factor

@@ -25,6 +25,7 @@ PR_FLAG_DEVICE_NOISE = 128
 PR_FLAG_DIVERGENCE_GRAD = 256
 PR_FLAG_SIGMOID_FEATURES = 512
 PR_FLAG_SPLIT_BACKWARD = 1024
+PR_FLAG_GEOMETRY_ONLY = 4096
 PR_PRECISION_FP32 = 0
 PR_PRECISION_F16X3 = 1
 PR_PRECISION_F16 = 2
@@ -177,6 +178,11 @@ class FineGuide(C.Structure):
                 ("scratch", C.c_void_p), ("scratch_bytes", C.c_size_t)]
 
 
+class Geometry(C.Structure):
+    """pr_geometry_t (include/playrender.h)."""
+    _fields_ = [("visibility", C.c_void_p), ("front_object", C.c_void_p)]
+
+
 # every exported symbol of include/playrender.h : (restype, argtypes)
 class SceneSetup(C.Structure):
     """pr_scene_setup_t (include/playrender.h)."""
@@ -208,6 +214,8 @@ SYMBOLS = {
     "pr_fine_guide_size": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.c_uint32, C.POINTER(C.c_size_t)]),
     "pr_render_forward_guided": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(Occupancy), C.POINTER(Retained),
                                            C.POINTER(FineGuide), C.POINTER(Outputs), C.POINTER(Outputs), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pr_render_geometry": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(Occupancy), C.POINTER(FineGuide), C.POINTER(Outputs),
+                                     C.POINTER(Outputs), C.POINTER(Geometry), C.POINTER(Geometry), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_occupancy_build": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p]),
     "pr_backward_workspace_size": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(C.c_size_t)]),
     "pr_render_backward": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(OutputGrads), C.POINTER(OutputGrads),

@@ -321,6 +321,32 @@ __global__ __launch_bounds__(64 * CW) void k_composite(CompositeParams p) {
     }
     __syncthreads();
 
+    // ---- geometry-only calls end here (PR_FLAG_GEOMETRY_ONLY; a parameter: uniform over the launch) -------------
+    // visibility[g][k] = the global weights of object k's entries summed (wg is indexed by concatenation index: the objects'
+    // offsets in concatenation order), in a fixed order; front_object = the lowest k that holds the ray's largest visibility,
+    // -1 when none is > 0 (a NaN is never greater)
+    if (p.geometry) {
+        if (p.visibility != nullptr || p.front_object != nullptr) {
+            float best = 0.f;
+            int front = -1;
+            int goff = 0;
+            for (int k = 0; k < p.objects; ++k) {
+                const int P = p.obj[k].positions;
+                float v = 0.f;
+                for (int i = tid; i < P; i += CT) v += sm.wg[goff + i];
+                v = block_sum<CW>(v, scratch, wave, lane);
+                if (tid == 0 && p.visibility != nullptr) as_global(p.visibility)[(size_t)g * p.objects + k] = v;
+                if (v > best) {
+                    best = v;
+                    front = k;
+                }
+                goff += P;
+            }
+            if (tid == 0 && p.front_object != nullptr) as_global(p.front_object)[g] = front;
+        }
+        return;
+    }
+
     // ---- features: one pass over the compact MLP rows --------------------------------------------
     // Per object the contributing samples (inside the box, non-zero weight) are compacted into per-wave lists (wave w
     // takes the w-th contiguous part of the object's samples; the sort keys are dead by now, their storage is reused),

@@ -906,6 +906,15 @@ __global__ __launch_bounds__(MLP_THREADS, MLP_BLOCKS_PER_CU) void k_mlp_mfma_gro
     PR_TRACE_MARK(4);
 }
 
+// geometry-only renders (PR_FLAG_GEOMETRY_ONLY): the objects of a model type, every tile ending behind the density head
+__global__ __launch_bounds__(MLP_THREADS, MLP_BLOCKS_PER_CU) void k_mlp_sigma_group(MlpParams j0, MlpParams j1, MlpParams j2, MlpParams j3,
+                                                                                    int count) {
+    mlp_tile_loop<false, true, false, true>(j0);
+    if (count > 1) mlp_tile_loop<false, true, false, true>(j1);
+    if (count > 2) mlp_tile_loop<false, true, false, true>(j2);
+    if (count > 3) mlp_tile_loop<false, true, false, true>(j3);
+}
+
 #ifdef PR_MLP_TRACE
 extern "C" int pr_debug_mlp_trace(unsigned long long* out) {
     (void)hipDeviceSynchronize();
@@ -1346,6 +1355,33 @@ int launch_mlp_group(const MlpParams* host_jobs, const int* max_rows, int count,
             fprintf(stderr, "\n");
         }
 #endif
+    }
+    return PR_OK;
+}
+
+// The density-only launch of several objects (geometry-only renders): slices of MLP_GROUP_MAX jobs, tiles claimed from the objects' counters
+int launch_mlp_sigma_group(const MlpParams* host_jobs, const int* max_rows, int count, hipStream_t s) {
+    PR_REQUIRE(count >= 1, "grouped density-only MLP launch: no jobs");
+    static thread_local MlpGroupParams g;     // 18 KB: not on the stack
+    for (int begin = 0; begin < count; begin += MLP_GROUP_MAX) {
+        const int n = count - begin < MLP_GROUP_MAX ? count - begin : MLP_GROUP_MAX;
+        long max_tiles = 0;
+        for (int j = 0; j < n; ++j) {
+            const MlpParams& q = host_jobs[begin + j];
+            PR_REQUIRE(q.phase == 0 && !q.gate && !q.split3 && q.tile_counter,
+                       "grouped density-only MLP launch: fused evaluation parameters without the gated head, with a tile counter");
+            max_tiles += ((long)max_rows[begin + j] + TILE_M - 1) / TILE_M;
+            g.jobs[j] = q;
+        }
+        if (max_tiles <= 0) continue;
+        int cu_count = 0;
+        PR_TRY(prepare_kernel(reinterpret_cast<const void*>(k_mlp_sigma_group), (int)sizeof(Smem), &cu_count));
+        int resident = cu_count * MLP_BLOCKS_PER_CU;
+        if (resident > MAX_RESIDENT_TILES) resident = MAX_RESIDENT_TILES;
+        const int grid = max_tiles < resident ? (int)max_tiles : resident;
+        ProfileScope scope(0, s);
+        hipLaunchKernelGGL(k_mlp_sigma_group, dim3(grid), dim3(MLP_THREADS), sizeof(Smem), s, g.jobs[0], g.jobs[1], g.jobs[2], g.jobs[3], n);
+        PR_LAUNCH_CHECK();
     }
     return PR_OK;
 }

@@ -679,6 +679,51 @@ __global__ __launch_bounds__(STHREADS, SBLOCKS_PER_CU) void k_mlp_split_sigma(Ml
     split_tile_loop<false, TERMS, true>(p);
 }
 
+// geometry-only renders (PR_FLAG_GEOMETRY_ONLY): the objects of a model type in one density-only launch
+__global__ __launch_bounds__(STHREADS, SBLOCKS_PER_CU) void k_mlp_split_sigma_group(MlpParams j0, MlpParams j1, MlpParams j2, MlpParams j3,
+                                                                                      int count) {
+    claim_matrix_priority();
+    split_tile_loop<true, 3, true>(j0);
+    if (count > 1) split_tile_loop<true, 3, true>(j1);
+    if (count > 2) split_tile_loop<true, 3, true>(j2);
+    if (count > 3) split_tile_loop<true, 3, true>(j3);
+}
+__global__ __launch_bounds__(STHREADS, SBLOCKS_PER_CU) void k_mlp_f16_sigma_group(MlpParams j0, MlpParams j1, MlpParams j2, MlpParams j3,
+                                                                                    int count) {
+    claim_matrix_priority();
+    split_tile_loop<true, 1, true>(j0);
+    if (count > 1) split_tile_loop<true, 1, true>(j1);
+    if (count > 2) split_tile_loop<true, 1, true>(j2);
+    if (count > 3) split_tile_loop<true, 1, true>(j3);
+}
+
+int launch_mlp_split_sigma_group(const MlpParams* host_jobs, const int* max_rows, int count, int terms, hipStream_t s) {
+    auto* const kernel = terms == 1 ? k_mlp_f16_sigma_group : k_mlp_split_sigma_group;
+    PR_REQUIRE(count >= 1, "grouped density-only MLP launch: no jobs");
+    static thread_local MlpGroupParams g;     // 18 KB: not on the stack
+    for (int begin = 0; begin < count; begin += MLP_GROUP_MAX) {
+        const int n = count - begin < MLP_GROUP_MAX ? count - begin : MLP_GROUP_MAX;
+        long max_tiles = 0;
+        for (int j = 0; j < n; ++j) {
+            const MlpParams& q = host_jobs[begin + j];
+            PR_REQUIRE(q.phase == 0 && !q.gate && q.tile_counter,
+                       "grouped density-only MLP launch: fused evaluation parameters without the gated head, with a tile counter");
+            max_tiles += ((long)max_rows[begin + j] + STILE_M - 1) / STILE_M;
+            g.jobs[j] = q;
+        }
+        if (max_tiles <= 0) continue;
+        int cu_count = 0;
+        PR_TRY(prepare_kernel(reinterpret_cast<const void*>(kernel), (int)sizeof(SmemH), &cu_count));
+        int resident = cu_count * SBLOCKS_PER_CU;
+        if (resident > MAX_RESIDENT_TILES) resident = MAX_RESIDENT_TILES;
+        const int grid = max_tiles < resident ? (int)max_tiles : resident;
+        ProfileScope scope(0, s);
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(STHREADS), sizeof(SmemH), s, g.jobs[0], g.jobs[1], g.jobs[2], g.jobs[3], n);
+        PR_LAUNCH_CHECK();
+    }
+    return PR_OK;
+}
+
 int launch_mlp_split_sigma(const MlpParams& p, int max_rows, int terms, hipStream_t s) {
     if (max_rows <= 0) return PR_OK;
     PR_REQUIRE(p.phase == 0 && !p.gate, "density-only MLP launch: fused evaluation parameters without the gated head only");

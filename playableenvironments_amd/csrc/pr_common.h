@@ -410,6 +410,21 @@ int launch_mlp_split_group(const MlpParams* host_jobs, const int* max_rows, int 
 // k_mlp_split_sigma<terms>; fused evaluation parameters (phase 0), gate == 0, p.feat is not written
 int launch_mlp_sigma(const MlpParams& p, int max_rows, hipStream_t s);
 int launch_mlp_split_sigma(const MlpParams& p, int max_rows, int terms, hipStream_t s);
+// the objects of a geometry-only render (PR_FLAG_GEOMETRY_ONLY) as one density-only launch: k_mlp_sigma_group /
+// k_mlp_split_sigma_group / k_mlp_f16_sigma_group, sliced and claimed like launch_mlp_group
+int launch_mlp_sigma_group(const MlpParams* host_jobs, const int* max_rows, int count, hipStream_t s);
+int launch_mlp_split_sigma_group(const MlpParams* host_jobs, const int* max_rows, int count, int terms, hipStream_t s);
+// the constant density of a skybox model (kind == 1) without an MLP launch: sigma = present ? 10 : empty_alpha wherever slot >= 0
+struct SkyboxSigmaParams {
+    long samples;                 // N * R * P
+    int samples_per_frame;        // R * P
+    const int32_t* slot;          // (N,R,P)
+    const uint8_t* in_scene;      // presence of THIS object in frame 0; frame n at in_scene + n * in_scene_stride
+    int in_scene_stride;
+    float empty_alpha;
+    float* sigma;                 // (N,R,P)
+};
+int launch_skybox_sigma(const SkyboxSigmaParams& p, hipStream_t s);
 
 // BatchNorm1d(affine=False) in training mode: batch mean / biased variance from the accumulated sums,
 // running statistics updated in place with momentum 0.1 and the unbiased variance, num_batches_tracked += 1
@@ -490,6 +505,11 @@ struct CompositeParams {
     int out_features;              // deferred projection: the real F of the models
     const float* proj_w[PR_MAX_OBJECTS];   // deferred projection: packed [W6 | b6] rows of object k's model, row stride proj_k
     int proj_k;
+    // geometry-only calls (PR_FLAG_GEOMETRY_ONLY): the kernel returns in front of the feature pass; before that it reduces the global
+    // weights per object into visibility (frames * rays, objects) and derives front_object (frames * rays) - either may be NULL
+    int geometry;
+    float* visibility;
+    int32_t* front_object;
 };
 int launch_composite(const CompositeParams& p, hipStream_t s);
 int launch_projection(const CompositeParams& p, hipStream_t s);

@@ -62,6 +62,28 @@ int launch_zero_fill(void* dst, size_t bytes, hipStream_t s) {
     return PR_OK;
 }
 
+// Geometry-only calls: the density of a skybox model is a constant, so its samples need no MLP launch - what the tile loop's
+// skybox branch writes (10 where the object is present, empty_alpha where it is not, for every sample that owns a compact row).
+__global__ __launch_bounds__(256) void k_skybox_sigma(SkyboxSigmaParams p) {
+    const PR_GLOBAL_AS int32_t* slot = as_global(p.slot);
+    const PR_GLOBAL_AS uint8_t* present = as_global(p.in_scene);
+    PR_GLOBAL_AS float* sigma = as_global(p.sigma);
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < p.samples; i += (long)gridDim.x * 256) {
+        if (slot[i] < 0) continue;
+        const long frame = i / p.samples_per_frame;
+        sigma[i] = present[(size_t)frame * p.in_scene_stride] ? 10.0f : p.empty_alpha;
+    }
+}
+
+int launch_skybox_sigma(const SkyboxSigmaParams& p, hipStream_t s) {
+    if (p.samples <= 0) return PR_OK;
+    long blocks = (p.samples + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(k_skybox_sigma, dim3((unsigned)blocks), dim3(256), 0, s, p);
+    PR_LAUNCH_CHECK();
+    return PR_OK;
+}
+
 ProfileScope::ProfileScope(int category, hipStream_t s) : category_(category), stream_(s), start_(nullptr), active_(false) {
     if (!g_profile_on.load(std::memory_order_relaxed)) return;
     if (hipEventCreate(&start_) != hipSuccess) return;
@@ -151,7 +173,7 @@ int validate_call(const pr_call_t& c, const pr_object_t* objs) {
 // The sigma-gated feature head applies to calls whose compositing weights are a function of the raw densities alone:
 // evaluation without perturbation noise, nothing saved for a backward pass, fused (unphased) MLP launches.
 bool gate_active(const pr_call_t& c) {
-    if (!(c.flags & PR_FLAG_GATE_HEAD)) return false;
+    if (!(c.flags & PR_FLAG_GATE_HEAD) || (c.flags & PR_FLAG_GEOMETRY_ONLY)) return false;      // (a geometry-only call has no head to gate)
     if (c.flags & (PR_FLAG_PERTURB | PR_FLAG_TRAIN_BN | PR_FLAG_SAVE_FOR_BACKWARD | PR_FLAG_NAIVE_MLP)) return false;
     for (int k = 0; k < c.objects; ++k)
         if (c.noise_coarse.integrate[k] || c.noise_fine.integrate[k]) return false;
@@ -164,7 +186,7 @@ bool gate_active(const pr_call_t& c) {
 // object model has the three-layer head (pr_object_model_t holds no other); the pooled rows of a ray have one width, so the models
 // of the call share layers_width.  Noise changes the weights only: perturbed calls are eligible.
 bool defer_active(const pr_call_t& c, const pr_object_t* objs) {
-    if (!(c.flags & PR_FLAG_DEFER_PROJECTION)) return false;
+    if (!(c.flags & PR_FLAG_DEFER_PROJECTION) || (c.flags & PR_FLAG_GEOMETRY_ONLY)) return false;   // (nor rows to project)
     if (c.flags & (PR_FLAG_SAVE_FOR_BACKWARD | PR_FLAG_TRAIN_BN | PR_FLAG_SIGMOID_FEATURES | PR_FLAG_NAIVE_MLP)) return false;
     if (c.precision != PR_PRECISION_FP32) return false;
     for (int k = 0; k < c.objects; ++k) {
@@ -217,7 +239,9 @@ int make_plan(const pr_call_t& c, const pr_object_t* objs, Plan* plan) {
             tp.dispmag[k] = m.has_bender ? take(sizeof(float) * cap) : (size_t)-1;
             tp.adain[k] = take(sizeof(float) * (size_t)c.frames * adain_row_floats(d));
             tp.feat[k] = feat_bytes[t];  // relative to the feature arena
-            feat_bytes[t] += align_up(sizeof(float) * cap * (defer_active(c, objs) ? hidden_row_floats(d.W2) : m.output_features));
+            // (a geometry-only call writes no feature row: no arena)
+            if (!(c.flags & PR_FLAG_GEOMETRY_ONLY))
+                feat_bytes[t] += align_up(sizeof(float) * cap * (defer_active(c, objs) ? hidden_row_floats(d.W2) : m.output_features));
             if (c.flags & PR_FLAG_SAVE_FOR_BACKWARD) {
                 // everything the backward pass re-reads, per object instance (compact rows, worst-case capacity)
                 SavedPlan& sv = tp.saved[k];
@@ -374,10 +398,12 @@ static int validate_guide(const pr_call_t& c, const pr_object_t* objs, const pr_
 }
 
 static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupancy_t* occupancy, const RetainCtx* rc,
-                  const pr_fine_guide_t* guide, const GuidePlan* gplan, const pr_outputs_t* outs[2], char* ws, const Plan& plan,
-                  hipStream_t s) {
+                  const pr_fine_guide_t* guide, const GuidePlan* gplan, const pr_outputs_t* outs[2], const pr_geometry_t* geos[2],
+                  char* ws, const Plan& plan, hipStream_t s) {
     const int ntypes = c.use_fine ? 2 : 1;
     const int K = c.objects;
+    // geometry-only call: density-only MLP launches (none for a skybox model), compositing ends behind the global weights
+    const bool geo = (c.flags & PR_FLAG_GEOMETRY_ONLY) != 0;
     // retention: the first launches compare the cached keys with this call's inputs and set the reuse flags
     if (rc) PR_TRY(launch_retain_probe(c, objs, *rc, s));
     int32_t* block_sums_all = reinterpret_cast<int32_t*>(ws + plan.block_sums);
@@ -396,6 +422,7 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
     MlpParams jobs[PR_MAX_OBJECTS];
     int job_rows[PR_MAX_OBJECTS];
     FoldParams fold_jobs[PR_MAX_OBJECTS];
+    int sigma_jobs = 0;          // geometry-only calls: the grouped jobs of a level (skybox models are left out), packed in object order
     // differentiable calls with several objects: phase 1 of every object (the whole network up to the first BatchNorm) runs as
     // one grouped launch too; what follows it per object (statistics, head phases, divergence) is deferred until after it
     const bool train_grouped = group_train_active(c);
@@ -415,6 +442,7 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
         PR_TRY(launch_zero_fill(ws + tp.zero_begin, tp.zero_bytes, s));
         const pr_noise_t& noise = t ? c.noise_fine : c.noise_coarse;
         int total_positions = 0;
+        sigma_jobs = 0;
         // what follows phase 1 of an object's phased launches (training / differentiable calls): batch statistics, the two head
         // phases, the divergence estimate
         // stage 1: statistics of phase 1 -> phase 2; stage 2: statistics of phase 2 -> phase 3; stage 3: counts, divergence.
@@ -615,7 +643,7 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
             mp.deformation = c.deformation + (size_t)k * m.deformation_features;
             mp.deformation_stride = K * m.deformation_features;
             mp.adain = adain; mp.adain_stride = fo.row_floats;
-            mp.sigma = sigma; mp.dispmag = dispmag; mp.feat = feat;
+            mp.sigma = sigma; mp.dispmag = dispmag; mp.feat = geo ? nullptr : feat;
             if (defer) {     // the kernels stop behind features_head.4 and write [h | 1] rows
                 mp.n_layers = mp.n_backbone + 2;
                 mp.F = hidden_row_floats(d.W2);
@@ -634,6 +662,28 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
             }
             const size_t cap = (size_t)c.frames * c.rays * P;
             const int max_tiles = (int)cap;   // rows: every launcher derives its own tile count
+            if (geo) {
+                // no AdaIN fold (the table feeds the feature head only); a skybox model's constant density needs no MLP launch
+                const int terms = c.precision == PR_PRECISION_F16 ? 1 : 3;
+                mp.adain = nullptr;
+                if (m.kind == 1) {
+                    SkyboxSigmaParams sp;
+                    memset(&sp, 0, sizeof(sp));
+                    sp.samples = (long)cap; sp.samples_per_frame = c.rays * P;
+                    sp.slot = slot; sp.in_scene = c.object_in_scene + k; sp.in_scene_stride = K;
+                    sp.empty_alpha = m.empty_space_alpha; sp.sigma = sigma;
+                    PR_TRY(launch_skybox_sigma(sp, s));
+                } else if (grouped) {
+                    jobs[sigma_jobs] = mp;
+                    job_rows[sigma_jobs] = max_tiles;
+                    ++sigma_jobs;
+                } else if (c.precision != PR_PRECISION_FP32) {
+                    PR_TRY(launch_mlp_split_sigma(mp, max_tiles, terms, s));
+                } else {
+                    PR_TRY(launch_mlp_sigma(mp, max_tiles, s));
+                }
+                continue;
+            }
             if (!(c.flags & (PR_FLAG_TRAIN_BN | PR_FLAG_SAVE_FOR_BACKWARD))) {
                 if (grouped) {
                     fold_jobs[k] = fo;       // folded and evaluated together once every object of the type is prepared
@@ -768,7 +818,14 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
             if (div_jobs) PR_TRY(launch_div_chain_group(dj, div_rows, div_jobs, s));
         }
 
-        if (grouped) {
+        if (geo) {
+            if (grouped && sigma_jobs > 0) {
+                if (c.precision != PR_PRECISION_FP32)
+                    PR_TRY(launch_mlp_split_sigma_group(jobs, job_rows, sigma_jobs, c.precision == PR_PRECISION_F16 ? 1 : 3, s));
+                else
+                    PR_TRY(launch_mlp_sigma_group(jobs, job_rows, sigma_jobs, s));
+            }
+        } else if (grouped) {
             if (rc) PR_TRY(launch_retain_gate(*rc, totals, 0, K, s));      // (behind the block scans of the level)
             PR_TRY(launch_adain_fold_group(fold_jobs, K, s));
             if (c.precision != PR_PRECISION_FP32)
@@ -811,7 +868,7 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
             o.divergence = ((c.flags & PR_FLAG_SAVE_FOR_BACKWARD) && m.has_bender)
                                ? reinterpret_cast<const float*>(ws + tp.saved[k].div) : nullptr;
             if (o.divergence) cp.any_divergence = 1;
-            o.feat = arr.feat;
+            o.feat = geo ? nullptr : arr.feat;
             o.noise = perturb_noise(noise.integrate[k], c, NOISE_INTEGRATE, t, k);
             o.positions = m.positions;
             if (out) o.out = out->object[k];
@@ -824,6 +881,14 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
             cp.out_features = cp.F;
             cp.F = hidden_row_floats(objs[0].coarse.layers_width / 2);
             cp.pooled = reinterpret_cast<float*>(ws + plan.pooled);
+        }
+        if (geo) {
+            cp.geometry = 1;
+            cp.sigmoid = 0;
+            if (geos[t]) {
+                cp.visibility = geos[t]->visibility;
+                cp.front_object = geos[t]->front_object;
+            }
         }
         PR_TRY(launch_composite(cp, s));
         if (defer) PR_TRY(launch_projection(cp, s));
@@ -842,7 +907,9 @@ static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupanc
             }
             if (out->evaluated_samples)
                 PR_CHECK_HIP(hipMemcpyAsync(out->evaluated_samples, totals, sizeof(int32_t) * K, hipMemcpyDeviceToDevice, s));
-            if (out->head_samples)   // without the gate every evaluated sample goes through the feature head
+            if (out->head_samples && geo)     // no sample goes through the feature head (a kernel fill: no memset node)
+                PR_TRY(launch_zero_fill(out->head_samples, sizeof(int32_t) * K, s));
+            else if (out->head_samples)   // without the gate every evaluated sample goes through the feature head
                 PR_CHECK_HIP(hipMemcpyAsync(out->head_samples, gate ? head_counts : totals, sizeof(int32_t) * K,
                                             hipMemcpyDeviceToDevice, s));
         }
@@ -892,12 +959,60 @@ extern "C" int pr_fine_guide_size(const pr_call_t* call, const pr_object_t* obje
     return PR_OK;
 }
 
+namespace pr {
+// Host checks of a geometry-only call (PR_FLAG_GEOMETRY_ONLY): no device work, so that a refusal precedes everything else.
+static int validate_geometry(const pr_call_t& c, const pr_retained_t* retained, const pr_outputs_t* coarse, const pr_outputs_t* fine) {
+    PR_REQUIRE(!(c.flags & PR_FLAG_TRAIN_BN), "a geometry-only call runs no feature head: PR_FLAG_TRAIN_BN is set (batch statistics need the head)");
+    PR_REQUIRE(!(c.flags & PR_FLAG_SAVE_FOR_BACKWARD), "a geometry-only call has no backward pass: PR_FLAG_SAVE_FOR_BACKWARD is set");
+    PR_REQUIRE(!(c.flags & PR_FLAG_NAIVE_MLP), "a geometry-only call is not supported with PR_FLAG_NAIVE_MLP");
+    PR_REQUIRE(retained == nullptr, "a geometry-only call cannot be retained: pr_retained_t is not NULL (the cache layout holds feature rows)");
+    const pr_outputs_t* levels[2] = {coarse, c.use_fine ? fine : nullptr};
+    for (int t = 0; t < 2; ++t) {
+        const pr_outputs_t* o = levels[t];
+        if (!o) continue;
+        const char* level = t ? "fine" : "coarse";
+        for (int k = 0; k < PR_MAX_OBJECTS; ++k)
+            PR_REQUIRE(o->object[k].integrated_features == nullptr,
+                       "a geometry-only call writes no features: integrated_features of object %d (%s) is not NULL", k, level);
+        PR_REQUIRE(o->global.integrated_features == nullptr,
+                   "a geometry-only call writes no features: integrated_features of the global entry (%s) is not NULL", level);
+        PR_REQUIRE(o->decoder.groups <= 0, "a geometry-only call writes no features: decoder.groups is %d (%s)", o->decoder.groups, level);
+    }
+    return PR_OK;
+}
+
+static int render_entry(const pr_call_t* call, const pr_object_t* objects, const pr_occupancy_t* occupancy, const pr_retained_t* retained,
+                        const pr_fine_guide_t* guide, const pr_outputs_t* coarse, const pr_outputs_t* fine,
+                        const pr_geometry_t* geometry_coarse, const pr_geometry_t* geometry_fine, void* workspace, size_t workspace_bytes,
+                        void* stream);
+}  // namespace pr
+
 extern "C" int pr_render_forward_guided(const pr_call_t* call, const pr_object_t* objects, const pr_occupancy_t* occupancy,
                                         const pr_retained_t* retained, const pr_fine_guide_t* guide, const pr_outputs_t* coarse,
                                         const pr_outputs_t* fine, void* workspace, size_t workspace_bytes, void* stream) {
+    return pr::render_entry(call, objects, occupancy, retained, guide, coarse, fine, nullptr, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int pr_render_geometry(const pr_call_t* call, const pr_object_t* objects, const pr_occupancy_t* occupancy,
+                                  const pr_fine_guide_t* guide, const pr_outputs_t* coarse, const pr_outputs_t* fine,
+                                  const pr_geometry_t* geometry_coarse, const pr_geometry_t* geometry_fine, void* workspace,
+                                  size_t workspace_bytes, void* stream) {
+    PR_REQUIRE(call && objects && workspace, "pr_render_geometry: NULL argument");
+    PR_REQUIRE(call->flags & PR_FLAG_GEOMETRY_ONLY, "pr_render_geometry needs PR_FLAG_GEOMETRY_ONLY in pr_call_t.flags");
+    return pr::render_entry(call, objects, occupancy, nullptr, guide, coarse, fine, geometry_coarse, geometry_fine, workspace,
+                            workspace_bytes, stream);
+}
+
+namespace pr {
+// Every render entry point ends here (geometry_* : the extras of pr_render_geometry, NULL elsewhere).
+static int render_entry(const pr_call_t* call, const pr_object_t* objects, const pr_occupancy_t* occupancy,
+                        const pr_retained_t* retained, const pr_fine_guide_t* guide, const pr_outputs_t* coarse,
+                        const pr_outputs_t* fine, const pr_geometry_t* geometry_coarse, const pr_geometry_t* geometry_fine,
+                        void* workspace, size_t workspace_bytes, void* stream) {
     PR_REQUIRE(call && objects && workspace, "pr_render_forward: NULL argument");
     PR_TRY(pr::validate_occupancy(*call, objects, occupancy));
     PR_TRY(pr::validate_call(*call, objects));
+    if (call->flags & PR_FLAG_GEOMETRY_ONLY) PR_TRY(pr::validate_geometry(*call, retained, coarse, fine));
     if (guide && guide->object_mask == 0) guide = nullptr;
     pr::GuidePlan gplan;
     if (guide) PR_TRY(pr::validate_guide(*call, objects, guide, &gplan));
@@ -911,9 +1026,11 @@ extern "C" int pr_render_forward_guided(const pr_call_t* call, const pr_object_t
     }
     PR_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
     const pr_outputs_t* outs[2] = {coarse, fine};
-    return pr::render(*call, objects, occupancy, retained ? &ctx : nullptr, guide, &gplan, outs, static_cast<char*>(workspace), plan,
+    const pr_geometry_t* geos[2] = {geometry_coarse, geometry_fine};
+    return pr::render(*call, objects, occupancy, retained ? &ctx : nullptr, guide, &gplan, outs, geos, static_cast<char*>(workspace), plan,
                       (hipStream_t)stream);
 }
+}  // namespace pr
 
 namespace pr {
 __global__ __launch_bounds__(256) void k_noise_fill(NoiseRef n, int normal, long count, float* out) {

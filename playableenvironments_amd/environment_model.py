@@ -1087,6 +1087,47 @@ class EnvironmentModel(Tracked, nn.Module):
         width = int(image_size[1] * upsample_factor)
         return self.fold_dictionary(flat, height, width)
 
+    def render_geometry_from_scene_encoding(self, camera_rotations, camera_translations, focals, image_size,
+                                            object_rotation_parameters_o2w, object_translation_parameters_o2w,
+                                            object_style, object_deformation, object_in_scene, upsample_factor: float = 1.0,
+                                            canonical_pose: bool = False) -> Dict:
+        """Depth, opacity, disparity and object mattes of every pixel of the frame, folded to (height, width): the scene set-up and
+        the full-frame rays of ``render_full_frame_from_scene_encoding``, then ONE ``ObjectComposer.render_geometry`` - no feature
+        head, no feature rows, no decoder.  Every field it shares with the full render is the same bits; the global entries gain
+        ``visibility`` (..., H, W, K) and ``front_object`` (..., H, W).  Evaluation mode, no gradients, always eager (the automatic
+        frame recordings do not cover it)."""
+        height = int(image_size[0] * upsample_factor)
+        width = int(image_size[1] * upsample_factor)
+        with torch.no_grad():
+            prepared = None
+            if self.fused_scene_setup:
+                prepared = self._scene_setup(camera_rotations, camera_translations, focals, object_rotation_parameters_o2w,
+                                             object_translation_parameters_o2w, object_style, object_deformation, object_in_scene,
+                                             height, width, upsample_factor)
+            key = (height, width, None, str(camera_rotations.device))
+            if key not in self._pixel_cache:
+                r = torch.arange(height * width, dtype=torch.int32)
+                self._pixel_cache[key] = ((r // width).to(device=camera_rotations.device, dtype=torch.int32).contiguous(),
+                                          (r % width).to(device=camera_rotations.device, dtype=torch.int32).contiguous())
+            rows, cols = self._pixel_cache[key]
+            lead = list(camera_rotations.shape[:-1])
+            if prepared is not None:
+                origins, directions, normals = _camera_rays_prepared(prepared["camera34"], prepared["render_focals"], lead, height,
+                                                                     width, rows, cols)
+                w2o = None
+            else:
+                rescaled_focals = focals * self.focal_length_multiplier
+                render_focals = rescaled_focals if upsample_factor == 1.0 else rescaled_focals * upsample_factor
+                c2w, _ = pose_matrices(camera_rotations, camera_translations)
+                w2o, _ = self.compute_transformation_matrix_w2o_o2w(object_rotation_parameters_o2w, object_translation_parameters_o2w)
+                origins, directions, normals = camera_rays(c2w, render_focals, height, width, rows, cols)
+            results = self.object_composer.render_geometry(origins, directions, normals, w2o, object_style.unsqueeze(-3),
+                                                           object_deformation.unsqueeze(-3), object_in_scene.unsqueeze(-2), False,
+                                                           canonical_pose=canonical_pose,
+                                                           _prepared=None if prepared is None else prepared["renderer"])
+            results = self.merge_dictionaries([results], dimension=directions.dim() - 2)
+        return self.fold_dictionary(results, height, width)
+
     # ------------------------------------------------------------------ observation-driven modes (injected encoders)
     def compute_rotation_translation_o2w(self, observations, transformation_matrix_w2c, camera_rotations, focals,
                                          bounding_boxes, bounding_boxes_validity):

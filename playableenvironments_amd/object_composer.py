@@ -437,6 +437,14 @@ class ObjectComposer(Tracked, nn.Module):
         #: the per-sample path by fp32 re-association, every other field is bit-identical.  Ignored (by the library) for training
         #: and differentiable calls, the f16x3 / f16 tiers, ``apply_activation`` and the scalar debugging kernel.
         self.defer_feature_projection = True
+        #: geometry-only route of ``forward_expected_positions`` (PR_FLAG_GEOMETRY_ONLY): in evaluation mode without a graph the
+        #: call reads weights, depths and displacements only, so it renders without the feature head - the same bits.  False: the
+        #: full render, as before (for comparisons).  Training mode and differentiable calls never take the route.
+        self.expected_positions_geometry = True
+        #: number of pr_render_geometry calls issued so far (tests and reports)
+        self.geometry_calls = 0
+        #: (bytes pr_workspace_size asked for, bytes of the workspace handed over) of the last geometry-only call
+        self.last_geometry_workspace = None
         #: device tensors (K,) per model type: samples that entered the BatchNorm batch statistics of the last training call
         self.last_normalised_samples: Dict[str, torch.Tensor] = {}
         #: where the random draws of perturbed / training calls come from when no explicit ``_noise`` is replayed:
@@ -1051,6 +1059,34 @@ class ObjectComposer(Tracked, nn.Module):
                                      object_in_scene, perturb, canonical_pose, _noise, _export, _decoder_layout, _prepared)
         raise RuntimeError("the HIP renderer needs device tensors (there is no CPU fallback)")
 
+    def render_geometry(self, ray_origins: torch.Tensor, ray_directions: torch.Tensor, focal_normals: torch.Tensor,
+                        transformation_matrix_w2o: torch.Tensor, style: torch.Tensor, deformation: torch.Tensor,
+                        object_in_scene: torch.Tensor, perturb: bool = False, *, canonical_pose: bool = False,
+                        _noise: Optional[dict] = None, _export: bool = False, _prepared: Optional[dict] = None) -> Dict:
+        """Geometry-only render (pr_render_geometry): depth, opacity, disparity, weights and displacement magnitudes of every
+        entry, bit for bit what ``forward`` returns, without running the feature head - the MLP of every object stops behind the
+        density head, no feature row is written or composited, skybox models run no MLP at all.
+
+        Takes the shapes of ``forward``; evaluation mode, device tensors, no gradients (the call runs under ``no_grad``).  Returns
+        the result dictionary of ``forward`` without any ``integrated_features`` / ``decoder_features``; the global entries gain
+        ``visibility`` (..., R, K) float32 - per object the sum of the global weights of its samples, its alpha matte under
+        occlusion - and ``front_object`` (..., R) int32 - the lowest object index with the largest visibility, -1 where nothing is
+        visible.  Packed weights, workspace budget with ray splitting, occupancy grids, the fine guide and the precision tiers work
+        as for ``forward``; retained objects are rendered like any other (geometry calls are never retained)."""
+        if not ray_directions.is_cuda:
+            raise RuntimeError("the HIP renderer needs device tensors (there is no CPU fallback)")
+        if self.training:
+            raise RuntimeError("render_geometry is an evaluation call: the module is in training mode (call .eval())")
+        K = self.object_id_helper.objects_count
+        if _prepared is None and transformation_matrix_w2o.size(-1) != K:
+            raise Exception(f"Transformation matrix must specifies transformations for"
+                            f"({transformation_matrix_w2o.size(-1)}) objects instead of ({K})")
+        self._raise_pending_batchnorm_check()
+        with torch.cuda.device(ray_directions.device), torch.no_grad():
+            return self._render(ray_origins, ray_directions, focal_normals, transformation_matrix_w2o, style, deformation,
+                                object_in_scene, perturb, canonical_pose, _noise, _export, False, None, None, _prepared=_prepared,
+                                _geometry=True)[0]
+
     def _forward(self, ray_origins, ray_directions, focal_normals, transformation_matrix_w2o, style, deformation,
                  object_in_scene, perturb, canonical_pose, _noise, _export, _decoder_layout=None, _prepared=None) -> Dict:
         K = self.object_id_helper.objects_count
@@ -1124,12 +1160,16 @@ class ObjectComposer(Tracked, nn.Module):
 
     def _render(self, ray_origins, ray_directions, focal_normals, transformation_matrix_w2o, style, deformation,
                 object_in_scene, perturb, canonical_pose=False, _noise=None, _export=False, _save=False, _object_ids=None,
-                _decoder_layout=None, _retry=False, _prepared=None):
+                _decoder_layout=None, _retry=False, _prepared=None, _geometry=False):
         """The renderer call proper.  Returns (results, state); ``state`` (only with ``_save``) keeps what
         pr_render_backward needs: the call structures, their tensors and the forward workspace.
         ``_object_ids``: render only these object instances (the tensors then carry ``len(_object_ids)`` objects);
-        used by forward_expected_positions."""
+        used by forward_expected_positions.  ``_geometry``: a geometry-only call (pr_render_geometry, evaluation without a graph):
+        no feature head, no ``integrated_features``; the global entries gain ``visibility`` and ``front_object``."""
         helper = self.object_id_helper
+        if _geometry and (_save or self.training or self.use_naive_mlp or _decoder_layout is not None):
+            raise RuntimeError("a geometry-only render is an evaluation call without a graph: not in training mode, not differentiable, "
+                               "not with the scalar debugging kernel and without a decoder layout")
         ids = list(range(helper.objects_count)) if _object_ids is None else list(_object_ids)
         K = len(ids)
 
@@ -1181,6 +1221,11 @@ class ObjectComposer(Tracked, nn.Module):
                 for k in range(K + 1):
                     P = counts[k] if k < K else sum(counts)
                     entry = {"integrated_features": torch.empty(lead + [R, F], **f32), "weights": torch.empty(lead + [R, P], **f32)}
+                    if _geometry:
+                        del entry["integrated_features"]
+                        if k == K:
+                            entry["visibility"] = torch.empty(lead + [R, K], **f32)
+                            entry["front_object"] = torch.empty(lead + [R], dtype=torch.int32, device=dev)
                     for key in ("opacity", "depth", "disparity", "integrated_displacements_magnitude", "integrated_divergence"):
                         entry[key] = torch.empty(lead + [R], **f32)
                     if k < K:
@@ -1241,6 +1286,8 @@ class ObjectComposer(Tracked, nn.Module):
             flags |= _lib.PR_FLAG_GATE_HEAD      # honoured by the library for unperturbed evaluation calls only
         if self.defer_feature_projection:
             flags |= _lib.PR_FLAG_DEFER_PROJECTION      # honoured by the library for fp32 evaluation calls without a sigmoid only
+        if _geometry:
+            flags |= _lib.PR_FLAG_GEOMETRY_ONLY         # (the three feature-head flags above are ignored with it)
 
         # ---- noise -----------------------------------------------------------------------------
         types = ["coarse"] + (["fine"] if use_fine else [])
@@ -1301,7 +1348,7 @@ class ObjectComposer(Tracked, nn.Module):
                 get(f"int_{ty}_global", (N, R, sum(ptot[ty])), True)
 
         culled = self._occupancy_for_call(N, ids, use_fine, perturb, _save, _object_ids, sty, dfm, canonical_pose, dev)
-        retained = self._retention_for_call(perturb, _save, _object_ids)
+        retained = None if _geometry else self._retention_for_call(perturb, _save, _object_ids)     # (geometry calls are never retained)
         guided = self._fine_guide_for_call(use_fine, perturb, _save, _object_ids, models_c)
 
         # ---- ray chunking against the workspace budget -----------------------------------------
@@ -1408,11 +1455,12 @@ class ObjectComposer(Tracked, nn.Module):
                         self._budget_ok = 0
                         return self._render(ray_origins, ray_directions, focal_normals, transformation_matrix_w2o, style,
                                             deformation, object_in_scene, perturb, canonical_pose, _noise, _export, _save,
-                                            _object_ids, _decoder_layout, _retry=True, _prepared=_prepared)
+                                            _object_ids, _decoder_layout, _retry=True, _prepared=_prepared, _geometry=_geometry)
                 workspace = self._workspace
             rc = r1 - r0
             outs = {}
             structs = {}
+            gstructs = {}
             for ty in types:
                 o = _lib.Outputs()
                 res = {}
@@ -1420,7 +1468,8 @@ class ObjectComposer(Tracked, nn.Module):
                     P = ptot[ty][k] if k < K else sum(ptot[ty])
                     shapes = {"integrated_features": (N, rc, F), "weights": (N, rc, P)}
                     wanted = ENTRY_KEYS if (k == K or object_fields is None) else object_fields
-                    e = {name: torch.empty(shapes.get(name, (N, rc)), **f32) for name in ENTRY_KEYS if name in wanted}
+                    e = {name: torch.empty(shapes.get(name, (N, rc)), **f32) for name in ENTRY_KEYS
+                         if name in wanted and not (_geometry and name == "integrated_features")}
                     entry = o.object[k] if k < K else o.global_
                     for name in e:       # (fields that are not wanted stay NULL: the compositing kernel skips them)
                         setattr(entry, name, e[name].data_ptr())
@@ -1458,6 +1507,12 @@ class ObjectComposer(Tracked, nn.Module):
                     ex["head_evaluated"] = torch.zeros((K,), dtype=torch.int32, device=dev)   # samples through the feature head
                     o.head_samples = ex["head_evaluated"].data_ptr()
                     res["_samples"] = ex
+                if _geometry:
+                    geo = _lib.Geometry()
+                    res["_visibility"] = torch.empty((N, rc, K), **f32)
+                    res["_front_object"] = torch.empty((N, rc), dtype=torch.int32, device=dev)
+                    geo.visibility, geo.front_object = res["_visibility"].data_ptr(), res["_front_object"].data_ptr()
+                    gstructs[ty] = geo
                 outs[ty] = res
                 structs[ty] = o
             rstruct = None
@@ -1466,6 +1521,7 @@ class ObjectComposer(Tracked, nn.Module):
                        bool(canonical_pose), None if culled is None else self.occupancy.serial)
                 retained.weights_seen(self._retained_weights_key(retained))
                 rstruct = retained.call_struct(lib, call, objs, K, key, dev, stream)
+            gstruct = None
             if guided is not None:
                 # the keep bits of this piece (pieces run one after the other on the stream and share the scratch, like the workspace)
                 guide, guided_ids = guided
@@ -1478,6 +1534,16 @@ class ObjectComposer(Tracked, nn.Module):
                     self._guide_scratch = None
                     self._guide_scratch = torch.empty(size.value, dtype=torch.uint8, device=dev)
                 gstruct.scratch, gstruct.scratch_bytes = self._guide_scratch.data_ptr(), self._guide_scratch.numel()
+            if _geometry:
+                self.geometry_calls += 1
+                self.last_geometry_workspace = (need, workspace.numel())
+                _lib.check(lib.pr_render_geometry(C.byref(call), objs, None if culled is None else C.byref(culled),
+                                                  None if gstruct is None else C.byref(gstruct), C.byref(structs["coarse"]),
+                                                  C.byref(structs["fine"]) if use_fine else None, C.byref(gstructs["coarse"]),
+                                                  C.byref(gstructs["fine"]) if use_fine else None,
+                                                  workspace.data_ptr(), workspace.numel(), stream),
+                           "pr_render_geometry")
+            elif guided is not None:
                 _lib.check(lib.pr_render_forward_guided(C.byref(call), objs, None if culled is None else C.byref(culled),
                                                         None if rstruct is None else C.byref(rstruct), C.byref(gstruct),
                                                         C.byref(structs["coarse"]), C.byref(structs["fine"]) if use_fine else None,
@@ -1541,6 +1607,11 @@ class ObjectComposer(Tracked, nn.Module):
                     entry[key] = t.reshape(lead + list(t.shape[1:]))
                 if name != "global":
                     entry["extra_outputs"] = {}
+                elif _geometry:
+                    for key in ("visibility", "front_object"):
+                        parts = [p[ty]["_" + key] for p in pieces]
+                        t = parts[0] if len(parts) == 1 else torch.cat(parts, dim=1)
+                        entry[key] = t.reshape(lead + list(t.shape[1:]))
                 results[ty][name] = entry
             if _export:
                 results[ty]["_samples"] = [p[ty]["_samples"] for p in pieces]
@@ -1593,7 +1664,8 @@ class ObjectComposer(Tracked, nn.Module):
         with torch.no_grad():
             results, _ = self._render(ray_origins, ray_directions, focal_normals, transformation_matrix_w2o.unsqueeze(-1),
                                       style.unsqueeze(-1), deformation.unsqueeze(-1), object_in_scene.unsqueeze(-1), perturb,
-                                      canonical_pose, noise, True, False, _object_ids=[object_id])
+                                      canonical_pose, noise, True, False, _object_ids=[object_id],
+                                      _geometry=bool(self.expected_positions_geometry) and not self.training and not self.use_naive_mlp)
             lib = _lib.load()
             dev = ray_directions.device
             stream = torch.cuda.current_stream(dev).cuda_stream
