@@ -443,6 +443,49 @@ int pr_occupancy_build(const float* sigma, int32_t groups, const int32_t* cells 
                        float threshold, int32_t dilate, uint32_t* bits, void* stream);
 
 /*
+ * Triangle meshes of density lattices: marching tetrahedra on the Freudenthal (Kuhn) split of every lattice cube - indexed,
+ * watertight inside the lattice, consistently oriented (triangle normals point from matter to empty space).
+ *   Lattice: sigma (G, nx, ny, nz), z fastest; point (i, j, k) sits at (axis[0][i], axis[1][j], axis[2][k]) - rectilinear, shared by
+ *     the groups, never computed with.  A point is INSIDE iff sigma > level (a NaN is never inside; a value equal to level is outside).
+ *   Edges: seven directions d = 0..6 leave a point: (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1).  An edge whose far end is
+ *     on the lattice CROSSES when exactly one end is inside; it then carries one vertex, from its lower end a and far end b in fp32
+ *     without contraction: t = (level - s_a) / (s_b - s_a); t = 0 unless t >= 0; t = 1 if t > 1; v = p_a + t (p_b - p_a) per axis.
+ *   Normals (optional): g = lattice gradient, per axis (s[i+1] - s[i-1]) / (x[i+1] - x[i-1]), one-sided at the two ends;
+ *     n = -(g_a + t (g_b - g_a)) divided by its fp32 length sqrt((n0 n0 + n1 n1) + n2 n2); (0,0,0) when the length is 0 or not finite.
+ *   Tetrahedra: six per cube, one per axis permutation p in lexicographic order, corners v0 = 0, v1 = e_p0, v2 = v1 + e_p1,
+ *     v3 = (1,1,1).  One corner alone on its side: one triangle; two and two: a quad as two triangles; orientation fixed per case.
+ *   Order: vertices by group, flat index of the lower end (i ny + j) nz + k, d; triangles by group, flat index of the cube origin,
+ *     tetrahedron, triangle of the case; indices are LOCAL to the group's vertex slice.
+ *   Degenerate on purpose: where lattice values equal `level` the vertices of several edges coincide and some triangles have zero
+ *     area; they are kept (the mesh stays topologically closed).  A surface that reaches the lattice border is open there.
+ * An element at or beyond its capacity is not written; the offsets always hold the true totals.  With vertices, normals and
+ * triangles all NULL the call only counts.
+ * Workspace bytes = the sum of these regions, each rounded up to 256 bytes, with P = nx ny nz and B = ceil(P / 256):
+ *   G P (crossing masks) + G P (triangle counts) + 4 G P (vertex bases) + 4 x 4 G B (block sums and their scans) + 8 (totals).
+ * Five kernel launches on `stream` (three when counting), no memset, no memcpy, no allocation, no synchronisation: capturable
+ * into a HIP graph.
+ */
+typedef struct pr_surface_t {
+    int32_t groups;              /* G >= 1 */
+    int32_t points[3];           /* lattice points per axis, each >= 2 */
+    float level;                 /* inside iff sigma > level; NaN refused */
+    uint32_t flags;              /* 0 */
+    const float* sigma;          /* (G, nx, ny, nz) */
+    const float* axis[3];        /* (nx) (ny) (nz) coordinates, shared by the groups */
+    int32_t max_vertices;        /* rows of vertices / normals, >= 0 */
+    int32_t max_triangles;       /* rows of triangles, >= 0 */
+    float* vertices;             /* (max_vertices, 3) or NULL */
+    float* normals;              /* (max_vertices, 3) or NULL; needs vertices */
+    int32_t* triangles;          /* (max_triangles, 3) or NULL; indices local to the group */
+    int32_t* vertex_offsets;     /* (G + 1), always written: group g owns [off[g], off[g+1]) */
+    int32_t* triangle_offsets;   /* (G + 1), always written */
+} pr_surface_t;
+/* Host computation, no device work.  12 G nx ny nz must stay below 2^31 (the counts are int32). */
+int pr_surface_workspace_size(const pr_surface_t* s, size_t* bytes);
+/* `workspace`: 256-byte aligned, pr_surface_workspace_size bytes. */
+int pr_extract_surface(const pr_surface_t* s, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Backward pass of pr_render_forward (what torch.autograd does for the reference's op graph when
  * training/trainer_backpropagated_autoencoder.py:349 calls total_loss.backward()).  The forward call must
  * have run with PR_FLAG_SAVE_FOR_BACKWARD (with or without PR_FLAG_TRAIN_BN) on the same `call`, `objects` and

@@ -10,14 +10,17 @@ Public surface (mirrors the reference's modules for the renderer hot path only):
   FrameGraph                a whole evaluation frame captured and replayed as one HIP graph
   geometry                  torch restatements of a geometry-only render's extra outputs (ObjectComposer.render_geometry,
                             EnvironmentModel.render_geometry_from_scene_encoding): per-object visibility, front object
+  surface, Mesh             triangle meshes of density lattices on the device (marching tetrahedra: surface.extract_surface,
+                            ObjectComposer.extract_mesh)
   ray_sampling, wire_format pixel / ray samplers and the renderer <-> decoder tensor glue of the reference
   parallel                  frame shards, overlapped feature all-gather, gradient all-reduce (torch.distributed / RCCL)
   configs / synthetic       shipped renderer configurations and seeded synthetic scenes
 """
-from . import batching, configs, encoders, geometry, parallel, ray_sampling, synthetic, wire_format  # noqa: F401
+from . import batching, configs, encoders, geometry, parallel, ray_sampling, surface, synthetic, wire_format  # noqa: F401
 from .environment_model import EnvironmentModel  # noqa: F401
 from .frame_graph import FrameGraph  # noqa: F401
 from .object_composer import ObjectComposer, ObjectIDsHelper  # noqa: F401
+from .surface import Mesh  # noqa: F401
 
 __all__ = ["ObjectComposer", "ObjectIDsHelper", "EnvironmentModel", "FrameGraph", "configs", "synthetic", "parallel",
-           "ray_sampling", "wire_format", "encoders", "batching", "geometry"]
+           "ray_sampling", "wire_format", "encoders", "batching", "geometry", "surface", "Mesh"]

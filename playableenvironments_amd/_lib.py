@@ -183,6 +183,13 @@ class Geometry(C.Structure):
     _fields_ = [("visibility", C.c_void_p), ("front_object", C.c_void_p)]
 
 
+class Surface(C.Structure):
+    """pr_surface_t (include/playrender.h)."""
+    _fields_ = [("groups", C.c_int32), ("points", C.c_int32 * 3), ("level", C.c_float), ("flags", C.c_uint32), ("sigma", C.c_void_p),
+                ("axis", C.c_void_p * 3), ("max_vertices", C.c_int32), ("max_triangles", C.c_int32), ("vertices", C.c_void_p),
+                ("normals", C.c_void_p), ("triangles", C.c_void_p), ("vertex_offsets", C.c_void_p), ("triangle_offsets", C.c_void_p)]
+
+
 # every exported symbol of include/playrender.h : (restype, argtypes)
 class SceneSetup(C.Structure):
     """pr_scene_setup_t (include/playrender.h)."""
@@ -217,6 +224,8 @@ SYMBOLS = {
     "pr_render_geometry": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(Occupancy), C.POINTER(FineGuide), C.POINTER(Outputs),
                                      C.POINTER(Outputs), C.POINTER(Geometry), C.POINTER(Geometry), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_occupancy_build": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p]),
+    "pr_surface_workspace_size": (C.c_int, [C.POINTER(Surface), C.POINTER(C.c_size_t)]),
+    "pr_extract_surface": (C.c_int, [C.POINTER(Surface), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_backward_workspace_size": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(C.c_size_t)]),
     "pr_render_backward": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(OutputGrads), C.POINTER(OutputGrads),
                                      C.POINTER(InputGrads), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),

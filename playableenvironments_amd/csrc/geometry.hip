@@ -44,32 +44,6 @@ __global__ void k_camera_rays(int frames, int rays, int per_frame, float half_h,
 }
 
 // ---------------------------------------------------------------------------------------------
-// Block-level helpers (256 threads)
-// ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ int wave_inclusive_scan(int v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int o = __shfl_up(v, d, 64);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
-// exclusive scan over the 256 threads of a block; `total` = block sum.  lds: >= 4 ints.
-__device__ __forceinline__ int block_exclusive_scan_256(int v, int* lds, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int inc = wave_inclusive_scan(v);
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += lds[w];
-    *total = lds[0] + lds[1] + lds[2] + lds[3];
-    __syncthreads();
-    return base + inc - v;
-}
-
-// ---------------------------------------------------------------------------------------------
 // Per-ray slab test, model/object_composer.py:104-151 + clamp :522-523
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ void ray_bounds(const ObjRay& ray, const float* lo, const float* hi, bool valid,
@@ -251,6 +225,22 @@ __global__ __launch_bounds__(256) void k_scan_blocks_group(ScanGroup g) {
 
 int launch_scan(const int32_t* sums, int32_t* offsets, int32_t* total, int n, hipStream_t s) {
     hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(256), 0, s, sums, offsets, total, n);
+    PR_LAUNCH_CHECK();
+    return PR_OK;
+}
+
+// `count` independent exclusive scans of n block sums each in one launch (a workgroup per array)
+int launch_scan_group(const int32_t* const* sums, int32_t* const* offsets, int32_t* const* totals, int count, int n, hipStream_t s) {
+    PR_REQUIRE(count >= 1 && count <= PR_MAX_OBJECTS, "scan group: %d arrays", count);
+    ScanGroup sg;
+    memset(&sg, 0, sizeof(sg));
+    for (int k = 0; k < count; ++k) {
+        sg.sums[k] = sums[k];
+        sg.offsets[k] = offsets[k];
+        sg.total[k] = totals[k];
+    }
+    sg.n = n;
+    hipLaunchKernelGGL(k_scan_blocks_group, dim3(count), dim3(256), 0, s, sg);
     PR_LAUNCH_CHECK();
     return PR_OK;
 }

@@ -356,6 +356,8 @@ int launch_placement_group(const PlaceParams* pp, const FillParams* fp, int32_t*
 
 // exclusive scan of n block sums (single workgroup), writes total to *total
 int launch_scan(const int32_t* sums, int32_t* offsets, int32_t* total, int n, hipStream_t s);
+// `count` (<= PR_MAX_OBJECTS) such scans of n block sums each, one workgroup per array (k_scan_blocks_group)
+int launch_scan_group(const int32_t* const* sums, int32_t* const* offsets, int32_t* const* totals, int count, int n, hipStream_t s);
 
 struct ResampleParams {
     int frames, rays, objects, object_index;
@@ -819,6 +821,32 @@ __device__ __forceinline__ float noise_normal(const NoiseRef& n, long g, int per
     const float u1 = (float)((x[0] >> 8) + 1u) * 5.9604644775390625e-8f;   // (0, 1]
     const float u2 = (float)(x[1] >> 8) * 5.9604644775390625e-8f;          // [0, 1)
     return sqrtf(-2.0f * logf(u1)) * cosf(6.2831853071795864769f * u2);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Block-level helpers (256 threads)
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int wave_inclusive_scan(int v) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int o = __shfl_up(v, d, 64);
+        if (lane >= d) v += o;
+    }
+    return v;
+}
+
+// exclusive scan over the 256 threads of a block; `total` = block sum.  lds: >= 4 ints.
+__device__ __forceinline__ int block_exclusive_scan_256(int v, int* lds, int* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int inc = wave_inclusive_scan(v);
+    if (lane == 63) lds[wave] = inc;
+    __syncthreads();
+    int base = 0;
+    for (int w = 0; w < wave; ++w) base += lds[w];
+    *total = lds[0] + lds[1] + lds[2] + lds[3];
+    __syncthreads();
+    return base + inc - v;
 }
 
 // torch.min / torch.max / clamp propagate NaN; fminf/fmaxf do not.

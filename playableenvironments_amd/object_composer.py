@@ -19,7 +19,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 import torch.nn as nn
 
-from . import _lib, field_query, guidance as _guidance, occupancy as _occupancy, retention as _retention
+from . import _lib, field_query, guidance as _guidance, occupancy as _occupancy, retention as _retention, surface as _surface
 from .modules import OBJECT_MODEL_CLASSES, REGISTRATION_EPOCH as _REGISTRATION_EPOCH, ModuleList, RayBendingStyleNerfModel, Tracked, \
     tree_is_tracked
 
@@ -878,10 +878,37 @@ class ObjectComposer(Tracked, nn.Module):
 
     def _grid_centres(self, object_idx: int, n, fine: bool, dev) -> torch.Tensor:
         """Voxel centres ``(nx, ny, nz, 3)`` of the box of object ``object_idx``'s model (``density_grid``, ``Occupancy.update``)."""
+        return torch.stack(torch.meshgrid(*self._grid_axes(object_idx, n, fine, dev), indexing="ij"), dim=-1)
+
+    def _grid_axes(self, object_idx: int, n, fine: bool, dev):
+        """The coordinates of the voxel centres along x, y, z: the three vectors ``_grid_centres`` is the product of."""
         model = self._occupancy_model(object_idx, "fine" if fine else "coarse")
         box = torch.as_tensor(model.model_config["bounding_box"], dtype=torch.float32, device=dev)
-        axes = [box[a, 0] + (torch.arange(n[a], dtype=torch.float32, device=dev) + 0.5) * ((box[a, 1] - box[a, 0]) / n[a]) for a in range(3)]
-        return torch.stack(torch.meshgrid(*axes, indexing="ij"), dim=-1)
+        return [box[a, 0] + (torch.arange(n[a], dtype=torch.float32, device=dev) + 0.5) * ((box[a, 1] - box[a, 0]) / n[a]) for a in range(3)]
+
+    def extract_mesh(self, object_idx: int, resolution, style: torch.Tensor, deformation: torch.Tensor, *, level: float,
+                     fine: bool = False, canonical_pose: bool = False, normals: bool = True, features: bool = False):
+        """Triangle meshes of the density field of object ``object_idx`` in its OBJECT frame: ``density_grid`` at the composer's
+        ``precision``, then ``surface.extract_surface`` (marching tetrahedra on the device) on the lattice of voxel centres.  One
+        ``surface.Mesh`` per row of ``style (G, S)`` / ``deformation (G, D)``.
+
+        ``level`` is a RAW-density threshold (matter is ``sigma > level``); it has no default: the right value belongs to the
+        checkpoint.  ``features=True`` adds the model's features at the vertices (one ``query_object`` over the vertices of all
+        groups; they lie inside the lattice of centres, hence inside the box).  ``Mesh.transformed`` takes a mesh to the world frame.
+        One host synchronisation (the mesh sizes).  Skybox models are refused, as by ``density_grid``."""
+        sigma, _ = self.density_grid(object_idx, resolution, style, deformation, fine=fine, canonical_pose=canonical_pose)
+        axes = self._grid_axes(object_idx, list(sigma.shape[1:]), fine, sigma.device)
+        meshes = _surface.extract_surface(sigma, axes, level, normals=normals)
+        if features:
+            # one query: the groups padded to the largest one (at least one row) with a lattice point, which is inside the box
+            G, most = len(meshes), max(1, max(m.vertices.size(0) for m in meshes))
+            points = torch.stack([axes[0][0], axes[1][0], axes[2][0]]).expand(G, most, 3).clone()
+            for g, m in enumerate(meshes):
+                points[g, :m.vertices.size(0)] = m.vertices
+            out = self.query_object(object_idx, points, style, deformation, fine=fine, canonical_pose=canonical_pose)["features"]
+            for g, m in enumerate(meshes):
+                m.features = out[g, :m.vertices.size(0)]
+        return meshes
 
     # ------------------------------------------------------------------ occupancy grids
     def _occupancy_model(self, object_idx: int, level: str):

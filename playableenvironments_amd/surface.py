@@ -1,0 +1,116 @@
+"""Triangle meshes of density lattices (``pr_extract_surface``, include/playrender.h): marching tetrahedra on the Freudenthal
+(Kuhn) split, on the device - what ``ObjectComposer.extract_mesh`` turns the output of ``density_grid`` into.
+
+``extract_surface`` takes a lattice ``sigma (G, nx, ny, nz)`` with the three coordinate vectors of its points and a raw-density
+``level`` and returns one ``Mesh`` per group: indexed, closed inside the lattice (a surface that reaches the lattice border is open
+there), triangle normals pointing from matter (``sigma > level``) to empty space.  Lattice values exactly equal to ``level`` count
+as outside and give coinciding vertices and zero-area triangles, which are kept.  The vertex and triangle order is fixed (header),
+so results can be compared bit for bit.  There is no CPU fallback.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+from typing import List, Optional, Sequence
+
+import torch
+
+from . import _lib
+from .field_query import NO_CPU
+
+
+@dataclass
+class Mesh:
+    """``vertices (V, 3)`` fp32, ``triangles (T, 3)`` int32 into them, ``normals (V, 3)`` unit vectors toward falling density (zero
+    rows where the lattice gradient vanishes or is not finite) or None, ``features (V, F)`` or None."""
+    vertices: torch.Tensor
+    triangles: torch.Tensor
+    normals: Optional[torch.Tensor] = None
+    features: Optional[torch.Tensor] = None
+
+    def transformed(self, matrix: torch.Tensor) -> "Mesh":
+        """A copy under the 4x4 (or 3x4) rigid transformation ``matrix`` (e.g. object-to-world): ``v' = R v + t``, normals are
+        rotated by ``R``; triangles and features are shared."""
+        m = torch.as_tensor(matrix, dtype=torch.float32, device=self.vertices.device)
+        if m.dim() != 2 or m.size(1) != 4 or m.size(0) not in (3, 4):
+            raise ValueError(f"matrix must be (4, 4) or (3, 4), got {list(m.shape)}")
+        rotation, translation = m[:3, :3], m[:3, 3]
+        normals = None if self.normals is None else self.normals @ rotation.T
+        return Mesh(self.vertices @ rotation.T + translation, self.triangles, normals, self.features)
+
+    def save_obj(self, path) -> None:
+        """Writes a Wavefront OBJ file: ``v`` lines, ``vn`` lines when the mesh has normals, ``f`` lines (1-based; ``a//a`` with
+        normals).  A plain host writer: the tensors are read back."""
+        v = self.vertices.detach().cpu().tolist()
+        n = None if self.normals is None else self.normals.detach().cpu().tolist()
+        with open(path, "w") as f:
+            f.write(f"# {len(v)} vertices, {self.triangles.size(0)} triangles\n")
+            f.writelines("v %.9g %.9g %.9g\n" % tuple(row) for row in v)
+            if n is not None:
+                f.writelines("vn %.9g %.9g %.9g\n" % tuple(row) for row in n)
+            for a, b, c in (self.triangles.detach().cpu() + 1).tolist():
+                f.write(f"f {a}//{a} {b}//{b} {c}//{c}\n" if n is not None else f"f {a} {b} {c}\n")
+
+
+def surface_struct(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float, vertex_offsets: torch.Tensor,
+                   triangle_offsets: torch.Tensor, vertices: Optional[torch.Tensor] = None, normals: Optional[torch.Tensor] = None,
+                   triangles: Optional[torch.Tensor] = None) -> _lib.Surface:
+    """``pr_surface_t`` over prepared tensors (fp32 / int32, contiguous, one device); the capacities are the outputs' rows."""
+    s = _lib.Surface()
+    s.groups = sigma.size(0)
+    for a in range(3):
+        s.points[a] = sigma.size(1 + a)
+        s.axis[a] = axes[a].data_ptr()
+    s.level = float(level)
+    s.sigma = sigma.data_ptr()
+    s.max_vertices = 0 if vertices is None else vertices.size(0)
+    s.max_triangles = 0 if triangles is None else triangles.size(0)
+    s.vertices = None if vertices is None else vertices.data_ptr()
+    s.normals = None if normals is None else normals.data_ptr()
+    s.triangles = None if triangles is None else triangles.data_ptr()
+    s.vertex_offsets = vertex_offsets.data_ptr()
+    s.triangle_offsets = triangle_offsets.data_ptr()
+    return s
+
+
+def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float, *, normals: bool = True) -> List[Mesh]:
+    """Meshes of the level set ``sigma = level`` of ``sigma (G, nx, ny, nz)`` (device tensor, z fastest - what ``density_grid``
+    returns); ``axes``: the coordinates of the lattice points along x, y, z (``nx``, ``ny``, ``nz`` values).  Returns G meshes.
+
+    Two calls on the current stream: a count-only one, then - after reading the two totals back, the ONE host synchronisation of
+    this function - an emitting one into exactly sized tensors."""
+    if not sigma.is_cuda:
+        raise RuntimeError(NO_CPU)
+    if sigma.dim() != 4:
+        raise ValueError(f"sigma must be (G, nx, ny, nz), got {list(sigma.shape)}")
+    if len(axes) != 3:
+        raise ValueError("axes must be the three coordinate vectors of the lattice")
+    dev = sigma.device
+    sigma = sigma.detach().to(torch.float32).contiguous()
+    axes = [torch.as_tensor(a).detach().to(device=dev, dtype=torch.float32).contiguous() for a in axes]
+    for a in range(3):
+        if axes[a].dim() != 1 or axes[a].numel() != sigma.size(1 + a):
+            raise ValueError(f"axes[{a}] must hold {sigma.size(1 + a)} coordinates, got {list(axes[a].shape)}")
+    G = sigma.size(0)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        offsets = torch.empty((2, G + 1), dtype=torch.int32, device=dev)
+        count = surface_struct(sigma, axes, level, offsets[0], offsets[1])
+        size = C.c_size_t()
+        _lib.check(lib.pr_surface_workspace_size(C.byref(count), C.byref(size)), "pr_surface_workspace_size")
+        workspace = torch.empty(size.value, dtype=torch.uint8, device=dev)
+        _lib.check(lib.pr_extract_surface(C.byref(count), workspace.data_ptr(), size.value, stream), "pr_extract_surface")
+        vertex_offsets, triangle_offsets = offsets.cpu().tolist()           # (the host synchronisation)
+        V, T = vertex_offsets[G], triangle_offsets[G]
+        vertices = torch.empty((V, 3), dtype=torch.float32, device=dev)
+        vertex_normals = torch.empty((V, 3), dtype=torch.float32, device=dev) if normals else None
+        triangles = torch.empty((T, 3), dtype=torch.int32, device=dev)
+        if V > 0:
+            emit = surface_struct(sigma, axes, level, offsets[0], offsets[1], vertices, vertex_normals, triangles)
+            _lib.check(lib.pr_extract_surface(C.byref(emit), workspace.data_ptr(), size.value, stream), "pr_extract_surface")
+    meshes = []
+    for g in range(G):
+        v0, v1, t0, t1 = vertex_offsets[g], vertex_offsets[g + 1], triangle_offsets[g], triangle_offsets[g + 1]
+        meshes.append(Mesh(vertices[v0:v1], triangles[t0:t1], vertex_normals[v0:v1] if normals else None))
+    return meshes
