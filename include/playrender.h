@@ -486,6 +486,61 @@ int pr_surface_workspace_size(const pr_surface_t* s, size_t* bytes);
 int pr_extract_surface(const pr_surface_t* s, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Connected components of density lattices: labels, sizes, and a lattice with the unwanted components blanked out - floater removal
+ * and capping in front of pr_extract_surface and pr_occupancy_build.
+ *   Lattice: sigma (G, nx, ny, nz), z fastest, each extent >= 1; the flat index of a point inside its group is p = (i ny + j) nz + k.
+ *   Inside: a point is INSIDE iff sigma > level - the comparison of pr_extract_surface and pr_occupancy_build (a NaN is never inside;
+ *     a value equal to level is outside).  With PR_COMPONENTS_CLOSE_BORDER a point with any index equal to 0 or to its extent - 1 is
+ *     outside, whatever its value.
+ *   Connectivity: two inside points are adjacent iff they differ by plus or minus one of the seven edge directions of
+ *     pr_extract_surface: (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1) - 14 neighbours, deliberately not symmetric under
+ *     reflection: (0,0,0) and (1,1,0) are adjacent, (1,0,0) and (0,1,0) are not.  These are exactly the edges that carry mesh vertices:
+ *     two points of different components never share a mesh edge, so removing a component removes its triangles and moves no vertex
+ *     of any other component.
+ *   Label: of an inside point the smallest flat index p of its component (local to the group), of an outside point -1: independent
+ *     of the execution order.  Size: the number of points of the component.
+ *   Selection: min_points >= 0 and keep_largest in [0, PR_COMPONENTS_MAX_KEEP], 0 = off.  The components of a group are ranked by
+ *     size descending, ties by label ascending; a component is KEPT iff size >= min_points and (keep_largest == 0 or
+ *     rank < keep_largest).  The cap of 8 is a design limit: every rank is one kernel launch, the cap bounds the launch count.
+ *   Outputs - any pointer may be NULL except counts:
+ *     labels (G, nx, ny, nz) int32;
+ *     sizes (G, nx, ny, nz) int32: at every inside point the size of its component, 0 outside;
+ *     sigma_out (G, nx, ny, nz): `fill` at every inside point of a component that is not kept and, with CLOSE_BORDER, at every border
+ *       point whose value is > level; everywhere else the input value bit for bit (NaN payloads included).  sigma_out == sigma (in
+ *       place) is allowed, a partial overlap is refused.  fill <= level is required (a NaN fill is refused);
+ *     counts (G, 4) int32, always written: inside points, components, kept components, kept points.
+ * Workspace bytes = the sum of these regions, each rounded up to 256 bytes, with P = nx ny nz:
+ *   4 G P (parents, then labels) + 4 G P (sizes) + 64 G (the keys of the eight largest components).
+ * 4 + keep_largest kernel launches on `stream` (initialise, merge, flatten and measure, one selection pass per rank, write), no memset,
+ * no memcpy, no allocation, no synchronisation: capturable into a HIP graph.  Integer atomics only: the outputs are deterministic.
+ * No kernel ever waits for the progress of another lane (csrc/components.hip, TERMINATION).
+ * Refused (PR_ERR_INVALID, before any device work): NULL sigma or counts, groups < 1, an extent < 1, a NaN level, unknown flag bits,
+ * keep_largest outside [0, 8], min_points < 0, with sigma_out a NaN fill or fill > level or a partial overlap with sigma,
+ * G nx ny nz >= 2^31, a misaligned or too small workspace.
+ */
+#define PR_COMPONENTS_CLOSE_BORDER 1u
+#define PR_COMPONENTS_MAX_KEEP 8
+typedef struct pr_components_t {
+    int32_t groups;              /* G >= 1 */
+    int32_t points[3];           /* lattice points per axis, each >= 1 */
+    float level;                 /* inside iff sigma > level; NaN refused */
+    uint32_t flags;              /* PR_COMPONENTS_CLOSE_BORDER or 0 */
+    int32_t min_points;          /* >= 0; 0 = off */
+    int32_t keep_largest;        /* 0 .. PR_COMPONENTS_MAX_KEEP; 0 = off */
+    float fill;                  /* written to blanked points of sigma_out; <= level */
+    uint32_t reserved_;
+    const float* sigma;          /* (G, nx, ny, nz) */
+    int32_t* labels;             /* (G, nx, ny, nz) or NULL */
+    int32_t* sizes;              /* (G, nx, ny, nz) or NULL */
+    float* sigma_out;            /* (G, nx, ny, nz) or NULL; may be sigma itself */
+    int32_t* counts;             /* (G, 4), always written */
+} pr_components_t;
+/* Host computation, no device work; refuses everything above that does not concern the workspace. */
+int pr_components_workspace_size(const pr_components_t* c, size_t* bytes);
+/* `workspace`: 256-byte aligned, pr_components_workspace_size bytes. */
+int pr_label_components(const pr_components_t* c, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Backward pass of pr_render_forward (what torch.autograd does for the reference's op graph when
  * training/trainer_backpropagated_autoencoder.py:349 calls total_loss.backward()).  The forward call must
  * have run with PR_FLAG_SAVE_FOR_BACKWARD (with or without PR_FLAG_TRAIN_BN) on the same `call`, `objects` and

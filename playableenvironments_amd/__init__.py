@@ -11,7 +11,8 @@ Public surface (mirrors the reference's modules for the renderer hot path only):
   geometry                  torch restatements of a geometry-only render's extra outputs (ObjectComposer.render_geometry,
                             EnvironmentModel.render_geometry_from_scene_encoding): per-object visibility, front object
   surface, Mesh             triangle meshes of density lattices on the device (marching tetrahedra: surface.extract_surface,
-                            ObjectComposer.extract_mesh)
+                            ObjectComposer.extract_mesh), with floater removal and capping on the same lattice
+                            (surface.label_components, surface.clean_lattice)
   ray_sampling, wire_format pixel / ray samplers and the renderer <-> decoder tensor glue of the reference
   parallel                  frame shards, overlapped feature all-gather, gradient all-reduce (torch.distributed / RCCL)
   configs / synthetic       shipped renderer configurations and seeded synthetic scenes
@@ -20,7 +21,8 @@ from . import batching, configs, encoders, geometry, parallel, ray_sampling, sur
 from .environment_model import EnvironmentModel  # noqa: F401
 from .frame_graph import FrameGraph  # noqa: F401
 from .object_composer import ObjectComposer, ObjectIDsHelper  # noqa: F401
-from .surface import Mesh  # noqa: F401
+from .surface import Mesh, clean_lattice, label_components  # noqa: F401
 
 __all__ = ["ObjectComposer", "ObjectIDsHelper", "EnvironmentModel", "FrameGraph", "configs", "synthetic", "parallel",
-           "ray_sampling", "wire_format", "encoders", "batching", "geometry", "surface", "Mesh"]
+           "ray_sampling", "wire_format", "encoders", "batching", "geometry", "surface", "Mesh", "label_components",
+           "clean_lattice"]

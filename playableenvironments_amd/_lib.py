@@ -190,6 +190,17 @@ class Surface(C.Structure):
                 ("normals", C.c_void_p), ("triangles", C.c_void_p), ("vertex_offsets", C.c_void_p), ("triangle_offsets", C.c_void_p)]
 
 
+COMPONENTS_CLOSE_BORDER = 1      # PR_COMPONENTS_CLOSE_BORDER
+COMPONENTS_MAX_KEEP = 8          # PR_COMPONENTS_MAX_KEEP
+
+
+class Components(C.Structure):
+    """pr_components_t (include/playrender.h)."""
+    _fields_ = [("groups", C.c_int32), ("points", C.c_int32 * 3), ("level", C.c_float), ("flags", C.c_uint32), ("min_points", C.c_int32),
+                ("keep_largest", C.c_int32), ("fill", C.c_float), ("reserved_", C.c_uint32), ("sigma", C.c_void_p), ("labels", C.c_void_p),
+                ("sizes", C.c_void_p), ("sigma_out", C.c_void_p), ("counts", C.c_void_p)]
+
+
 # every exported symbol of include/playrender.h : (restype, argtypes)
 class SceneSetup(C.Structure):
     """pr_scene_setup_t (include/playrender.h)."""
@@ -226,6 +237,8 @@ SYMBOLS = {
     "pr_occupancy_build": (C.c_int, [C.c_void_p, C.c_int32, c_int32_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p, C.c_void_p]),
     "pr_surface_workspace_size": (C.c_int, [C.POINTER(Surface), C.POINTER(C.c_size_t)]),
     "pr_extract_surface": (C.c_int, [C.POINTER(Surface), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pr_components_workspace_size": (C.c_int, [C.POINTER(Components), C.POINTER(C.c_size_t)]),
+    "pr_label_components": (C.c_int, [C.POINTER(Components), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_backward_workspace_size": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(C.c_size_t)]),
     "pr_render_backward": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(OutputGrads), C.POINTER(OutputGrads),
                                      C.POINTER(InputGrads), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),

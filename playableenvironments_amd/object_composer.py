@@ -887,7 +887,8 @@ class ObjectComposer(Tracked, nn.Module):
         return [box[a, 0] + (torch.arange(n[a], dtype=torch.float32, device=dev) + 0.5) * ((box[a, 1] - box[a, 0]) / n[a]) for a in range(3)]
 
     def extract_mesh(self, object_idx: int, resolution, style: torch.Tensor, deformation: torch.Tensor, *, level: float,
-                     fine: bool = False, canonical_pose: bool = False, normals: bool = True, features: bool = False):
+                     fine: bool = False, canonical_pose: bool = False, normals: bool = True, features: bool = False,
+                     keep_largest: int = 0, min_points: int = 0, close_border: bool = False):
         """Triangle meshes of the density field of object ``object_idx`` in its OBJECT frame: ``density_grid`` at the composer's
         ``precision``, then ``surface.extract_surface`` (marching tetrahedra on the device) on the lattice of voxel centres.  One
         ``surface.Mesh`` per row of ``style (G, S)`` / ``deformation (G, D)``.
@@ -895,10 +896,14 @@ class ObjectComposer(Tracked, nn.Module):
         ``level`` is a RAW-density threshold (matter is ``sigma > level``); it has no default: the right value belongs to the
         checkpoint.  ``features=True`` adds the model's features at the vertices (one ``query_object`` over the vertices of all
         groups; they lie inside the lattice of centres, hence inside the box).  ``Mesh.transformed`` takes a mesh to the world frame.
-        One host synchronisation (the mesh sizes).  Skybox models are refused, as by ``density_grid``."""
+        One host synchronisation (the mesh sizes).  Skybox models are refused, as by ``density_grid``.
+
+        ``keep_largest`` / ``min_points`` / ``close_border`` are ``surface.extract_surface``'s: the lattice is cleaned of floaters and
+        capped at the box before it is meshed (``surface.clean_lattice``); at their defaults nothing changes."""
         sigma, _ = self.density_grid(object_idx, resolution, style, deformation, fine=fine, canonical_pose=canonical_pose)
         axes = self._grid_axes(object_idx, list(sigma.shape[1:]), fine, sigma.device)
-        meshes = _surface.extract_surface(sigma, axes, level, normals=normals)
+        meshes = _surface.extract_surface(sigma, axes, level, normals=normals, keep_largest=keep_largest, min_points=min_points,
+                                          close_border=close_border)
         if features:
             # one query: the groups padded to the largest one (at least one row) with a lattice point, which is inside the box
             G, most = len(meshes), max(1, max(m.vertices.size(0) for m in meshes))
@@ -934,17 +939,24 @@ class ObjectComposer(Tracked, nn.Module):
         return _occupancy.LEVELS if fine is not None else _occupancy.LEVELS[:1]
 
     def build_occupancy(self, style: torch.Tensor, deformation: torch.Tensor, *, resolution=32, supersample: int = 2,
-                        threshold: float = 0.0, dilate: int = 1, objects=None, canonical_pose: bool = False) -> "_occupancy.Occupancy":
+                        threshold: float = 0.0, dilate: int = 1, objects=None, canonical_pose: bool = False, keep_largest: int = 0,
+                        min_points: int = 0) -> "_occupancy.Occupancy":
         """Occupancy grids from the objects' own density fields, for ``composer.occupancy = ...``.  ``style (..., S, K)`` /
         ``deformation (..., D, K)`` in ``forward``'s layout (one grid per frame of the leading dimensions).  For every chosen
         object (``objects=None``: every object that is not a skybox), every frame, the coarse model and - where there is one - the
         fine model: ``density_grid`` at ``resolution * supersample`` points per axis, then ``pr_occupancy_build``: a cell is occupied
         iff any of its ``supersample ** 3`` lattice values is ``> threshold``, and the occupied set is grown by ``dilate`` cells.
         A lattice samples the field: structure thinner than a lattice step can be missed (``dilate`` and ``supersample`` are the
-        margins).  Evaluation mode, under ``torch.no_grad()``."""
+        margins).  Evaluation mode, under ``torch.no_grad()``.
+
+        ``keep_largest`` (0..8) / ``min_points``: every density lattice first loses the components of ``sigma > threshold`` that are
+        not kept (``surface.clean_lattice`` with ``level = fill = threshold``): floaters stop costing MLP work and disappear from
+        culled renders.  At their defaults the grids are today's, bit for bit."""
         n = _occupancy._cells_of(resolution)
         if int(supersample) < 1 or int(dilate) < 0:
             raise ValueError(f"supersample must be >= 1 and dilate >= 0, got {supersample} / {dilate}")
+        if not 0 <= int(keep_largest) <= 8 or int(min_points) < 0:
+            raise ValueError(f"keep_largest must be in 0..8 and min_points >= 0, got {keep_largest} / {min_points}")
         helper = self.object_id_helper
         if objects is None:
             chosen = [k for k in range(helper.objects_count)
@@ -965,7 +977,8 @@ class ObjectComposer(Tracked, nn.Module):
             for level in self._occupancy_levels(k):
                 grids[(k, level)] = {"bits": torch.empty((frames, _occupancy.words_of(n)), dtype=torch.int32, device=dev), "cells": n}
         occ = _occupancy.Occupancy(self, frames, grids, build=dict(resolution=n, supersample=int(supersample), threshold=float(threshold),
-                                                                   dilate=int(dilate), canonical_pose=bool(canonical_pose)))
+                                                                   dilate=int(dilate), canonical_pose=bool(canonical_pose),
+                                                                   keep_largest=int(keep_largest), min_points=int(min_points)))
         return occ.update(style, deformation)
 
     def occupancy_from_mask(self, masks: Dict) -> "_occupancy.Occupancy":

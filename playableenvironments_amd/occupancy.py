@@ -17,7 +17,7 @@ from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, surface
 
 LEVELS = ("coarse", "fine")
 _SERIAL = itertools.count(1)
@@ -98,7 +98,7 @@ class Occupancy:
         self._composer = composer
         self.frames = int(frames)
         self.grids = grids
-        self.build = build            # resolution / supersample / threshold / dilate / canonical_pose, or None (from masks)
+        self.build = build            # resolution / supersample / threshold / dilate / canonical_pose / keep_largest / min_points, or None (from masks)
         self.follow = False
         self.serial = next(_SERIAL)   # identity of the grid in the signatures of recorded frames
         self._centres: Dict = {}
@@ -163,6 +163,9 @@ class Occupancy:
                 with torch.cuda.device(dev):
                     sigma = composer.query_object(k, centres.expand(self.frames, -1, 3), style_nks[:, k], deformation_nkd[:, k],
                                                   fine=level == "fine", canonical_pose=canonical, features=False)["sigma"]
+                    if b.get("keep_largest", 0) or b.get("min_points", 0):          # floaters leave the lattice before the bits are made
+                        sigma, _ = surface.clean_lattice(sigma.reshape([self.frames] + n), float(b["threshold"]),
+                                                         keep_largest=b.get("keep_largest", 0), min_points=b.get("min_points", 0))
                     cells = (C.c_int32 * 3)(*g["cells"])
                     _lib.check(lib.pr_occupancy_build(sigma.data_ptr(), self.frames, cells, b["supersample"], float(b["threshold"]),
                                                       int(b["dilate"]), g["bits"].data_ptr(), torch.cuda.current_stream(dev).cuda_stream),

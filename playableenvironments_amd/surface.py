@@ -6,6 +6,10 @@
 there), triangle normals pointing from matter (``sigma > level``) to empty space.  Lattice values exactly equal to ``level`` count
 as outside and give coinciding vertices and zero-area triangles, which are kept.  The vertex and triangle order is fixed (header),
 so results can be compared bit for bit.  There is no CPU fallback.
+
+``label_components`` / ``clean_lattice`` (``pr_label_components``) label the connected components of the inside set on the same
+lattice and blank out the unwanted ones: floater removal (``keep_largest``, ``min_points``) and capping (``close_border``) in front of
+the mesher and of ``pr_occupancy_build``.
 """
 from __future__ import annotations
 
@@ -73,12 +77,94 @@ def surface_struct(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: flo
     return s
 
 
-def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float, *, normals: bool = True) -> List[Mesh]:
+def components_struct(sigma: torch.Tensor, level: float, counts: torch.Tensor, *, labels: Optional[torch.Tensor] = None,
+                      sizes: Optional[torch.Tensor] = None, sigma_out: Optional[torch.Tensor] = None, keep_largest: int = 0,
+                      min_points: int = 0, close_border: bool = False, fill: Optional[float] = None) -> _lib.Components:
+    """``pr_components_t`` over prepared tensors (fp32 / int32, contiguous, one device); ``fill=None`` means ``level``."""
+    c = _lib.Components()
+    c.groups = sigma.size(0)
+    for a in range(3):
+        c.points[a] = sigma.size(1 + a)
+    c.level = float(level)
+    c.flags = _lib.COMPONENTS_CLOSE_BORDER if close_border else 0
+    c.min_points = int(min_points)
+    c.keep_largest = int(keep_largest)
+    c.fill = float(level if fill is None else fill)
+    c.sigma = sigma.data_ptr()
+    c.labels = None if labels is None else labels.data_ptr()
+    c.sizes = None if sizes is None else sizes.data_ptr()
+    c.sigma_out = None if sigma_out is None else sigma_out.data_ptr()
+    c.counts = counts.data_ptr()
+    return c
+
+
+def _lattice(sigma: torch.Tensor) -> torch.Tensor:
+    if not sigma.is_cuda:
+        raise RuntimeError(NO_CPU)
+    if sigma.dim() != 4:
+        raise ValueError(f"sigma must be (G, nx, ny, nz), got {list(sigma.shape)}")
+    return sigma.detach().to(torch.float32).contiguous()
+
+
+def _run_components(sigma: torch.Tensor, level: float, **outputs) -> torch.Tensor:
+    """One ``pr_label_components`` call on the current stream of ``sigma``'s device; returns ``counts (G, 4)``."""
+    lib = _lib.load()
+    dev = sigma.device
+    with torch.cuda.device(dev):
+        counts = torch.empty((sigma.size(0), 4), dtype=torch.int32, device=dev)
+        c = components_struct(sigma, level, counts, **outputs)
+        size = C.c_size_t()
+        _lib.check(lib.pr_components_workspace_size(C.byref(c), C.byref(size)), "pr_components_workspace_size")
+        workspace = torch.empty(size.value, dtype=torch.uint8, device=dev)
+        _lib.check(lib.pr_label_components(C.byref(c), workspace.data_ptr(), size.value, torch.cuda.current_stream(dev).cuda_stream),
+                   "pr_label_components")
+    return counts
+
+
+def label_components(sigma: torch.Tensor, level: float, *, close_border: bool = False):
+    """Connected components of the inside set ``sigma > level`` of ``sigma (G, nx, ny, nz)`` under the 14-neighbourhood of the
+    mesher's seven edge directions (``pr_label_components``, include/playrender.h).  Returns ``(labels, sizes, counts)`` on the
+    device: int32 ``(G, nx, ny, nz)`` labels (the smallest flat index of the point's component inside its group, -1 outside) and
+    sizes (points of the point's component, 0 outside), and ``counts (G, 4)`` = inside points, components, kept components, kept
+    points.  ``close_border``: the border layer of the lattice counts as outside.  No host synchronisation."""
+    sigma = _lattice(sigma)
+    labels = torch.empty(sigma.shape, dtype=torch.int32, device=sigma.device)
+    sizes = torch.empty(sigma.shape, dtype=torch.int32, device=sigma.device)
+    counts = _run_components(sigma, level, labels=labels, sizes=sizes, close_border=close_border)
+    return labels, sizes, counts
+
+
+def clean_lattice(sigma: torch.Tensor, level: float, *, keep_largest: int = 0, min_points: int = 0, close_border: bool = False,
+                  fill: Optional[float] = None):
+    """``sigma`` with its unwanted components blanked out: ``(sigma_out, counts)``.  The components of every group are ranked by size
+    (ties: the smaller label first); one is kept iff it has at least ``min_points`` points and - with ``keep_largest`` in 1..8 - is
+    among the ``keep_largest`` largest.  Every inside point of a component that is not kept holds ``fill`` (``None``: ``level``, which
+    is outside) and, with ``close_border``, so does every border point ``> level``; all other values are the input's, bit for bit.
+    ``counts (G, 4)`` as in ``label_components``.  No host read-back."""
+    if not 0 <= int(keep_largest) <= _lib.COMPONENTS_MAX_KEEP:
+        raise ValueError(f"keep_largest must be in 0..{_lib.COMPONENTS_MAX_KEEP}, got {keep_largest}")
+    if int(min_points) < 0:
+        raise ValueError(f"min_points must be >= 0, got {min_points}")
+    if fill is not None and not float(fill) <= float(level):
+        raise ValueError(f"fill must be <= level ({level}), got {fill}")
+    sigma = _lattice(sigma)
+    out = torch.empty_like(sigma)
+    counts = _run_components(sigma, level, sigma_out=out, keep_largest=keep_largest, min_points=min_points, close_border=close_border,
+                             fill=fill)
+    return out, counts
+
+
+def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float, *, normals: bool = True, keep_largest: int = 0,
+                    min_points: int = 0, close_border: bool = False) -> List[Mesh]:
     """Meshes of the level set ``sigma = level`` of ``sigma (G, nx, ny, nz)`` (device tensor, z fastest - what ``density_grid``
     returns); ``axes``: the coordinates of the lattice points along x, y, z (``nx``, ``ny``, ``nz`` values).  Returns G meshes.
 
     Two calls on the current stream: a count-only one, then - after reading the two totals back, the ONE host synchronisation of
-    this function - an emitting one into exactly sized tensors."""
+    this function - an emitting one into exactly sized tensors.
+
+    ``keep_largest`` / ``min_points`` / ``close_border``: with any of them set the lattice goes through ``clean_lattice`` (fill =
+    ``level``) first - floaters are dropped, the surface is capped at the lattice border.  Positions and triangles of the kept
+    components do not change; normals near a removed component can, because the gradient stencil reads the blanked values."""
     if not sigma.is_cuda:
         raise RuntimeError(NO_CPU)
     if sigma.dim() != 4:
@@ -87,6 +173,8 @@ def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: fl
         raise ValueError("axes must be the three coordinate vectors of the lattice")
     dev = sigma.device
     sigma = sigma.detach().to(torch.float32).contiguous()
+    if keep_largest or min_points or close_border:
+        sigma, _ = clean_lattice(sigma, level, keep_largest=keep_largest, min_points=min_points, close_border=close_border)
     axes = [torch.as_tensor(a).detach().to(device=dev, dtype=torch.float32).contiguous() for a in axes]
     for a in range(3):
         if axes[a].dim() != 1 or axes[a].numel() != sigma.size(1 + a):
