@@ -619,6 +619,30 @@ int pr_render_backward(const pr_call_t* call, const pr_object_t* objects, const 
                        void* backward_workspace, size_t backward_workspace_bytes, void* stream);
 
 /*
+ * The per-sample gradients of the compositing backward (tests and diagnostics): what its kernel left in the backward workspace
+ * for the per-object network passes, copied out right behind its launch - the later kernels clear and reuse those buffers.
+ * Every pointer may be NULL (not wanted); objects beyond call->objects are ignored.  One struct per level.
+ */
+typedef struct pr_sample_grads_t {
+    float* sigma[PR_MAX_OBJECTS];                   /* (N,R,P_k) d loss / d raw density, summed over the object's own entry and
+                                                       the global entry */
+    float* t[PR_MAX_OBJECTS];                       /* (N,R,P_k) d loss / d sample depth (through the spacings and `depth`) */
+    float* displacement_magnitude[PR_MAX_OBJECTS];  /* (N,R,P_k) d loss / d |delta|; objects with a ray bender, ignored otherwise */
+    float* features[PR_MAX_OBJECTS];                /* (N,R,P_k,F) dense d loss / d feature row; zeros where sample_slot < 0 */
+    float* norm;                                    /* (N,R) d loss / d |d| through the sample spacings of every entry */
+    float* feature_rows[PR_MAX_OBJECTS];            /* (N,R,P_k,F) dense: the forward pass's feature rows the kernel read (the
+                                                       input of the stage no forward export carries); zeros where sample_slot < 0 */
+} pr_sample_grads_t;
+
+/* pr_render_backward plus the exports above (`exports_coarse` / `exports_fine`: NULL = none; with both NULL this IS
+ * pr_render_backward: no additional launch).  Additive entry point: PR_ABI_VERSION is unchanged. */
+int pr_render_backward_exported(const pr_call_t* call, const pr_object_t* objects, const pr_output_grads_t* grads_coarse,
+                                const pr_output_grads_t* grads_fine /* NULL unless use_fine */, const pr_input_grads_t* out,
+                                void* forward_workspace, size_t forward_workspace_bytes,
+                                void* backward_workspace, size_t backward_workspace_bytes, void* stream,
+                                const pr_sample_grads_t* exports_coarse, const pr_sample_grads_t* exports_fine);
+
+/*
  * Camera rays (RayHelper.create_camera_rays + pixel selection + transform_rays, ray_helper.py:15-52,
  * :433-482, :1203-1227): for frame n and ray r with pixel (rows[r], cols[r]),
  *   d_cam = ((col - W/2)/f_n, -(row - H/2)/f_n, -1),  d_world = R_n d_cam,  o_world = t_n.

@@ -148,6 +148,13 @@ class InputGrads(C.Structure):
                 ("model_fine", ModelGrads * PR_MAX_OBJECTS), ("ray_origins", C.c_void_p), ("ray_directions", C.c_void_p)]
 
 
+class SampleGrads(C.Structure):
+    """pr_sample_grads_t (include/playrender.h): the per-sample gradients of the compositing backward, per level."""
+    _fields_ = [("sigma", C.c_void_p * PR_MAX_OBJECTS), ("t", C.c_void_p * PR_MAX_OBJECTS),
+                ("displacement_magnitude", C.c_void_p * PR_MAX_OBJECTS), ("features", C.c_void_p * PR_MAX_OBJECTS),
+                ("norm", C.c_void_p), ("feature_rows", C.c_void_p * PR_MAX_OBJECTS)]
+
+
 class Query(C.Structure):
     """pr_query_t (include/playrender.h): a point query of one object model's fields."""
     _fields_ = [("groups", C.c_int32), ("points", C.c_int32), ("flags", C.c_uint32), ("precision", C.c_int32),
@@ -242,6 +249,9 @@ SYMBOLS = {
     "pr_backward_workspace_size": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(C.c_size_t)]),
     "pr_render_backward": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(OutputGrads), C.POINTER(OutputGrads),
                                      C.POINTER(InputGrads), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pr_render_backward_exported": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(OutputGrads), C.POINTER(OutputGrads),
+                                              C.POINTER(InputGrads), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                              C.POINTER(SampleGrads), C.POINTER(SampleGrads)]),
     "pr_camera_rays": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pr_expected_positions": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,

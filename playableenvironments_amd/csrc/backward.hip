@@ -431,6 +431,44 @@ static int launch_composite_bwd(const CompositeBwdParams& p, hipStream_t s) {
     return PR_OK;
 }
 
+// pr_sample_grads_t: copies of what k_composite_bwd wrote, taken right behind it (k_gather_rows clears the feature rows of
+// unused samples, the head products reuse them).  One launch per level, blockIdx.y = object; element = (sample, channel).
+struct SampleGradExport {
+    long samples[PR_MAX_OBJECTS];                 // N R P_k
+    const int32_t* slot[PR_MAX_OBJECTS];
+    const float *g_sigma[PR_MAX_OBJECTS], *g_t[PR_MAX_OBJECTS], *g_dm[PR_MAX_OBJECTS], *g_feat[PR_MAX_OBJECTS];
+    float *sigma[PR_MAX_OBJECTS], *t[PR_MAX_OBJECTS], *dm[PR_MAX_OBJECTS], *feat[PR_MAX_OBJECTS], *rows[PR_MAX_OBJECTS];
+    const float* f_rows[PR_MAX_OBJECTS];          // the forward pass's compact feature rows (stride F)
+    const float* g_norm;
+    float* norm;
+    long rays;                                    // N R
+    int F, Fs;
+};
+
+__global__ __launch_bounds__(256) void k_export_sample_grads(SampleGradExport x) {
+    const int k = blockIdx.y;
+    const long n = x.samples[k];
+    const long step = (long)gridDim.x * 256;
+    const long first = (long)blockIdx.x * 256 + threadIdx.x;
+    for (long i = first; i < n; i += step) {
+        if (x.sigma[k]) x.sigma[k][i] = x.g_sigma[k][i];
+        if (x.t[k]) x.t[k][i] = x.g_t[k][i];
+        if (x.dm[k] && x.g_dm[k]) x.dm[k][i] = x.g_dm[k][i];
+    }
+    if (x.feat[k] || x.rows[k]) {
+        const long total = n * x.F;
+        for (long e = first; e < total; e += step) {
+            const long i = e / x.F;
+            const int c = (int)(e - i * x.F);
+            const int row = x.slot[k][i];
+            if (x.feat[k]) x.feat[k][e] = row >= 0 ? x.g_feat[k][(size_t)row * x.Fs + c] : 0.f;
+            if (x.rows[k]) x.rows[k][e] = row >= 0 ? x.f_rows[k][(size_t)row * x.F + c] : 0.f;
+        }
+    }
+    if (k == 0 && x.norm)
+        for (long i = first; i < x.rays; i += step) x.norm[i] = x.g_norm[i];
+}
+
 // ---------------------------------------------------------------------------------------------
 // Row-wise kernels of the per-object network backward.  "rows" = compact evaluated samples, M = *total.
 // flags: bit 0 = real sample, bit 1 = passed the second AABB test (its outputs are used).
@@ -1603,7 +1641,8 @@ static int chain_backward(const GemmCtx& g, const pr_linear_t* layers, const pr_
 // compositing backward of one model type: per-sample gradients (feature rows, sigma, t, |delta|, divergence) of every object
 struct CompositeBwdResult { bool div_grad, ray_grads; float* g_norm; };
 static int composite_backward(const pr_call_t& c, const pr_object_t* objs, int t, const pr_output_grads_t& grads, const pr_input_grads_t& out,
-                              char* fws, const Plan& plan, char* bws, const BwdPlan& bp, hipStream_t s, CompositeBwdResult* res) {
+                              char* fws, const Plan& plan, char* bws, const BwdPlan& bp, hipStream_t s, CompositeBwdResult* res,
+                              const pr_sample_grads_t* ex) {
     const int K = c.objects;
     const TypePlan& tp = plan.type[t];
     const pr_noise_t& noise = t ? c.noise_fine : c.noise_coarse;
@@ -1660,12 +1699,36 @@ static int composite_backward(const pr_call_t& c, const pr_object_t* objs, int t
     res->ray_grads = out.ray_origins != nullptr || out.ray_directions != nullptr;
     res->g_norm = (out.ray_directions && bp.g_norm_bytes) ? reinterpret_cast<float*>(bws + bp.g_norm) : nullptr;
     cp.g_norm = res->g_norm;
-    return launch_composite_bwd(cp, s);
+    if (!ex) return launch_composite_bwd(cp, s);
+    // exports: d loss / d |d| is computed for them even where no ray gradient is wanted (the buffer is part of every plan)
+    if (ex->norm && !cp.g_norm) cp.g_norm = reinterpret_cast<float*>(bws + bp.g_norm);
+    PR_TRY(launch_composite_bwd(cp, s));
+    SampleGradExport x;
+    memset(&x, 0, sizeof(x));
+    long most = 0;
+    for (int k = 0; k < K; ++k) {
+        const CompositeBwdObject& o = cp.obj[k];
+        x.samples[k] = (long)c.frames * c.rays * o.positions;
+        x.slot[k] = o.slot;
+        x.g_sigma[k] = o.g_sigma; x.g_t[k] = o.g_t; x.g_dm[k] = o.g_dm; x.g_feat[k] = o.g_feat;
+        x.sigma[k] = ex->sigma[k]; x.t[k] = ex->t[k]; x.dm[k] = ex->displacement_magnitude[k]; x.feat[k] = ex->features[k];
+        x.rows[k] = ex->feature_rows[k]; x.f_rows[k] = o.feat;
+        most = std::max(most, x.samples[k] * ((x.feat[k] || x.rows[k]) ? F : 1));
+    }
+    x.g_norm = cp.g_norm;
+    x.norm = ex->norm;
+    x.rays = (long)c.frames * c.rays;
+    x.F = F; x.Fs = Fs;
+    most = std::max(most, x.rays);
+    const long blocks = std::min<long>((most + 255) / 256, 65535);
+    hipLaunchKernelGGL(k_export_sample_grads, dim3((unsigned)blocks, K), dim3(256), 0, s, x);
+    PR_LAUNCH_CHECK();
+    return PR_OK;
 }
 
 // backward of one model type (t = 0: coarse models / results["coarse"], 1: fine), one object after the other on two lanes
 static int backward(const pr_call_t& c, const pr_object_t* objs, int t, const pr_output_grads_t& grads, const pr_input_grads_t& out,
-                    char* fws, const Plan& plan, char* bws, const BwdPlan& bp, hipStream_t s_caller) {
+                    char* fws, const Plan& plan, char* bws, const BwdPlan& bp, hipStream_t s_caller, const pr_sample_grads_t* ex) {
     const int K = c.objects;
     const TypePlan& tp = plan.type[t];
     const pr_noise_t& noise = t ? c.noise_fine : c.noise_coarse;
@@ -1673,7 +1736,7 @@ static int backward(const pr_call_t& c, const pr_object_t* objs, int t, const pr
     const int F = objs[0].coarse.output_features;
     const int Fs = (F + 15) & ~15;     // row stride of the feature gradients
     CompositeBwdResult cr;
-    PR_TRY(composite_backward(c, objs, t, grads, out, fws, plan, bws, bp, s_caller, &cr));
+    PR_TRY(composite_backward(c, objs, t, grads, out, fws, plan, bws, bp, s_caller, &cr, ex));
     const bool div_grad = cr.div_grad, ray_grads = cr.ray_grads;
     float* g_norm = cr.g_norm;
 
@@ -1977,7 +2040,7 @@ static int backward(const pr_call_t& c, const pr_object_t* objs, int t, const pr
 //   gradient of every object (one launch + its reduction) -> style affines -> sample placement
 // ---------------------------------------------------------------------------------------------
 static int backward_grouped(const pr_call_t& c, const pr_object_t* objs, int t, const pr_output_grads_t& grads, const pr_input_grads_t& out,
-                            char* fws, const Plan& plan, char* bws, const BwdPlan& bp, hipStream_t s) {
+                            char* fws, const Plan& plan, char* bws, const BwdPlan& bp, hipStream_t s, const pr_sample_grads_t* ex) {
     const int K = c.objects;
     const TypePlan& tp = plan.type[t];
     const GroupPlan& gp = bp.group;
@@ -1986,7 +2049,7 @@ static int backward_grouped(const pr_call_t& c, const pr_object_t* objs, int t, 
     const int Fs = (F + 15) & ~15;
     PR_TRY(launch_zero_fill(bws + gp.zero_begin, gp.zero_bytes, s));
     CompositeBwdResult cr;
-    PR_TRY(composite_backward(c, objs, t, grads, out, fws, plan, bws, bp, s, &cr));
+    PR_TRY(composite_backward(c, objs, t, grads, out, fws, plan, bws, bp, s, &cr, ex));
 
     static thread_local HeadBwdJob h1[PR_MAX_OBJECTS], h2[PR_MAX_OBJECTS];
     static thread_local ChainBwdJob cn[PR_MAX_OBJECTS], cb[PR_MAX_OBJECTS];
@@ -2338,10 +2401,10 @@ extern "C" int pr_backward_workspace_size(const pr_call_t* call, const pr_object
     return PR_OK;
 }
 
-extern "C" int pr_render_backward(const pr_call_t* call, const pr_object_t* objects, const pr_output_grads_t* grads,
-                                  const pr_output_grads_t* grads_fine, const pr_input_grads_t* out, void* forward_workspace,
-                                  size_t forward_workspace_bytes, void* backward_workspace, size_t backward_workspace_bytes,
-                                  void* stream) {
+extern "C" int pr_render_backward_exported(const pr_call_t* call, const pr_object_t* objects, const pr_output_grads_t* grads,
+                                           const pr_output_grads_t* grads_fine, const pr_input_grads_t* out, void* forward_workspace,
+                                           size_t forward_workspace_bytes, void* backward_workspace, size_t backward_workspace_bytes,
+                                           void* stream, const pr_sample_grads_t* exports_coarse, const pr_sample_grads_t* exports_fine) {
     PR_REQUIRE(grads && out && forward_workspace && backward_workspace, "pr_render_backward: NULL argument");
     PR_TRY(check_backward_call(call, objects));
     PR_REQUIRE(!call->use_fine || grads_fine, "pr_render_backward: use_fine calls need grads_fine");
@@ -2358,11 +2421,19 @@ extern "C" int pr_render_backward(const pr_call_t* call, const pr_object_t* obje
     // calls with gradients of the divergence estimate, or whose scratch would not fit, take the per-object path
     auto pass = bp.group.usable ? pr::backward_grouped : pr::backward;
     PR_TRY(pass(*call, objects, 0, *grads, *out, static_cast<char*>(forward_workspace), plan,
-                static_cast<char*>(backward_workspace), bp, (hipStream_t)stream));
+                static_cast<char*>(backward_workspace), bp, (hipStream_t)stream, exports_coarse));
     if (call->use_fine)
         PR_TRY(pass(*call, objects, 1, *grads_fine, *out, static_cast<char*>(forward_workspace), plan,
-                    static_cast<char*>(backward_workspace), bp, (hipStream_t)stream));
+                    static_cast<char*>(backward_workspace), bp, (hipStream_t)stream, exports_fine));
     return PR_OK;
+}
+
+extern "C" int pr_render_backward(const pr_call_t* call, const pr_object_t* objects, const pr_output_grads_t* grads,
+                                  const pr_output_grads_t* grads_fine, const pr_input_grads_t* out, void* forward_workspace,
+                                  size_t forward_workspace_bytes, void* backward_workspace, size_t backward_workspace_bytes,
+                                  void* stream) {
+    return pr_render_backward_exported(call, objects, grads, grads_fine, out, forward_workspace, forward_workspace_bytes,
+                                       backward_workspace, backward_workspace_bytes, stream, nullptr, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------

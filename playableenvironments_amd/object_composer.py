@@ -340,11 +340,35 @@ class _RenderFunction(torch.autograd.Function):
         _lib.check(lib.pr_backward_workspace_size(C.byref(st["call"]), st["objs"], C.byref(size)), "pr_backward_workspace_size")
         scratch = torch.empty(size.value, dtype=torch.uint8, device=dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.pr_render_backward(C.byref(st["call"]), st["objs"], C.byref(ogs["coarse"]),
-                                          C.byref(ogs["fine"]) if "fine" in st["types"] else None, C.byref(ig),
-                                          st["workspace"].data_ptr(),
-                                          st["workspace"].numel(), scratch.data_ptr(), scratch.numel(), stream),
-                   "pr_render_backward")
+        if ctx.exported and composer._export_sample_grads:
+            # (tests) what the compositing backward computed per sample: pr_sample_grads_t, one per level
+            xs, composer.last_sample_grads = {}, {}
+            for ty in st["types"]:
+                x, got = _lib.SampleGrads(), {"norm": torch.empty((N, R), **f32)}
+                x.norm = got["norm"].data_ptr()
+                for field in ("sigma", "t", "displacement_magnitude", "features", "feature_rows"):
+                    got[field] = []
+                    for k in range(K):
+                        model = st["objs"][k].fine if ty == "fine" else st["objs"][k].coarse
+                        if field == "displacement_magnitude" and not model.has_bender:
+                            got[field].append(None)
+                            continue
+                        tail = (F,) if field in ("features", "feature_rows") else ()
+                        got[field].append(torch.empty((N, R, st["ptot"][ty][k]) + tail, **f32))
+                        getattr(x, field)[k] = got[field][k].data_ptr()
+                xs[ty], composer.last_sample_grads[ty] = x, got
+            _lib.check(lib.pr_render_backward_exported(C.byref(st["call"]), st["objs"], C.byref(ogs["coarse"]),
+                                                       C.byref(ogs["fine"]) if "fine" in st["types"] else None, C.byref(ig),
+                                                       st["workspace"].data_ptr(), st["workspace"].numel(), scratch.data_ptr(),
+                                                       scratch.numel(), stream, C.byref(xs["coarse"]),
+                                                       C.byref(xs["fine"]) if "fine" in st["types"] else None),
+                       "pr_render_backward_exported")
+        else:
+            _lib.check(lib.pr_render_backward(C.byref(st["call"]), st["objs"], C.byref(ogs["coarse"]),
+                                              C.byref(ogs["fine"]) if "fine" in st["types"] else None, C.byref(ig),
+                                              st["workspace"].data_ptr(),
+                                              st["workspace"].numel(), scratch.data_ptr(), scratch.numel(), stream),
+                       "pr_render_backward")
         for hook in composer.gradient_hooks:
             hook(flat)
         # parameter gradients exist now: an optimiser step is about to change the weights, and torch's FUSED optimisers
@@ -447,6 +471,11 @@ class ObjectComposer(Tracked, nn.Module):
         self.last_geometry_workspace = None
         #: device tensors (K,) per model type: samples that entered the BatchNorm batch statistics of the last training call
         self.last_normalised_samples: Dict[str, torch.Tensor] = {}
+        #: private switch of the tests (off): the backward pass of a differentiable ``_export=True`` call leaves the compositing
+        #: backward's per-sample gradients (pr_sample_grads_t) in ``last_sample_grads``: {level: {"sigma", "t",
+        #: "displacement_magnitude", "features", "feature_rows": per object (None without a ray bender), "norm"}}
+        self._export_sample_grads = False
+        self.last_sample_grads: Dict[str, dict] = {}
         #: where the random draws of perturbed / training calls come from when no explicit ``_noise`` is replayed:
         #: "device" - generated inside the kernels that consume them (PR_FLAG_DEVICE_NOISE: Philox4x32-10 keyed by a per-call
         #: seed, regenerated by the backward pass; nothing of size (N, R, P) is materialised); "torch" - torch.rand / torch.randn

@@ -717,3 +717,265 @@ def capture_oracle_stages(run_oracle):
     finally:
         ro.hierarchical_positions, ro.integrate = h0, i0
     return result, resampled, integrated
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Compositing backward on surface-like densities ("Compositing backward in the density regimes"): the
+# per-sample gradients k_composite_bwd wrote (pr_sample_grads_t) against float64 autograd of the oracle's functions for that stage
+GRADIENT_FIELDS = ("integrated_features", "opacity", "depth", "integrated_displacements_magnitude", "weights")
+GRADIENT_TENSORS = ("sigma", "t", "displacement_magnitude", "features")
+
+
+def stage_probes(cfg, flat, positions, seed, fields=GRADIENT_FIELDS, entries=None):
+    """{entry: {field: probe}}: the random linear functional of one level (the suite's ``_probe_loss`` pattern) in the folded layout
+    (N, R, ...); ``positions``: per object the length of its list; ``entries``: the entries the loss reads (default: all)."""
+    g = torch.Generator().manual_seed(seed)
+    N, R, K = flat["d"].size(0), flat["R"], flat["K"]
+    F = _object_config(cfg, 0)["nerf_model"]["output_features"]
+    out = {}
+    for k in range(K + 1):
+        name = f"object_{k}" if k < K else "global"
+        P = positions[k] if k < K else sum(positions)
+        shapes = {"integrated_features": (N, R, F), "weights": (N, R, P)}
+        probes = {f: torch.randn(shapes.get(f, (N, R)), generator=g, dtype=torch.float32) for f in GRADIENT_FIELDS}       # (drawn whether read or not)
+        if entries is None or name in entries:
+            out[name] = {f: probes[f] for f in fields}
+    return out
+
+
+def replay_gradients(cfg, level, lists, slots, features, d_world, noise, probes):
+    """Autograd (torch's default dtype: float64 under ``oracle_in_float64``) through replay_integration, replay_composition and
+    expected_features - the oracle's functions of the compositing stage - of the loss
+        sum over the entries and fields of ``probes`` of (probe * field).sum().
+    Leaves: per object the depths ``t``, raw densities ``sigma`` (N, R, P), the displacement magnitudes |delta| and the raw feature
+    rows ``features`` (N, R, P, F; masked with ``slots >= 0``, then the sigmoid of ``apply_activation``), and the ray direction norm
+    |d| (N, R).  ``lists``: per object (t, sigma, delta or None); ``noise``: the recorded draws of a perturbed call or None
+    (``int_<level>_<k>``, ``int_<level>_global``).
+
+    |delta| as a variable: the lists carry (|delta| + 1, 0, 0) - torch.norm's subgradient at 0 is 0, the derivative with respect to
+    the magnitude is w / n everywhere (a sample outside its box has delta = 0 and, with density noise, a weight); the weights are
+    detached in that field, so the shift adds nothing to any gradient.
+
+    Returns dict(objects=[{sigma, t, displacement_magnitude, features}], norm, masked): ``t`` and ``sigma`` summed over the object's
+    own entry and the global entry, as the kernel accumulates them."""
+    dt = torch.get_default_dtype()
+    K = len(lists)
+    leaf = lambda v: v.detach().to(dt).clone().requires_grad_(True)
+    d_world = d_world.detach().to(dt)
+    length = torch.linalg.norm(d_world, dim=-1)
+    norm = leaf(length)
+    directions = d_world / length.unsqueeze(-1) * norm.unsqueeze(-1)
+    ts, sigmas, mags, feats, disps = [], [], [], [], []
+    for k, (t, sigma, delta) in enumerate(lists):
+        ts.append(leaf(t))
+        sigmas.append(leaf(sigma))
+        mags.append(leaf(torch.linalg.norm(delta.detach().to(dt), dim=-1) if delta is not None else torch.zeros(t.shape)))
+        feats.append(leaf(features[k]))
+        zero = torch.zeros_like(mags[k])
+        disps.append(torch.stack([mags[k] + 1.0, zero, zero], dim=-1))
+    key = lambda name: None if noise is None else noise[f"int_{level}_{name}"]
+    own = [replay_integration(ts[k], sigmas[k], disps[k], directions, key(k)) for k in range(K)]
+    comp = replay_composition(cfg, [(ts[k], sigmas[k], disps[k]) for k in range(K)], directions, key("global"))
+    shown = [f * (slots[k] >= 0).unsqueeze(-1).to(dt) for k, f in enumerate(feats)]
+    if cfg["model"]["apply_activation"]:
+        shown = [torch.sigmoid(f) for f in shown]
+    per_object, total = expected_features(shown, [o["weights"] for o in own], comp["weights"], comp["order"])
+    loss = torch.zeros(())
+    for name, fields in probes.items():
+        entry = comp if name == "global" else own[int(name.split("_")[1])]
+        for f, probe in fields.items():
+            if f == "integrated_features":
+                value = total if name == "global" else per_object[int(name.split("_")[1])]
+            else:
+                value = entry[f]
+            loss = loss + (value * probe.to(dt).reshape(value.shape)).sum()
+    leaves = ts + sigmas + mags + feats + [norm]
+    if loss.requires_grad:
+        grads = torch.autograd.grad(loss, leaves, allow_unused=True)
+    else:
+        grads = [None] * len(leaves)
+    grads = [torch.zeros_like(v) if g is None else g for g, v in zip(grads, leaves)]
+    objects = [dict(t=grads[k], sigma=grads[K + k], displacement_magnitude=grads[2 * K + k], features=grads[3 * K + k]) for k in range(K)]
+    return dict(objects=objects, norm=grads[4 * K], masked=comp["masked"], order=comp["order"])
+
+
+GRADIENT_RTOL, GRADIENT_ATOL = 1e-4, 1e-5      # |got - want| <= RTOL |want| + ATOL max |want| (+ the cancellation term), per tensor
+#: the one free constant of the cancellation term (gradient_mismatch): measured on the CPU only, never on the kernel
+GRADIENT_C = 2.0
+
+
+def gradient_mismatch(want, got, magnitude=None, c=GRADIENT_C):
+    """(worst |got - want| / tolerance, ok) position by position; every value of ``got`` finite.  A tensor whose reference is zero
+    everywhere must be zero everywhere.
+
+    TOLERANCE (derived, not tuned):  1e-4 |want| + 1e-5 max |want| + c 2^-23 ``magnitude``.
+    d alpha_j = dw_j T_j - (sum_{i>j} dw_i w_i) / (1 - alpha_j + 1e-10) is a difference: behind a dense sample both terms are small
+    multiples of T_j and cancel to a fraction of themselves, and d t_j = gD w_j + dd_{j-1} - dd_j is a difference of neighbours.
+    Each term is the end of a running product or sum over the n samples of the list, known in fp32 to n 2^-24 of itself at best,
+    whatever the order of the scan - so a gradient is known to 2^-23 n (sum of the absolute values of its terms), which
+    gradient_magnitudes forms in float64 from the inputs of the stage alone (``magnitude``; None: the first two terms only).  The
+    first two terms - the issue's tolerance - do not cover it: measured on the CPU (tests/test_composite_backward_cpu.py prints both
+    ratios), fp32 torch autograd of the oracle's function and the sequential restatement need 1.54 of them on tennis_64_128 /
+    surfaces / perturb (coarse d sigma of object 2, a sample behind sigma dt = 12), each other's error to 3 digits.  ``c`` is the
+    smallest power of two for which both stay inside the tolerance on every case x regime x {eval, perturb}: with c = 1 both
+    need 1.05 on tennis_64_128 / sparse / perturb (fine d sigma of object 3; 19.5 of the first two terms alone), so c = 2.  The kernel is held to
+    the same tolerance and is never used to choose c."""
+    a, b = want.detach().cpu().double(), got.detach().cpu().double().reshape(want.shape)
+    if not a.numel():
+        return 0.0, True
+    if not bool(torch.isfinite(b).all()):
+        return float("inf"), False
+    tol = GRADIENT_RTOL * a.abs() + GRADIENT_ATOL * a.abs().max()
+    if magnitude is not None:
+        tol = tol + c * FP32_EPS * magnitude.detach().cpu().double().reshape(want.shape)
+    diff = (a - b).abs()
+    ratio = torch.where(diff > 0, diff / tol, torch.zeros_like(diff))          # (x / 0 = inf for x > 0)
+    worst = float(ratio.max())
+    return worst, worst <= 1.0
+
+
+def compare_gradients(want, got, bender, magnitudes=None, c=GRADIENT_C):
+    """replay_gradients' result against the tensors of the side under test ({"sigma", "t", "displacement_magnitude", "features": per
+    object, "norm"}): {"<tensor>/<object>": (worst ratio, ok)}; ``bender``: per object whether |delta| exists; ``magnitudes``:
+    gradient_magnitudes of the same inputs (sigma, t and norm carry a cancellation term) or None."""
+    rep = {}
+    for k, obj in enumerate(want["objects"]):
+        for name in GRADIENT_TENSORS:
+            if name == "displacement_magnitude" and not bender[k]:
+                continue
+            m = magnitudes["objects"][k][name] if magnitudes is not None and name in ("sigma", "t") else None
+            rep[f"{name}/{k}"] = gradient_mismatch(obj[name], got[name][k], m, c)
+    rep["norm"] = gradient_mismatch(want["norm"], got["norm"], None if magnitudes is None else magnitudes["norm"], c)
+    return rep
+
+
+def gradient_magnitudes(cfg, level, lists, slots, features, d_world, noise, probes):
+    """Per gradient of replay_gradients (sigma, t, norm): n times the sum of the absolute values of the terms it is a difference of,
+    in float64 (sequential_composite_bwd_fp32 with ``magnitude=True``) - the cancellation term of gradient_mismatch."""
+    return sequential_composite_bwd_fp32(cfg, level, lists, slots, features, d_world, noise, probes, magnitude=True)
+
+
+def sequential_composite_bwd_fp32(cfg, level, lists, slots, features, d_world, noise, probes, mutation=None, magnitude=False):
+    """numpy fp32 restatement of k_composite_bwd's ``entry_backward`` arithmetic over the entries of a level, one rounding per
+    operation, every scan strictly sequential (the precedent: sequential_resampling_fp32): alpha_j = 1 - exp(-relu(raw) dt |d|),
+    T_j = prod_{i<j} (1 - alpha_i + 1e-10), w_j = alpha_j T_j, dw_j = gF . f_j (skipped where T_j = 0 or the sample has no row)
+    + gO + gD t_j + gW_j, d alpha_j = dw_j T_j - (sum_{i>j} dw_i w_i) / (1 - alpha_j + 1e-10), and from it d sigma, d t (both
+    neighbours' spacings and gD w_j), d |delta| = gM w_j / n and d |d|.  The per-object entries run on the lists as exported, the
+    global entry on the merged list behind the overlap fix, whose masked samples are constants.  Same arguments and result layout
+    as replay_gradients (without d features: the kernel forms them from the weights the forward tests cover).
+
+    ``mutation``: one of four wrong kernels the comparison must notice - "no_floor" (the quotient without its 1e-10),
+    "no_carry" (the suffix sum restarts at every 64-entry block, counted from the front as the kernel's blocks are),
+    "concatenation_order" (the global entry's gradients assigned by position in the merged list instead of through the order),
+    ``magnitude=True`` (gradient_magnitudes): the same pass in float64 with every difference replaced by the sum of the absolute
+    values of its terms, each entry's share times the length n of its list - what the cancelling terms of a gradient amount to.
+
+    "masked_gradient" (the backward pass of the global entry forgets the overlap fix: the masked static samples keep their density
+    and depth there and so receive gradient.  Dropping only the kernel's ``!mk`` guards changes nothing that can be seen: a masked
+    sample's sigma = -10 and t = 0 leave alpha = 0 and d alpha / d t = 0 exactly, so whatever it would accumulate is zero)."""
+    import numpy as np
+    f = np.float64 if magnitude else np.float32
+    K = len(lists)
+    arr = lambda v: np.ascontiguousarray(v.detach().cpu().numpy(), dtype=f)
+    mag = (lambda v: np.abs(v)) if magnitude else (lambda v: v)
+    sign = f(-1.0) if magnitude else f(1.0)                # a - b becomes |a| + |b|
+    d = arr(d_world).reshape(-1, 3)
+    M = d.shape[0]
+    norm = np.sqrt(((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]).astype(f)).astype(f)
+    counts = [int(t.size(-1)) for t, _, _ in lists]
+    PT = sum(counts)
+    tt = np.concatenate([arr(t).reshape(M, -1) for t, _, _ in lists], 1)
+    sg = np.concatenate([arr(s).reshape(M, -1) for _, s, _ in lists], 1)
+    sl = np.concatenate([s.detach().cpu().numpy().reshape(M, -1) for s in slots], 1)
+    ff = np.concatenate([arr(v).reshape(M, c, -1) for v, c in zip(features, counts)], 1)
+    if cfg["model"]["apply_activation"]:
+        ff = np.where(sl[..., None] >= 0, ff, f(0.0))
+        ff = (f(1.0) / (f(1.0) + np.exp(-ff))).astype(f)
+        has_row = np.ones_like(sl, dtype=bool)
+    else:
+        has_row = sl >= 0
+    gs, gt, gd = np.zeros((M, PT), f), np.zeros((M, PT), f), np.zeros((M, PT), f)
+    mk = np.zeros((M, PT), bool)
+    g_norm = np.zeros(M, f)
+    rows = np.arange(M)[:, None]
+
+    def entry(name, idx, n):
+        with np.errstate(all="ignore"):            # (the "no_floor" mutation divides by zero: its NaNs are what the comparison sees)
+            _entry(name, idx, n)
+
+    def _entry(name, idx, n):
+        nonlocal g_norm
+        pr = probes.get(name, {})
+        get = lambda field: arr(pr[field]).reshape(M, -1) if field in pr else None
+        gO, gD, gM, gW, gF = (get(x) for x in ("opacity", "depth", "integrated_displacements_magnitude", "weights", "integrated_features"))
+        gO, gD, gM = (np.zeros(M, f) if v is None else mag(v[:, 0]) for v in (gO, gD, gM))
+        scale = f(n) if magnitude else f(1.0)
+        t_e, raw = tt[rows, idx], sg[rows, idx].copy()
+        nz = None if noise is None else noise.get(f"int_{level}_{name.replace('object_', '')}")
+        if nz is not None:
+            raw = (raw + arr(nz).reshape(M, n)).astype(f)
+        dtv = np.concatenate([t_e[:, 1:] - t_e[:, :-1], np.full((M, 1), 1e10, f)], 1).astype(f)
+        dist = (dtv * norm[:, None]).astype(f)
+        s = np.maximum(raw, f(0.0))
+        E = np.exp((-s * dist).astype(f)).astype(f)
+        a = (f(1.0) - E).astype(f)
+        T, w = np.empty((M, n), f), np.empty((M, n), f)
+        run = np.ones(M, f)
+        for j in range(n):
+            T[:, j] = run
+            w[:, j] = a[:, j] * run
+            run = (run * ((f(1.0) - a[:, j]) + f(1e-10))).astype(f)
+        if gF is None and gW is None and not gO.any() and not gD.any() and not gM.any():
+            return
+        dw = np.zeros((M, n), f)
+        if gF is not None:
+            dot = np.einsum("mf,mjf->mj", mag(gF), mag(ff[rows, idx])).astype(f)
+            dw = np.where(has_row[rows, idx] & (T != 0), dot, f(0.0)).astype(f)
+        dw = (dw + gO[:, None] + gD[:, None] * mag(t_e) + (mag(gW) if gW is not None else f(0.0))).astype(f)
+        da = np.empty((M, n), f)
+        suffix = np.zeros(M, f)
+        with np.errstate(all="ignore"):
+            for j in range(n - 1, -1, -1):
+                if mutation == "no_carry" and j % 64 == 63:
+                    suffix = np.zeros(M, f)
+                den = (f(1.0) - a[:, j]) if mutation == "no_floor" else ((f(1.0) - a[:, j]) + f(1e-10))
+                da[:, j] = dw[:, j] * T[:, j] - sign * suffix / den
+                suffix = (suffix + dw[:, j] * w[:, j]).astype(f)
+        inner = np.arange(n)[None, :] < n - 1
+        dd = np.where(inner, da * s * E * norm[:, None], f(0.0)).astype(f)
+        g_norm = (g_norm + scale * np.where(inner, da * s * E * dtv, f(0.0)).astype(f).sum(1, dtype=f)).astype(f)
+        to = np.broadcast_to(np.arange(n)[None, :], (M, n)) if (mutation == "concatenation_order" and name == "global") else idx
+        live = ~mk[rows, idx]
+        before = np.concatenate([np.zeros((M, 1), f), dd[:, :-1]], 1)
+        np.add.at(gs, (rows, to), scale * np.where(live & (raw > 0), da * dist * E, f(0.0)).astype(f))
+        np.add.at(gt, (rows, to), scale * np.where(live, gD[:, None] * w + (before - sign * dd), f(0.0)).astype(f))
+        np.add.at(gd, (rows, to), np.where(live, gM[:, None] * w / f(n), f(0.0)).astype(f))
+
+    off = 0
+    for k in range(K):
+        entry(f"object_{k}", np.broadcast_to(off + np.arange(counts[k])[None, :], (M, counts[k])), counts[k])
+        off += counts[k]
+    layout = ro.ObjectLayout(cfg)
+    if cfg["model"]["fix_object_overlaps"] and mutation != "masked_gradient":
+        offs = np.concatenate([[0], np.cumsum(counts)])
+        for sidx in range(layout.static_objects):
+            ps = counts[sidx]
+            ts_ = tt[:, offs[sidx]:offs[sidx] + ps].copy()
+            hit = np.zeros((M, ps), bool)
+            for dyn in range(layout.static_objects, K):
+                b0, b1 = tt[:, offs[dyn]], tt[:, offs[dyn] + ps - 1]
+                lo = (ts_ < b0[:, None]).sum(1)              # searchsorted(left) on a sorted list
+                hi = (ts_ < b1[:, None]).sum(1)
+                i = np.arange(ps)[None, :]
+                hit |= (i >= lo[:, None]) & (i < hi[:, None])
+            tt[:, offs[sidx]:offs[sidx] + ps][hit] = 0.0
+            sg[:, offs[sidx]:offs[sidx] + ps][hit] = -10.0
+            mk[:, offs[sidx]:offs[sidx] + ps][hit] = True
+    order = np.argsort(tt, axis=1, kind="stable")
+    entry("global", order, PT)
+    out, off = [], 0
+    for k in range(K):
+        cut = lambda v: torch.from_numpy(v[:, off:off + counts[k]].copy()).reshape(lists[k][0].shape)
+        out.append(dict(sigma=cut(gs), t=cut(gt), displacement_magnitude=cut(gd)))
+        off += counts[k]
+    return dict(objects=out, norm=torch.from_numpy(g_norm).reshape(lists[0][0].shape[:-1]))
