@@ -541,6 +541,74 @@ int pr_components_workspace_size(const pr_components_t* c, size_t* bytes);
 int pr_label_components(const pr_components_t* c, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Density lattices evaluated only in a band around the level set: the front end (pr_band_plan) and the back end (pr_band_fill) around
+ * a field evaluation that stays the caller's.  An opt-in approximation: the field is evaluated at a coarse SKELETON of the lattice and
+ * then only where a skeleton cell saw the level set; a feature thinner than the stride that no skeleton cell sees as mixed is lost,
+ * and `guard` does not bring it back.
+ *   Lattice: sigma (G, nx, ny, nz), z fastest, every extent >= 2; point (i, j, k) sits at (axis[0][i], axis[1][j], axis[2][k]) -
+ *     rectilinear, shared by the groups, never computed with.  The flat index of a point inside its group is p = (i ny + j) nz + k.  A
+ *     point is INSIDE iff sigma > level (a NaN is never inside; a value equal to level is outside).
+ *   Skeleton: stride r in [PR_BAND_MIN_STRIDE, PR_BAND_MAX_STRIDE].  Along an axis of n points the skeleton indices are 0, r, 2r, ...
+ *     below n, plus n - 1 if it is not among them (the last cell may be shorter).  A SKELETON POINT has all three indices in these
+ *     sets.  A CELL is the box between two consecutive skeleton indices on every axis, closed; there are (cx, cy, cz) cells,
+ *     c = ceil((n - 1) / r) per axis, cell (a, b, c) has the flat index (a cy + b) cz + c.  On entry the lattice holds the field's value
+ *     at every skeleton point; every other entry is ignored.
+ *   Active cells: a cell is MIXED iff at least one of its 8 corner skeleton values is inside and at least one is not.  A cell is ACTIVE
+ *     iff some cell within Chebyshev distance `guard` (in [0, PR_BAND_MAX_GUARD], clipped at the cell grid) is mixed.
+ *   Band: a point belongs to the BAND iff it is not a skeleton point and at least one cell that contains it is active (a point on
+ *     cell faces belongs to up to 8 cells).  The band points are listed by group, then by ascending flat index: the order does not
+ *     depend on the execution.
+ * pr_band_plan writes point_offsets (G + 1) - group g owns the rows [off[g], off[g+1]) - and counts (G, 4) = cells, mixed cells,
+ *   active cells, band points; always.  Optionally: active (G, cx, cy, cz) bytes (1 = active), point_index (the flat index in the group
+ *   of every band point) and positions (rows, 3), read from the axes without arithmetic, up to max_points rows: an element at or beyond
+ *   the capacity is not written, the offsets always hold the true totals.  With active, point_index and positions all NULL the call only
+ *   counts.  values and exact are not looked at.
+ * pr_band_fill takes the same description, the same workspace - untouched since the plan call - and values (max_points): the field at
+ *   the listed points, row by row.  It writes values to their lattice entries; every remaining non-skeleton point receives the bits
+ *   of the skeleton value at the lower corner of the lowest-indexed cell that contains it - a copy, never arithmetic (NaN payloads
+ *   included).  Such a point lies in unmixed cells only, so the copy is on the side of `level` that all of its cells agree on.
+ *   Skeleton entries are never written.  Optionally exact (G, nx, ny, nz) bytes: 1 at skeleton and band points, 0 at filled ones.
+ *   active, point_index and positions are not looked at.  The number of band points lives on the device: the host cannot compare it
+ *   with max_points, which must be at least point_offsets[G].  values is never read at or beyond max_points; a band point whose row
+ *   is not there is filled like a point outside the band (exact 0).
+ * Workspace bytes = the sum of these regions, each rounded up to 256 bytes, with P = nx ny nz, B = ceil(P / 256), C = cx cy cz and
+ *   D = ceil(C / 256):  G C (mixed cells) + G C (active cells) + 2 x 4 G D (block sums of both) + 2 x 4 G B (block sums of the band
+ *   points and their scan) + 4 (the total).
+ * pr_band_plan: six kernel launches on `stream` (five when point_index and positions are NULL); pr_band_fill: one.  No memset, no
+ * memcpy, no allocation, no synchronisation: capturable into a HIP graph.  No atomics: the outputs are deterministic.
+ * Refused (PR_ERR_INVALID, before any device work; by pr_band_workspace_size too, except the workspace itself): NULL sigma, axis,
+ * point_offsets or counts, groups < 1, an extent < 2, stride or guard out of range, a NaN level, non-zero flags, a negative max_points,
+ * G nx ny nz >= 2^31, a NULL, misaligned or too small workspace; by pr_band_fill NULL values with max_points > 0.
+ */
+#define PR_BAND_MIN_STRIDE 2
+#define PR_BAND_MAX_STRIDE 64
+#define PR_BAND_MAX_GUARD 8
+typedef struct pr_band_t {
+    int32_t groups;              /* G >= 1 */
+    int32_t points[3];           /* lattice points per axis, each >= 2 */
+    float level;                 /* inside iff sigma > level; NaN refused */
+    uint32_t flags;              /* 0 */
+    int32_t stride;              /* PR_BAND_MIN_STRIDE .. PR_BAND_MAX_STRIDE */
+    int32_t guard;               /* 0 .. PR_BAND_MAX_GUARD */
+    int32_t max_points;          /* rows of point_index / positions (plan) or of values (fill), >= 0 */
+    uint32_t reserved_;
+    float* sigma;                /* (G, nx, ny, nz): read at the skeleton points; written by pr_band_fill everywhere else */
+    const float* axis[3];        /* (nx) (ny) (nz) coordinates, shared by the groups */
+    const float* values;         /* fill: (max_points) the field at the listed points; NULL only with max_points == 0 */
+    int32_t* point_offsets;      /* plan: (G + 1), always written */
+    int32_t* counts;             /* plan: (G, 4), always written */
+    uint8_t* active;             /* plan: (G, cx, cy, cz) or NULL */
+    int32_t* point_index;        /* plan: (max_points) or NULL */
+    float* positions;            /* plan: (max_points, 3) or NULL */
+    uint8_t* exact;              /* fill: (G, nx, ny, nz) or NULL */
+} pr_band_t;
+/* Host computation, no device work; refuses everything above that does not concern the workspace. */
+int pr_band_workspace_size(const pr_band_t* s, size_t* bytes);
+/* `workspace`: 256-byte aligned, pr_band_workspace_size bytes. */
+int pr_band_plan(const pr_band_t* s, void* workspace, size_t workspace_bytes, void* stream);
+int pr_band_fill(const pr_band_t* s, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Backward pass of pr_render_forward (what torch.autograd does for the reference's op graph when
  * training/trainer_backpropagated_autoencoder.py:349 calls total_loss.backward()).  The forward call must
  * have run with PR_FLAG_SAVE_FOR_BACKWARD (with or without PR_FLAG_TRAIN_BN) on the same `call`, `objects` and

@@ -12,7 +12,8 @@ Public surface (mirrors the reference's modules for the renderer hot path only):
                             EnvironmentModel.render_geometry_from_scene_encoding): per-object visibility, front object
   surface, Mesh             triangle meshes of density lattices on the device (marching tetrahedra: surface.extract_surface,
                             ObjectComposer.extract_mesh), with floater removal and capping on the same lattice
-                            (surface.label_components, surface.clean_lattice)
+                            (surface.label_components, surface.clean_lattice); surface.refine_band / ObjectComposer.density_band
+                            evaluate a lattice only in a band around the level set
   ray_sampling, wire_format pixel / ray samplers and the renderer <-> decoder tensor glue of the reference
   parallel                  frame shards, overlapped feature all-gather, gradient all-reduce (torch.distributed / RCCL)
   configs / synthetic       shipped renderer configurations and seeded synthetic scenes

@@ -208,6 +208,19 @@ class Components(C.Structure):
                 ("sizes", C.c_void_p), ("sigma_out", C.c_void_p), ("counts", C.c_void_p)]
 
 
+BAND_MIN_STRIDE = 2              # PR_BAND_MIN_STRIDE
+BAND_MAX_STRIDE = 64             # PR_BAND_MAX_STRIDE
+BAND_MAX_GUARD = 8               # PR_BAND_MAX_GUARD
+
+
+class Band(C.Structure):
+    """pr_band_t (include/playrender.h)."""
+    _fields_ = [("groups", C.c_int32), ("points", C.c_int32 * 3), ("level", C.c_float), ("flags", C.c_uint32), ("stride", C.c_int32),
+                ("guard", C.c_int32), ("max_points", C.c_int32), ("reserved_", C.c_uint32), ("sigma", C.c_void_p), ("axis", C.c_void_p * 3),
+                ("values", C.c_void_p), ("point_offsets", C.c_void_p), ("counts", C.c_void_p), ("active", C.c_void_p),
+                ("point_index", C.c_void_p), ("positions", C.c_void_p), ("exact", C.c_void_p)]
+
+
 # every exported symbol of include/playrender.h : (restype, argtypes)
 class SceneSetup(C.Structure):
     """pr_scene_setup_t (include/playrender.h)."""
@@ -246,6 +259,9 @@ SYMBOLS = {
     "pr_extract_surface": (C.c_int, [C.POINTER(Surface), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_components_workspace_size": (C.c_int, [C.POINTER(Components), C.POINTER(C.c_size_t)]),
     "pr_label_components": (C.c_int, [C.POINTER(Components), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pr_band_workspace_size": (C.c_int, [C.POINTER(Band), C.POINTER(C.c_size_t)]),
+    "pr_band_plan": (C.c_int, [C.POINTER(Band), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pr_band_fill": (C.c_int, [C.POINTER(Band), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_backward_workspace_size": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(C.c_size_t)]),
     "pr_render_backward": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(OutputGrads), C.POINTER(OutputGrads),
                                      C.POINTER(InputGrads), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -915,9 +915,41 @@ class ObjectComposer(Tracked, nn.Module):
         box = torch.as_tensor(model.model_config["bounding_box"], dtype=torch.float32, device=dev)
         return [box[a, 0] + (torch.arange(n[a], dtype=torch.float32, device=dev) + 0.5) * ((box[a, 1] - box[a, 0]) / n[a]) for a in range(3)]
 
+    def density_band(self, object_idx: int, resolution, style: torch.Tensor, deformation: torch.Tensor, *, level: float,
+                     stride: int = 4, guard: int = 1, fine: bool = False, canonical_pose: bool = False):
+        """``density_grid`` for a mesh at ``level``, with the network spent only near that level set: ``(sigma (G, nx, ny, nz),
+        centres (nx, ny, nz, 3), exact (G, nx, ny, nz) uint8, counts (G, 4))`` on ``density_grid``'s lattice.
+
+        One density-only ``query_object`` at the lattice's skeleton (every ``stride``-th point per axis and the last), then
+        ``surface.refine_band``: the points of the skeleton cells within ``guard`` cells of one that straddles ``level`` are queried
+        (one density-only ``query_object`` per group), all others receive a copy of a skeleton value of their cell.  ``exact`` is 1
+        where ``sigma`` is the network's value - there it equals ``density_grid``'s - and 0 where it is a copy; ``counts`` = cells,
+        mixed cells, active cells, band points per group.  AN APPROXIMATION: a feature thinner than ``stride`` that no skeleton cell
+        sees as mixed is lost, and ``guard`` does not help there.  One host synchronisation (the band sizes).  Skybox models are
+        refused, as by ``density_grid``."""
+        self._occupancy_model(object_idx, "fine" if fine else "coarse")
+        n = [int(resolution)] * 3 if isinstance(resolution, int) else [int(v) for v in resolution]
+        if len(n) != 3 or min(n) < 2:
+            raise ValueError(f"resolution must be an integer >= 2 or three of them, got {resolution!r}")
+        if not 0 <= int(guard) <= _lib.BAND_MAX_GUARD:
+            raise ValueError(f"guard must be in 0..{_lib.BAND_MAX_GUARD}, got {guard}")
+        dev = style.device
+        axes = self._grid_axes(object_idx, n, fine, dev)
+        index = [torch.tensor(_surface.skeleton_indices(n[a], stride), device=dev) for a in range(3)]      # (refuses a bad stride)
+        skeleton = torch.stack(torch.meshgrid(*[axes[a][index[a]] for a in range(3)], indexing="ij"), dim=-1)
+        G = style.size(0)
+        query = dict(fine=fine, canonical_pose=canonical_pose, features=False)
+        out = self.query_object(object_idx, skeleton.reshape(1, -1, 3).expand(G, -1, 3), style, deformation, **query)
+        sigma = torch.zeros([G] + n, dtype=torch.float32, device=dev)
+        sigma[:, index[0][:, None, None], index[1][None, :, None], index[2][None, None, :]] = out["sigma"].reshape([G] + list(skeleton.shape[:3]))
+        sigma, exact, counts = _surface.refine_band(
+            sigma, axes, level, stride=stride, guard=guard,
+            evaluate=lambda g, positions: self.query_object(object_idx, positions, style[g], deformation[g], **query)["sigma"])
+        return sigma, self._grid_centres(object_idx, n, fine, dev), exact, counts
+
     def extract_mesh(self, object_idx: int, resolution, style: torch.Tensor, deformation: torch.Tensor, *, level: float,
                      fine: bool = False, canonical_pose: bool = False, normals: bool = True, features: bool = False,
-                     keep_largest: int = 0, min_points: int = 0, close_border: bool = False):
+                     keep_largest: int = 0, min_points: int = 0, close_border: bool = False, stride: int = 0, guard: int = 1):
         """Triangle meshes of the density field of object ``object_idx`` in its OBJECT frame: ``density_grid`` at the composer's
         ``precision``, then ``surface.extract_surface`` (marching tetrahedra on the device) on the lattice of voxel centres.  One
         ``surface.Mesh`` per row of ``style (G, S)`` / ``deformation (G, D)``.
@@ -928,8 +960,16 @@ class ObjectComposer(Tracked, nn.Module):
         One host synchronisation (the mesh sizes).  Skybox models are refused, as by ``density_grid``.
 
         ``keep_largest`` / ``min_points`` / ``close_border`` are ``surface.extract_surface``'s: the lattice is cleaned of floaters and
-        capped at the box before it is meshed (``surface.clean_lattice``); at their defaults nothing changes."""
-        sigma, _ = self.density_grid(object_idx, resolution, style, deformation, fine=fine, canonical_pose=canonical_pose)
+        capped at the box before it is meshed (``surface.clean_lattice``); at their defaults nothing changes.
+
+        ``stride`` > 0: the lattice comes from ``density_band`` at this ``level`` (``stride``, ``guard``) - the network runs on a coarse
+        skeleton and near the surface only, an approximation that can lose features thinner than ``stride`` (``density_band``).  At
+        ``stride=0`` (the default) the lattice is ``density_grid``'s."""
+        if stride:
+            sigma = self.density_band(object_idx, resolution, style, deformation, level=level, stride=stride, guard=guard, fine=fine,
+                                      canonical_pose=canonical_pose)[0]
+        else:
+            sigma, _ = self.density_grid(object_idx, resolution, style, deformation, fine=fine, canonical_pose=canonical_pose)
         axes = self._grid_axes(object_idx, list(sigma.shape[1:]), fine, sigma.device)
         meshes = _surface.extract_surface(sigma, axes, level, normals=normals, keep_largest=keep_largest, min_points=min_points,
                                           close_border=close_border)

@@ -10,6 +10,9 @@ so results can be compared bit for bit.  There is no CPU fallback.
 ``label_components`` / ``clean_lattice`` (``pr_label_components``) label the connected components of the inside set on the same
 lattice and blank out the unwanted ones: floater removal (``keep_largest``, ``min_points``) and capping (``close_border``) in front of
 the mesher and of ``pr_occupancy_build``.
+
+``refine_band`` (``pr_band_plan`` / ``pr_band_fill``) fills a lattice from its coarse skeleton and evaluates the field only in a band
+around the level set - the opt-in approximation behind ``ObjectComposer.density_band`` and ``extract_mesh(stride=...)``.
 """
 from __future__ import annotations
 
@@ -152,6 +155,110 @@ def clean_lattice(sigma: torch.Tensor, level: float, *, keep_largest: int = 0, m
     counts = _run_components(sigma, level, sigma_out=out, keep_largest=keep_largest, min_points=min_points, close_border=close_border,
                              fill=fill)
     return out, counts
+
+
+def skeleton_indices(n: int, stride: int) -> List[int]:
+    """The skeleton indices of an axis of ``n`` lattice points (``pr_band_t``): ``0, stride, 2 stride, ...`` below ``n``, plus
+    ``n - 1`` if it is not among them."""
+    n, stride = int(n), int(stride)
+    if n < 2:
+        raise ValueError(f"a lattice has at least 2 points per axis, got {n}")
+    if not _lib.BAND_MIN_STRIDE <= stride <= _lib.BAND_MAX_STRIDE:
+        raise ValueError(f"stride must be in {_lib.BAND_MIN_STRIDE}..{_lib.BAND_MAX_STRIDE}, got {stride}")
+    idx = list(range(0, n, stride))
+    if idx[-1] != n - 1:
+        idx.append(n - 1)
+    return idx
+
+
+def band_struct(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float, stride: int, guard: int, point_offsets: torch.Tensor,
+                counts: torch.Tensor, *, active: Optional[torch.Tensor] = None, point_index: Optional[torch.Tensor] = None,
+                positions: Optional[torch.Tensor] = None, values: Optional[torch.Tensor] = None, exact: Optional[torch.Tensor] = None,
+                max_points: Optional[int] = None) -> _lib.Band:
+    """``pr_band_t`` over prepared tensors (fp32 / int32 / uint8, contiguous, one device); ``max_points=None``: the rows of the first
+    of ``point_index``, ``positions``, ``values`` that is given (0 without any)."""
+    b = _lib.Band()
+    b.groups = sigma.size(0)
+    for a in range(3):
+        b.points[a] = sigma.size(1 + a)
+        b.axis[a] = axes[a].data_ptr()
+    b.level = float(level)
+    b.stride = int(stride)
+    b.guard = int(guard)
+    if max_points is None:
+        rows = [t.size(0) for t in (point_index, positions, values) if t is not None]
+        max_points = rows[0] if rows else 0
+    b.max_points = int(max_points)
+    b.sigma = sigma.data_ptr()
+    b.point_offsets = point_offsets.data_ptr()
+    b.counts = counts.data_ptr()
+    for name, t in (("active", active), ("point_index", point_index), ("positions", positions), ("values", values), ("exact", exact)):
+        setattr(b, name, None if t is None or t.numel() == 0 else t.data_ptr())
+    return b
+
+
+def refine_band(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float, *, stride: int, guard: int = 1, evaluate):
+    """Fills a lattice of which only the skeleton is known, spending ``evaluate`` only in a band around the level set
+    (``pr_band_plan`` / ``pr_band_fill``, include/playrender.h).
+
+    ``sigma (G, nx, ny, nz)`` (device tensor, z fastest) holds the field at its skeleton points - ``skeleton_indices`` per axis, every
+    ``stride``-th point and the last; all other entries are ignored.  A skeleton cell whose 8 corners are not all on one side of
+    ``level`` is mixed; every non-skeleton point of a cell within ``guard`` cells of a mixed one is evaluated:
+    ``evaluate(g, positions (M, 3)) -> (M,)`` is the caller's field for group ``g`` (called for the groups that have points).  Every other
+    point receives a copy of a skeleton value of its cell, which is on the right side of ``level`` as far as the skeleton can tell.
+
+    AN APPROXIMATION: a feature thinner than ``stride`` that no skeleton cell sees as mixed is lost, whatever ``guard`` is.  With
+    ``guard >= 1`` and a surface the skeleton does see, the mesh of the result (positions, triangles and normals) is the mesh of the
+    dense lattice.
+
+    Three calls on the current stream: a counting plan call, then - after reading ``point_offsets`` back, the ONE host
+    synchronisation of this function - an emitting one into exactly sized tensors, the evaluations, the fill.  Returns
+    ``(sigma, exact, counts)``: the filled lattice (a new tensor), ``exact (G, nx, ny, nz)`` uint8 - 1 where the value is the field's
+    own (skeleton and band), 0 where it is a copy - and ``counts (G, 4)`` int32 = cells, mixed cells, active cells, band points."""
+    if not sigma.is_cuda:
+        raise RuntimeError(NO_CPU)
+    if sigma.dim() != 4:
+        raise ValueError(f"sigma must be (G, nx, ny, nz), got {list(sigma.shape)}")
+    if len(axes) != 3:
+        raise ValueError("axes must be the three coordinate vectors of the lattice")
+    if not _lib.BAND_MIN_STRIDE <= int(stride) <= _lib.BAND_MAX_STRIDE:
+        raise ValueError(f"stride must be in {_lib.BAND_MIN_STRIDE}..{_lib.BAND_MAX_STRIDE}, got {stride}")
+    if not 0 <= int(guard) <= _lib.BAND_MAX_GUARD:
+        raise ValueError(f"guard must be in 0..{_lib.BAND_MAX_GUARD}, got {guard}")
+    dev = sigma.device
+    sigma = sigma.detach().to(torch.float32).contiguous().clone()
+    axes = [torch.as_tensor(a).detach().to(device=dev, dtype=torch.float32).contiguous() for a in axes]
+    for a in range(3):
+        if axes[a].dim() != 1 or axes[a].numel() != sigma.size(1 + a):
+            raise ValueError(f"axes[{a}] must hold {sigma.size(1 + a)} coordinates, got {list(axes[a].shape)}")
+    G = sigma.size(0)
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        point_offsets = torch.empty(G + 1, dtype=torch.int32, device=dev)
+        counts = torch.empty((G, 4), dtype=torch.int32, device=dev)
+        count = band_struct(sigma, axes, level, stride, guard, point_offsets, counts)
+        size = C.c_size_t()
+        _lib.check(lib.pr_band_workspace_size(C.byref(count), C.byref(size)), "pr_band_workspace_size")
+        workspace = torch.empty(size.value, dtype=torch.uint8, device=dev)
+        _lib.check(lib.pr_band_plan(C.byref(count), workspace.data_ptr(), size.value, stream), "pr_band_plan")
+        offsets = point_offsets.cpu().tolist()                               # (the host synchronisation)
+        rows = offsets[G]
+        positions = torch.empty((rows, 3), dtype=torch.float32, device=dev)
+        values = torch.empty(rows, dtype=torch.float32, device=dev)
+        if rows > 0:
+            emit = band_struct(sigma, axes, level, stride, guard, point_offsets, counts, positions=positions)
+            _lib.check(lib.pr_band_plan(C.byref(emit), workspace.data_ptr(), size.value, stream), "pr_band_plan")
+            for g in range(G):
+                if offsets[g + 1] > offsets[g]:
+                    got = evaluate(g, positions[offsets[g]:offsets[g + 1]])
+                    if got.numel() != offsets[g + 1] - offsets[g]:
+                        raise ValueError(f"evaluate({g}, ...) returned {list(got.shape)} for {offsets[g + 1] - offsets[g]} positions")
+                    values[offsets[g]:offsets[g + 1]] = got.detach().reshape(-1).to(device=dev, dtype=torch.float32)
+        exact = torch.empty(sigma.shape, dtype=torch.uint8, device=dev)
+        fill = band_struct(sigma, axes, level, stride, guard, point_offsets, counts, values=values, exact=exact)
+        _lib.check(lib.pr_band_fill(C.byref(fill), workspace.data_ptr(), size.value, stream), "pr_band_fill")
+    return sigma, exact, counts
 
 
 def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float, *, normals: bool = True, keep_largest: int = 0,
