@@ -25,6 +25,11 @@ struct CompositeSmem {
     int* sl;        // compact feature row per entry (-1: outside the box)
     unsigned int* key;   // entry index per merged rank
 };
+// The feature pass reuses key / tt / al for its compacted lists (row, own weight, global weight): the ranks, the depths and the
+// sorted-order weights are dead behind the barrier that ends the global pass (wg and the outputs have been written from them).  A list
+// occupies entries of its own (object, part) only, so lists never overlap; what the compaction reads - sl, wo, wg (the storage of sg) -
+// are three other arrays, never written in that pass.  Hence neither the shared pass nor pooled_row_sums needs a barrier between a
+// wave's compaction and its reads.
 
 constexpr int MAX_FCHUNK = 4;  // F <= 256 channels, 64 lanes
 
@@ -122,6 +127,115 @@ __device__ __forceinline__ void store_channel_sums(float (&acc)[MAX_FCHUNK], flo
         for (int c = 0; c < MAX_FCHUNK; ++c) {
             const int ch = lane + 64 * c;
             if (ch < F) dst[ch] = acc[c];
+        }
+    }
+}
+
+constexpr int POOLED_ROWS_IN_FLIGHT = 8;   // as above, for the per-object pass of the deferred calls (four channels per lane and row)
+
+// Feature pass of the deferred calls (p.pooled, CW > 1): every sum of such a call belongs to ONE object - its rows under its own
+// weights go to pooled[2 k], under the global weights to pooled[2 k + 1] - so object k is the business of wave k % CW alone: no
+// cross-wave sum, no scratch, no barrier.  The wave walks the object's parts j = 0, 1, ... - [j part, (j + 1) part), the ranges the
+// waves 0, 1, ... own in the shared pass of k_composite - compacts each part and sums it from a fresh pair of accumulators in list
+// order, then folds the parts in part order: tot = part 0, tot = tot + part 1, ...  That is the shared pass's wave-order sum, bit for
+// bit.  A part that does not exist (j part >= P: the waves beyond the list in the shared pass) is skipped; exact, because an
+// accumulator that starts at +0 and only ever adds never becomes -0 (+0 + -0 = +0 under round-to-nearest), so the `+ 0.0f` the shared
+// pass spends on such a wave changes no bit.
+// A row is F floats, F a multiple of 4 (launch_projection requires it), rows and pooled blocks are 16-byte aligned (the workspace
+// plan aligns every array to 256 bytes): lane l < F / 4 reads the channels 4 l .. 4 l + 3 of a row as one 16-byte load.  Every
+// channel keeps its own chain acc = acc + w * v over the list.
+// LDS: the part lists go to key / tt / al at [off + j part, off + j part + count), inside the entries of this (object, part), so the
+// lists of different waves never overlap; sl / wo / wg (= sg), which the compaction reads, are other arrays.  See CompositeSmem.
+template <int CW>
+__device__ __forceinline__ void pooled_row_sums(const CompositeParams& p, const CompositeSmem& sm, const long g, const int wave, const int lane) {
+    // the four channels of a lane as one vector (two packed operations each): a product is rounded, then the sum - never fused
+#pragma clang fp contract(off)
+    const int F = p.F;
+    const bool owner = 4 * lane < F;       // this lane holds four channels
+    const int col4 = owner ? lane : 0;     // (the other lanes read lane 0's channels again - no divergent load - and store nothing)
+    const bool want_global = p.global.integrated_features || p.decoder.groups > 0;
+    int* lrow = reinterpret_cast<int*>(sm.key);
+    float* lw1 = sm.tt;
+    float* lw2 = sm.al;
+    int off = 0;
+#pragma unroll 1
+    for (int k = 0; k < p.objects; off += p.obj[k].positions, ++k) {
+        if (k % CW != wave) continue;
+        const CompositeObject& o = p.obj[k];
+        const int P = o.positions;
+        const int part = (((P + CW - 1) / CW) + 63) & ~63;
+        f32x4_t toto = {0.f, 0.f, 0.f, 0.f}, totg = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll 1
+        for (int begin = 0; begin < P; begin += part) {
+            const int end = (begin + part < P) ? begin + part : P;
+            int count = 0;
+#pragma unroll 1
+            for (int base = begin; base < end; base += 64) {
+                const int i = base + lane;
+                bool take = false;
+                int row = -1;
+                float w1 = 0.f, w2 = 0.f;
+                if (i < end) {
+                    row = sm.sl[off + i];
+                    w1 = sm.wo[off + i];
+                    w2 = sm.wg[off + i];
+                    take = row >= 0 && (w1 != 0.f || w2 != 0.f);
+                }
+                const unsigned long long m = __ballot(take);
+                if (take) {
+                    const int pos = off + begin + count + __popcll(m & ((1ull << lane) - 1ull));
+                    lrow[pos] = row;
+                    lw1[pos] = w1;
+                    lw2[pos] = w2;
+                }
+                count += __popcll(m);
+            }
+            // (the list is written and read by this wave only: no barrier needed in between)
+            const int* rows_w = lrow + off + begin;
+            const float* w1_w = lw1 + off + begin;
+            const float* w2_w = lw2 + off + begin;
+            f32x4_t acco = {0.f, 0.f, 0.f, 0.f}, accg = {0.f, 0.f, 0.f, 0.f};
+            int i = 0;
+#pragma unroll 1
+            for (; i + POOLED_ROWS_IN_FLIGHT <= count; i += POOLED_ROWS_IN_FLIGHT) {
+                // lane u < POOLED_ROWS_IN_FLIGHT fetches list entry i + u; the entries are handed round as scalars, so a row address is a
+                // scalar base plus this lane's 16 bytes and the weights need no vector register per row
+                const int u0 = lane < POOLED_ROWS_IN_FLIGHT ? lane : 0;
+                const int row_l = rows_w[i + u0];
+                const int w1_l = __float_as_int(w1_w[i + u0]), w2_l = __float_as_int(w2_w[i + u0]);
+                f32x4_t v[POOLED_ROWS_IN_FLIGHT];
+#pragma unroll
+                for (int u = 0; u < POOLED_ROWS_IN_FLIGHT; ++u) {
+                    const float* row = o.feat + (size_t)__builtin_amdgcn_readlane(row_l, u) * F;
+                    v[u] = as_global(reinterpret_cast<const f32x4_t*>(row))[col4];
+                }
+#pragma unroll
+                for (int u = 0; u < POOLED_ROWS_IN_FLIGHT; ++u) {
+                    const float w1 = __int_as_float(__builtin_amdgcn_readlane(w1_l, u)), w2 = __int_as_float(__builtin_amdgcn_readlane(w2_l, u));
+                    acco = acco + v[u] * w1;
+                    accg = accg + v[u] * w2;
+                }
+            }
+#pragma unroll 1
+            for (; i < count; ++i) {
+                const float* row = o.feat + (size_t)__builtin_amdgcn_readfirstlane(rows_w[i]) * F;
+                const f32x4_t v = as_global(reinterpret_cast<const f32x4_t*>(row))[col4];
+                const float w1 = w1_w[i], w2 = w2_w[i];
+                acco = acco + v * w1;
+                accg = accg + v * w2;
+            }
+            if (begin == 0) {
+                toto = acco;
+                totg = accg;
+            } else {
+                toto = toto + acco;
+                totg = totg + accg;
+            }
+        }
+        if (owner) {
+            float* own = p.pooled + ((size_t)(2 * k) * gridDim.x + g) * F + 4 * lane;
+            if (o.out.integrated_features) *as_global(reinterpret_cast<f32x4_t*>(own)) = toto;
+            if (want_global) *as_global(reinterpret_cast<f32x4_t*>(own + (size_t)gridDim.x * F)) = totg;
         }
     }
 }
@@ -347,6 +461,12 @@ __global__ __launch_bounds__(64 * CW) void k_composite(CompositeParams p) {
         return;
     }
 
+    // ---- features of a deferred call: one object per wave (the barrier above is the only one this pass needs: wo, wg, sl are complete)
+    if (CW > 1 && p.pooled != nullptr) {
+        pooled_row_sums<CW>(p, sm, g, wave, lane);
+        return;       // (the global features and the decoder maps are written by the projection kernel)
+    }
+
     // ---- features: one pass over the compact MLP rows --------------------------------------------
     // Per object the contributing samples (inside the box, non-zero weight) are compacted into per-wave lists (wave w
     // takes the w-th contiguous part of the object's samples; the sort keys are dead by now, their storage is reused),
@@ -538,9 +658,42 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int PJ_ROWS = 64;
 constexpr int PJ_KMAX = MAX_WIDTH / 2 + 8;        // projection_k(W / 2) <= this
 constexpr int PJ_LDA = PJ_KMAX + 4;
+constexpr int PJ_TILE = PJ_ROWS * PJ_LDA;          // floats of one staged 64-ray tile
+constexpr int PJ_LDS_BYTES = 2 * PJ_TILE * (int)sizeof(float);   // object k under its own and under the global weights: 70 KB, two workgroups per CU
 
-__global__ __launch_bounds__(256) void k_project_features(CompositeParams p) {
-    __shared__ __attribute__((aligned(16))) float SA[PJ_ROWS * PJ_LDA];
+// 64 pooled rows of one block, zero-padded to the K step and beyond the last ray, into LDS
+__device__ __forceinline__ void stage_pooled_tile(float* S, const float* A, long row0, long total, int HW, int k4, int tid) {
+    for (int idx = tid; idx < PJ_ROWS * k4; idx += 256) {
+        const int row = idx / k4, c = (idx - row * k4) * 4;
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (row0 + row < total && c < HW) v = *reinterpret_cast<const float4*>(A + (size_t)row * HW + c);
+        *reinterpret_cast<float4*>(S + row * PJ_LDA + c) = v;
+    }
+}
+
+// One K step (8 floats of K: this lane's four) of a wave's 64 x 32 block: both row blocks against the weight fragment w.
+__device__ __forceinline__ void project_step(f32x16 (&acc)[2], const float* a, const f32x4_t w) {
+    const float4 x0 = *reinterpret_cast<const float4*>(a);
+    const float4 x1 = *reinterpret_cast<const float4*>(a + 32 * PJ_LDA);
+    acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.x, w.x, acc[0], 0, 0, 0);
+    acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.x, w.x, acc[1], 0, 0, 0);
+    acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.y, w.y, acc[0], 0, 0, 0);
+    acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.y, w.y, acc[1], 0, 0, 0);
+    acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.z, w.z, acc[0], 0, 0, 0);
+    acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.z, w.z, acc[1], 0, 0, 0);
+    acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.w, w.w, acc[0], 0, 0, 0);
+    acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.w, w.w, acc[1], 0, 0, 0);
+}
+
+// Objects in order; object k's two pooled tiles (own weights, global weights) are staged together and multiplied off the SAME weight
+// fragments - one pass over [W6 | b6] of the object's model feeds the object's own accumulators (fresh per object) and the global
+// accumulators (one chain over the objects) - with the fragment of the next K step loaded before the current one is consumed.  Every
+// accumulator sees its products in the order it always did: objects ascending (global), q ascending, x, y, z, w inside a step.
+// 128 accumulator registers and two workgroups per CU (launch bounds): one workgroup's staging and stores hide behind the other's MFMAs.
+__global__ __launch_bounds__(256, 2) void k_project_features(CompositeParams p) {
+    extern __shared__ __attribute__((aligned(16))) float pj_smem[];
+    float* SO = pj_smem;              // object k's pooled rows under its own weights
+    float* SG = pj_smem + PJ_TILE;    // ... under the global weights
     const int tid = threadIdx.x, lane = tid & 63, r = lane & 31, half = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const long total = (long)p.frames * p.rays;
@@ -549,74 +702,85 @@ __global__ __launch_bounds__(256) void k_project_features(CompositeParams p) {
     const int nblk = (F + 31) / 32;
     const int k4 = PK >> 2;
     const bool want_global = p.global.integrated_features != nullptr || p.decoder.groups > 0;
-    for (int set = 0; set <= p.objects; ++set) {          // the objects' own features, then the global ones
-        const bool global = set == p.objects;
-        float* out = global ? p.global.integrated_features : p.obj[set].out.integrated_features;
-        if (global ? !want_global : out == nullptr) continue;
-        f32x16 acc[2][2];
+    f32x16 accg[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b)
+#pragma unroll
+            for (int i = 0; i < 16; ++i) accg[a][b][i] = 0.f;
+    for (int k = 0; k < p.objects; ++k) {
+        float* out = p.obj[k].out.integrated_features;
+        const bool own = out != nullptr;
+        if (!own && !want_global) continue;
+        __syncthreads();     // the previous object's products have finished reading the tiles
+        if (own) stage_pooled_tile(SO, p.pooled + ((size_t)(2 * k) * total + row0) * HW, row0, total, HW, k4, tid);
+        if (want_global) stage_pooled_tile(SG, p.pooled + ((size_t)(2 * k + 1) * total + row0) * HW, row0, total, HW, k4, tid);
+        __syncthreads();
+        f32x16 acco[2][2];
 #pragma unroll
         for (int a = 0; a < 2; ++a)
 #pragma unroll
             for (int b = 0; b < 2; ++b)
 #pragma unroll
-                for (int i = 0; i < 16; ++i) acc[a][b][i] = 0.f;
-        const int kfirst = global ? 0 : set, klast = global ? p.objects - 1 : set;
-        for (int k = kfirst; k <= klast; ++k) {
-            const float* A = p.pooled + ((size_t)(2 * k + (global ? 1 : 0)) * total + row0) * HW;
-            __syncthreads();     // the previous product has finished reading the tile
-            for (int idx = tid; idx < PJ_ROWS * k4; idx += 256) {
-                const int row = idx / k4, c = (idx - row * k4) * 4;
-                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-                if (row0 + row < total && c < HW) v = *reinterpret_cast<const float4*>(A + (size_t)row * HW + c);
-                *reinterpret_cast<float4*>(SA + row * PJ_LDA + c) = v;
+                for (int i = 0; i < 16; ++i) acco[a][b][i] = 0.f;
+        const float* W = p.proj_w[k];
+        const int a0 = r * PJ_LDA + 4 * half;
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk) {
+            const int cb = wave + 4 * blk;
+            if (cb >= nblk) continue;
+            const auto* wp = as_global(reinterpret_cast<const f32x4_t*>(W + (size_t)(cb * 32 + r) * PK + 4 * half));
+            f32x4_t w = wp[0];
+            for (int q = 0; q < k4; q += 2) {
+                const f32x4_t w_next = wp[q + 2 < k4 ? q + 2 : q];      // (the last step reads its own fragment again)
+                if (own) project_step(acco[blk], SO + a0 + 4 * q, w);
+                if (want_global) project_step(accg[blk], SG + a0 + 4 * q, w);
+                w = w_next;
             }
-            __syncthreads();
-            const float* W = p.proj_w[k];
-            const float* a0 = SA + r * PJ_LDA + 4 * half;
+        }
+        // accumulator element i of lane (r, half): tile row (i & 3) + 8 (i >> 2) + 4 half (+ 32 for the second row block), column r - the
+        // 32 lanes of a half write 128 consecutive bytes of a row
+        if (own) {
 #pragma unroll
             for (int blk = 0; blk < 2; ++blk) {
-                const int cb = wave + 4 * blk;
-                if (cb >= nblk) continue;
-                const auto* wp = as_global(reinterpret_cast<const f32x4_t*>(W + (size_t)(cb * 32 + r) * PK + 4 * half));
-                for (int q = 0; q < k4; q += 2) {
-                    const f32x4_t w = wp[q];
-                    const float4 x0 = *reinterpret_cast<const float4*>(a0 + 4 * q);
-                    const float4 x1 = *reinterpret_cast<const float4*>(a0 + 32 * PJ_LDA + 4 * q);
-                    acc[blk][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.x, w.x, acc[blk][0], 0, 0, 0);
-                    acc[blk][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.x, w.x, acc[blk][1], 0, 0, 0);
-                    acc[blk][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.y, w.y, acc[blk][0], 0, 0, 0);
-                    acc[blk][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.y, w.y, acc[blk][1], 0, 0, 0);
-                    acc[blk][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.z, w.z, acc[blk][0], 0, 0, 0);
-                    acc[blk][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.z, w.z, acc[blk][1], 0, 0, 0);
-                    acc[blk][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.w, w.w, acc[blk][0], 0, 0, 0);
-                    acc[blk][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.w, w.w, acc[blk][1], 0, 0, 0);
+                const int col = (wave + 4 * blk) * 32 + r;
+                if (col >= F) continue;
+#pragma unroll
+                for (int rb = 0; rb < 2; ++rb) {
+#pragma unroll
+                    for (int i = 0; i < 16; ++i) {
+                        const long g = row0 + 32 * rb + (i & 3) + 8 * (i >> 2) + 4 * half;
+                        if (g < total) out[(size_t)g * F + col] = acco[blk][rb][i];
+                    }
                 }
             }
         }
-        // accumulator element i of lane (r, half): tile row (i & 3) + 8 (i >> 2) + 4 half (+ 32 for the second row block), column r
+    }
+    if (!want_global) return;
+    float* out = p.global.integrated_features;
 #pragma unroll
-        for (int blk = 0; blk < 2; ++blk) {
-            const int col = (wave + 4 * blk) * 32 + r;
-            if (col >= F) continue;
+    for (int blk = 0; blk < 2; ++blk) {
+        const int col = (wave + 4 * blk) * 32 + r;
+        if (col >= F) continue;
 #pragma unroll
-            for (int rb = 0; rb < 2; ++rb) {
+        for (int rb = 0; rb < 2; ++rb) {
 #pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const long g = row0 + 32 * rb + (i & 3) + 8 * (i >> 2) + 4 * half;
-                    if (g >= total) continue;
-                    const float v = acc[blk][rb][i];
-                    if (out) out[(size_t)g * F + col] = v;
-                    if (global && p.decoder.groups > 0) {
-                        // decoder layout: this ray is cell (r / width, r % width) of its group's grid (see k_composite)
-                        const int frame = (int)(g / p.rays);
-                        int rr = (int)(g - (long)frame * p.rays);
-                        int grp = 0;
-                        while (grp < p.decoder.groups - 1 && rr >= p.decoder.rays[grp]) rr -= p.decoder.rays[grp++];
-                        const int c0 = p.decoder.channel_begin[grp], c1 = p.decoder.channel_end[grp];
-                        const size_t cells = (size_t)p.decoder.rays[grp];
-                        float* map = p.decoder.map[grp] + (size_t)frame * (c1 - c0) * cells + rr;
-                        if (col >= c0 && col < c1) map[(size_t)(col - c0) * cells] = v;
-                    }
+            for (int i = 0; i < 16; ++i) {
+                const long g = row0 + 32 * rb + (i & 3) + 8 * (i >> 2) + 4 * half;
+                if (g >= total) continue;
+                const float v = accg[blk][rb][i];
+                if (out) out[(size_t)g * F + col] = v;
+                if (p.decoder.groups > 0) {
+                    // decoder layout: this ray is cell (r / width, r % width) of its group's grid (see k_composite)
+                    const int frame = (int)(g / p.rays);
+                    int rr = (int)(g - (long)frame * p.rays);
+                    int grp = 0;
+                    while (grp < p.decoder.groups - 1 && rr >= p.decoder.rays[grp]) rr -= p.decoder.rays[grp++];
+                    const int c0 = p.decoder.channel_begin[grp], c1 = p.decoder.channel_end[grp];
+                    const size_t cells = (size_t)p.decoder.rays[grp];
+                    float* map = p.decoder.map[grp] + (size_t)frame * (c1 - c0) * cells + rr;
+                    if (col >= c0 && col < c1) map[(size_t)(col - c0) * cells] = v;
                 }
             }
         }
@@ -631,7 +795,8 @@ int launch_projection(const CompositeParams& p, hipStream_t s) {
     for (int k = 0; k < p.objects; ++k) PR_REQUIRE(p.proj_w[k] != nullptr, "deferred projection: object %d has no packed matrix", k);
     const long total = (long)p.frames * p.rays;
     ProfileScope scope(1, s);
-    hipLaunchKernelGGL(k_project_features, dim3((unsigned)((total + PJ_ROWS - 1) / PJ_ROWS)), dim3(256), 0, s, p);
+    PR_TRY(prepare_kernel(reinterpret_cast<const void*>(&k_project_features), PJ_LDS_BYTES, nullptr));
+    hipLaunchKernelGGL(k_project_features, dim3((unsigned)((total + PJ_ROWS - 1) / PJ_ROWS)), dim3(256), PJ_LDS_BYTES, s, p);
     PR_LAUNCH_CHECK();
     return PR_OK;
 }
