@@ -605,7 +605,6 @@ bool group_active(const pr_call_t& c);
 bool group_train_active(const pr_call_t& c);
 bool gate_active(const pr_call_t& c);
 bool defer_active(const pr_call_t& c, const pr_object_t* objs);
-bool group_active(const pr_call_t& c);
 int make_plan(const pr_call_t& c, const pr_object_t* objs, Plan* plan);
 void bbox_split(const pr_object_model_t& m, float* lo, float* hi, float* size);
 int build_mlp_layers(const pr_object_model_t& m, const ModelDims& d, const PackedLayout& l, const float* base,

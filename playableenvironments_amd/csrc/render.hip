@@ -116,9 +116,6 @@ void set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
-int build_mlp_layers(const pr_object_model_t& m, const ModelDims& d, const PackedLayout& l, const float* base,
-                     MlpParams* p, bool split3);
-
 // ---------------------------------------------------------------------------------------------
 // Workspace plan (structs in pr_common.h)
 // ---------------------------------------------------------------------------------------------
@@ -287,7 +284,7 @@ int make_plan(const pr_call_t& c, const pr_object_t* objs, Plan* plan) {
         PR_TRY(compute_dims(objs[0].coarse, &d0));
         plan->pooled = take(sizeof(float) * 2 * (size_t)c.objects * nr * hidden_row_floats(d0.W2));
     }
-    if (c.flags & (PR_FLAG_TRAIN_BN | PR_FLAG_SAVE_FOR_BACKWARD)) {   // the phased launch structure (see render())
+    if (c.flags & (PR_FLAG_TRAIN_BN | PR_FLAG_SAVE_FOR_BACKWARD)) {   // the phased launch structure (see make_train_job)
         plan->h1 = take(sizeof(float) * max_cap * MAX_WIDTH);
         plan->h2 = take(sizeof(float) * max_cap * (MAX_WIDTH / 2 + 32));
         plan->row_flags = take(sizeof(int32_t) * max_cap);
@@ -397,526 +394,585 @@ static int validate_guide(const pr_call_t& c, const pr_object_t* objs, const pr_
     return PR_OK;
 }
 
-static int render(const pr_call_t& c, const pr_object_t* objs, const pr_occupancy_t* occupancy, const RetainCtx* rc,
-                  const pr_fine_guide_t* guide, const GuidePlan* gplan, const pr_outputs_t* outs[2], const pr_geometry_t* geos[2],
-                  char* ws, const Plan& plan, hipStream_t s) {
-    const int ntypes = c.use_fine ? 2 : 1;
-    const int K = c.objects;
-    // geometry-only call: density-only MLP launches (none for a skybox model), compositing ends behind the global weights
-    const bool geo = (c.flags & PR_FLAG_GEOMETRY_ONLY) != 0;
-    // retention: the first launches compare the cached keys with this call's inputs and set the reuse flags
-    if (rc) PR_TRY(launch_retain_probe(c, objs, *rc, s));
-    int32_t* block_sums_all = reinterpret_cast<int32_t*>(ws + plan.block_sums);
-    int32_t* block_offsets_all = reinterpret_cast<int32_t*>(ws + plan.block_offsets);
-    // coarse placement / block scan / compaction of several objects: three launches for all of them
-    const bool place_grouped = c.objects > 1 && ((c.flags & PR_FLAG_SAVE_FOR_BACKWARD) || group_active(c));   // (every object has its own sample records)
-    static thread_local PlaceParams place_jobs[PR_MAX_OBJECTS];
-    static thread_local FillParams fill_jobs[PR_MAX_OBJECTS];
-    int32_t* total_ptrs[PR_MAX_OBJECTS];
-    float* rec_pos = reinterpret_cast<float*>(ws + plan.rec_pos);
-    int32_t* rec_flat = reinterpret_cast<int32_t*>(ws + plan.rec_flat);
-    const bool naive = (c.flags & PR_FLAG_NAIVE_MLP) != 0;
-    const bool gate = gate_active(c);
-    const bool defer = defer_active(c, objs);
-    const bool grouped = group_active(c);
-    MlpParams jobs[PR_MAX_OBJECTS];
-    int job_rows[PR_MAX_OBJECTS];
-    FoldParams fold_jobs[PR_MAX_OBJECTS];
-    int sigma_jobs = 0;          // geometry-only calls: the grouped jobs of a level (skybox models are left out), packed in object order
-    // differentiable calls with several objects: phase 1 of every object (the whole network up to the first BatchNorm) runs as
-    // one grouped launch too; what follows it per object (statistics, head phases, divergence) is deferred until after it
-    const bool train_grouped = group_train_active(c);
-    struct TrainJob {
-        MlpParams mp; FoldParams fo; ModelDims d; const pr_object_model_t* m; const SavedPlan* sv;
-        double* stats; int32_t* stat_count; float* batch; float* h1; float* h2; float* rec_pos; int32_t* rec_flat;
-        int k, P, max_tiles; bool frozen, save;
-    };
-    static thread_local TrainJob train_jobs[PR_MAX_OBJECTS];
+// ---------------------------------------------------------------------------------------------
+// One renderer call: per level the stages sampling -> evaluation -> compositing -> exports ("Host stages")
+// ---------------------------------------------------------------------------------------------
+// What the stages of a call share.
+struct CallState {
+    const pr_call_t& c; const pr_object_t* objs; const pr_occupancy_t* occupancy; const RetainCtx* rc;
+    const pr_fine_guide_t* guide; const GuidePlan* gplan; const pr_outputs_t* const* outs; const pr_geometry_t* const* geos;
+    char* ws; const Plan& plan; hipStream_t s;
+    bool geo;             // geometry-only call: density-only MLP launches (none for a skybox model), compositing ends behind the global weights
+    bool naive, gate, defer, save;
+    bool phased;          // training / differentiable call: three MLP phases around the two BatchNorm reductions
+    bool grouped;         // evaluation call with several objects: one launch per stage for all of them
+    bool train_grouped;   // differentiable call with several objects: the same for placement, the phases and the divergence
+    int terms;            // fp16 terms per product of the split-precision tiers
+    template <class T> T* at(size_t offset) const { return reinterpret_cast<T*>(ws + offset); }
+};
 
-    for (int t = 0; t < ntypes; ++t) {
-        const TypePlan& tp = plan.type[t];
-        int32_t* totals = reinterpret_cast<int32_t*>(ws + tp.totals);
-        int32_t* head_counts = reinterpret_cast<int32_t*>(ws + tp.head_counts);
-        // one fill: feature-head / tile counters, and - training / differentiable calls - every object's batch-statistics
-        // accumulators and divergence array
-        PR_TRY(launch_zero_fill(ws + tp.zero_begin, tp.zero_bytes, s));
-        const pr_noise_t& noise = t ? c.noise_fine : c.noise_coarse;
-        int total_positions = 0;
-        sigma_jobs = 0;
-        // what follows phase 1 of an object's phased launches (training / differentiable calls): batch statistics, the two head
-        // phases, the divergence estimate
-        // stage 1: statistics of phase 1 -> phase 2; stage 2: statistics of phase 2 -> phase 3; stage 3: counts, divergence.
-        // `launch`: enqueue the stage's MLP phase here (one object at a time) - false when the caller groups the objects' launches
-        auto finish_object = [&](TrainJob& J, int stage, bool launch) -> int {
-            MlpParams& mp = J.mp; FoldParams& fo = J.fo; const ModelDims& d = J.d; const pr_object_model_t& m = *J.m;
-            const SavedPlan& sv = *J.sv;
-            double* stats = J.stats; int32_t* stat_count = J.stat_count; float* batch = J.batch; float* h1 = J.h1; float* h2 = J.h2;
-            float* rec_pos = J.rec_pos; int32_t* rec_flat = J.rec_flat;
-            const int k = J.k, P = J.P, max_tiles = J.max_tiles;
-            const bool frozen = J.frozen, save = J.save;
-            BnFinalizeParams bf;
-            memset(&bf, 0, sizeof(bf));
-            bf.count = stat_count; bf.momentum = 0.1f;
-            bf.frozen = frozen ? 1 : 0;
-            if (stage == 1) {
-                bf.stats = stats; bf.width = d.W; bf.width_pad = d.Wpad;
-                bf.running_mean = m.bn1_mean; bf.running_var = m.bn1_var; bf.num_batches_tracked = (long long*)m.bn1_batches;
-                bf.batch_mean = batch; bf.batch_var = batch + MAX_WIDTH;
-                PR_TRY(launch_bn_finalize(bf, s));
-                fo.bn1_mean = batch; fo.bn1_var = batch + MAX_WIDTH;
-                PR_TRY(launch_adain_fold(fo, s));          // second layer still folded with placeholders
-                mp.phase = 2; mp.h_in = h1; mp.h_in_width = d.Wpad; mp.h_out = h2; mp.h_out_width = d.W2pad;
-                mp.stats = stats + 2 * MAX_WIDTH;
-                if (launch) PR_TRY(launch_mlp(mp, max_tiles, false, &m, s));
-                return PR_OK;
-            }
-            if (stage == 2) {
-                bf.stats = stats + 2 * MAX_WIDTH; bf.width = d.W2; bf.width_pad = d.W2pad;
-                bf.running_mean = m.bn4_mean; bf.running_var = m.bn4_var; bf.num_batches_tracked = (long long*)m.bn4_batches;
-                bf.batch_mean = batch + 2 * MAX_WIDTH; bf.batch_var = batch + 3 * MAX_WIDTH;
-                PR_TRY(launch_bn_finalize(bf, s));
-                fo.bn4_mean = batch + 2 * MAX_WIDTH; fo.bn4_var = batch + 3 * MAX_WIDTH;
-                PR_TRY(launch_adain_fold(fo, s));
-                mp.phase = 3; mp.h_in = h2; mp.h_in_width = d.W2pad; mp.h_out = nullptr;
-                if (launch) PR_TRY(launch_mlp(mp, max_tiles, false, &m, s));
-                return PR_OK;
-            }
-            if (outs[t] && outs[t]->normalised_samples)
-                PR_CHECK_HIP(hipMemcpyAsync(outs[t]->normalised_samples + k, stat_count, sizeof(int32_t),
-                                            hipMemcpyDeviceToDevice, s));
-            if (save && m.has_bender) {
-                // Hutchinson divergence of the displacement field (train mode with a graph; zeros without a probe)
-                const size_t cap_rows = (size_t)c.frames * c.rays * P;
-                float* div = reinterpret_cast<float*>(ws + sv.div);      // (zeroed by the fill at the top of the type)
-                // probes: explicit, or generated for training calls with a graph (the reference draws them whenever it
-                // trains with a graph, object_composer.py:597)
-                NoiseRef probes = make_noise(noise.divergence[k], c, NOISE_DIVERGENCE, t, k);
-                if (!(c.flags & PR_FLAG_TRAIN_BN)) probes.generate = 0;
-                if (probes.ptr || probes.generate) {
-                    DivergenceParams dp;
-                    memset(&dp, 0, sizeof(dp));
-                    dp.total = totals + k; dp.max_rows = (int)cap_rows;
-                    dp.rec_flat = rec_flat; dp.row_flags = mp.row_flags; dp.rec_pos = rec_pos;
-                    dp.noise = probes; dp.positions = P;
-                    dp.bin = mp.save_bin; dp.bin_pad = d.bin_pad; dp.benc = d.benc; dp.b_octaves = m.bender_octaves;
-                    dp.bacts = mp.save_bact; dp.bact_stride = mp.save_bact_stride; dp.BW = d.BW; dp.BWpad = d.BWpad;
-                    dp.b_count = m.bender_count; dp.b_skip = m.bender_skip; dp.bin_real = d.bin;
-                    dp.layers = m.bender; dp.out_head = m.bender_out; dp.braw = mp.save_braw;
-                    bbox_split(m, dp.lo, dp.hi, nullptr);
-                    dp.canonical = (c.flags & PR_FLAG_CANONICAL_POSE) ? 1 : 0;
-                    dp.t0 = reinterpret_cast<float*>(ws + plan.div_t0);
-                    dp.ta = reinterpret_cast<float*>(ws + plan.div_ta);
-                    dp.tb = reinterpret_cast<float*>(ws + plan.div_tb);
-                    dp.div = div;
-                    PR_TRY(launch_divergence(dp, s));
-                }
-            }
-            return PR_OK;
-        };
-        for (int pass = (place_grouped && t == 0) ? 0 : 1; pass < 2; ++pass) {
-        // pass 0 (grouped coarse placement only): collect the placement / compaction jobs of every object and launch them;
-        // pass 1: everything else per object
-        if (pass == 1 && place_grouped && t == 0) PR_TRY(launch_placement_group(place_jobs, fill_jobs, total_ptrs, K, s));
-        for (int k = 0; k < K; ++k) {
-            const pr_object_model_t& m = t ? objs[k].fine : objs[k].coarse;
-            const float* packed = static_cast<const float*>(t ? objs[k].packed_fine : objs[k].packed_coarse);
-            ModelDims d;
-            PackedLayout l;
-            PR_TRY(compute_dims(m, &d));
-            PR_TRY(compute_layout(m, d, &l));
-            const int P = m.positions;
-            if (pass == 1) total_positions += P;
-            int32_t* block_sums = block_sums_all + (size_t)k * plan.nblocks256;
-            int32_t* block_offsets = block_offsets_all + (size_t)k * plan.nblocks256;
-            const bool placed = place_grouped && t == 0;     // pass 0 has placed and compacted this object
-            const SampleArrays arr = sample_arrays(plan, ws, rc, t, k, m.has_bender != 0);
-            float* t_arr = arr.t;
-            float* sigma = arr.sigma;
-            int32_t* slot = arr.slot;
-            float* dispmag = arr.dispmag;
-            float* feat = arr.feat;
-            // a retained object's jobs return at once when its cached state is reused (NULL: never)
-            const int32_t* skip = (rc && ((rc->mask >> k) & 1u)) ? &rc->hdr->reuse[k] : nullptr;
-            float* adain = reinterpret_cast<float*>(ws + tp.adain[k]);
-            const bool save = (c.flags & PR_FLAG_SAVE_FOR_BACKWARD) != 0;
-            const SavedPlan& sv = tp.saved[k];
-            // empty-space skipping: the grid of this object and model type (bits == NULL without one) - the same grid at the
-            // count and the fill site of the type
-            // fine guide: this object's keep bits at the fine level (NULL: not guided) - written by the resampler, read by the fill
-            uint32_t* keep = (guide && t == 1 && gplan->at[k] != (size_t)-1)
-                                 ? reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(guide->scratch) + gplan->at[k]) : nullptr;
-            OccGrid occ;
-            PR_TRY(make_occ_grid(occupancy ? (t ? &occupancy->fine[k] : &occupancy->coarse[k]) : nullptr, m, k, t ? "fine" : "coarse", &occ));
-            if (save) {
-                rec_pos = reinterpret_cast<float*>(ws + sv.rec_pos);
-                rec_flat = reinterpret_cast<int32_t*>(ws + sv.rec_flat);
-            } else if (grouped) {
-                rec_pos = reinterpret_cast<float*>(ws + plan.rec_pos_k[k]);
-                rec_flat = reinterpret_cast<int32_t*>(ws + plan.rec_flat_k[k]);
-            }
+// Object k at level t: everything the stages read of it, resolved once.
+struct ObjectLevel {
+    int k, P;
+    size_t cap;                       // frames * rays * P: the rows of every per-sample array, the row bound of every launch
+    const pr_object_model_t* m; const float* packed; ModelDims d; PackedLayout l;
+    SampleArrays arr, coarse;         // (coarse: the arrays of the object's coarse level - fine level only)
+    const int32_t* skip;              // retained object: its jobs return at once when the cached state is reused (NULL: never)
+    uint32_t* keep; int keep_words;   // fine level of a guided object: the keep bits the resampler writes and the fill reads (NULL: not guided)
+    OccGrid occ;                      // empty-space skipping: the same grid at the count and the fill site (bits == NULL without one)
+    float* adain; const SavedPlan* sv;
+    float* rec_pos; int32_t* rec_flat;                               // compact sample records
+    int32_t* block_sums; int32_t* block_offsets; int32_t* total;
+};
 
-            // ---- sample placement --------------------------------------------------------------
-            if (t == 0) {
-                PlaceParams pp;
-                memset(&pp, 0, sizeof(pp));
-                pp.frames = c.frames; pp.rays = c.rays; pp.positions = P; pp.objects = K; pp.object_index = k;
-                pp.ray_origins = c.ray_origins; pp.ray_directions = c.ray_directions; pp.w2o = c.w2o;
-                pp.in_scene = c.object_in_scene;
-                bbox_split(m, pp.lo, pp.hi, nullptr);
-                pp.z_near_min = m.z_near_min; pp.z_far_max = m.z_far_max; pp.empty_alpha = m.empty_space_alpha;
-                pp.linspace = c.linspace_coarse[k];
-                pp.jitter = perturb_noise(c.noise_coarse.jitter[k], c, NOISE_JITTER, 0, k);
-                pp.t = t_arr; pp.sigma = sigma; pp.dispmag = dispmag; pp.block_sums = block_sums;
-                pp.occ = occ;
-                pp.skip = skip;
-                if (pass == 0) place_jobs[k] = pp;
-                else if (!placed) PR_TRY(launch_place_coarse(pp, s));
-            } else {
-                ResampleParams rp;
-                memset(&rp, 0, sizeof(rp));
-                rp.frames = c.frames; rp.rays = c.rays; rp.objects = K; rp.object_index = k;
-                rp.pc = objs[k].coarse.positions; rp.pf = c.positions_fine[k];
-                rp.ray_origins = c.ray_origins; rp.ray_directions = c.ray_directions; rp.w2o = c.w2o;
-                rp.in_scene = c.object_in_scene;
-                bbox_split(m, rp.lo, rp.hi, nullptr);
-                rp.empty_alpha = m.empty_space_alpha;
-                const SampleArrays coarse_arr = sample_arrays(plan, ws, rc, 0, k, objs[k].coarse.has_bender != 0);
-                rp.t_coarse = coarse_arr.t;
-                rp.sigma_coarse = coarse_arr.sigma;
-                rp.alpha_noise = perturb_noise(c.noise_coarse.alpha[k], c, NOISE_ALPHA, 0, k);
-                rp.u_fixed = c.linspace_fine[k];
-                rp.u_random = perturb_noise(c.noise_coarse.pdf[k], c, NOISE_PDF, 0, k);
-                rp.t_fine = t_arr; rp.sigma_fine = sigma; rp.dispmag_fine = dispmag; rp.block_sums = block_sums;
-                rp.occ = occ;
-                rp.skip = skip;
-                if (keep) {
-                    rp.keep = keep; rp.keep_words = gplan->words[k]; rp.guard = guide->guard; rp.threshold = guide->threshold;
-                }
-                PR_TRY(launch_resample(rp, s));
-            }
-            if (pass == 1 && !placed) PR_TRY(launch_scan(block_sums, block_offsets, totals + k, plan.nblocks256, s));
+static int make_object_level(const CallState& cs, int t, int k, ObjectLevel* o) {
+    const pr_object_t& obj = cs.objs[k];
+    const TypePlan& tp = cs.plan.type[t];
+    o->k = k;
+    o->m = t ? &obj.fine : &obj.coarse;
+    o->packed = static_cast<const float*>(t ? obj.packed_fine : obj.packed_coarse);
+    PR_TRY(compute_dims(*o->m, &o->d));
+    PR_TRY(compute_layout(*o->m, o->d, &o->l));
+    o->P = o->m->positions; o->cap = (size_t)cs.c.frames * cs.c.rays * o->P;
+    o->arr = sample_arrays(cs.plan, cs.ws, cs.rc, t, k, o->m->has_bender != 0);
+    if (t) o->coarse = sample_arrays(cs.plan, cs.ws, cs.rc, 0, k, obj.coarse.has_bender != 0);
+    o->skip = (cs.rc && ((cs.rc->mask >> k) & 1u)) ? &cs.rc->hdr->reuse[k] : nullptr;
+    const bool guided = cs.guide && t == 1 && cs.gplan->at[k] != (size_t)-1;
+    o->keep = guided ? reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(cs.guide->scratch) + cs.gplan->at[k]) : nullptr;
+    o->keep_words = guided ? cs.gplan->words[k] : 0;
+    PR_TRY(make_occ_grid(cs.occupancy ? (t ? &cs.occupancy->fine[k] : &cs.occupancy->coarse[k]) : nullptr, *o->m, k, t ? "fine" : "coarse", &o->occ));
+    o->adain = cs.at<float>(tp.adain[k]);
+    o->sv = &tp.saved[k];
+    // a differentiable call keeps every object's records, grouped evaluation launches read them side by side; every other call
+    // evaluates one object after the other on the shared pair
+    o->rec_pos = cs.at<float>(cs.save ? o->sv->rec_pos : cs.grouped ? cs.plan.rec_pos_k[k] : cs.plan.rec_pos);
+    o->rec_flat = cs.at<int32_t>(cs.save ? o->sv->rec_flat : cs.grouped ? cs.plan.rec_flat_k[k] : cs.plan.rec_flat);
+    o->block_sums = cs.at<int32_t>(cs.plan.block_sums) + (size_t)k * cs.plan.nblocks256;
+    o->block_offsets = cs.at<int32_t>(cs.plan.block_offsets) + (size_t)k * cs.plan.nblocks256;
+    o->total = cs.at<int32_t>(tp.totals) + k;
+    return PR_OK;
+}
 
-            // ---- compaction --------------------------------------------------------------------
-            FillParams fp;
-            memset(&fp, 0, sizeof(fp));
-            fp.frames = c.frames; fp.rays = c.rays; fp.positions = P; fp.objects = K; fp.object_index = k;
-            fp.ray_origins = c.ray_origins; fp.ray_directions = c.ray_directions; fp.w2o = c.w2o;
-            fp.in_scene = c.object_in_scene;
-            bbox_split(m, fp.lo, fp.hi, nullptr);
-            fp.t = t_arr; fp.block_offsets = block_offsets; fp.rec_pos = rec_pos; fp.rec_flat = rec_flat; fp.slot = slot;
-            fp.occ = occ;
-            fp.skip = skip;
-            if (keep) {
-                fp.keep = keep; fp.keep_words = gplan->words[k];
-            }
-            if (pass == 0) {
-                fill_jobs[k] = fp;
-                total_ptrs[k] = totals + k;
-                continue;
-            }
-            if (!placed) PR_TRY(launch_fill(fp, s));
+// A phased object (training / differentiable calls): its launch parameters, advanced from phase to phase, and where its BatchNorm state is.
+struct TrainJob {
+    MlpParams mp; FoldParams fo; const ObjectLevel* o;
+    double* stats; int32_t* stat_count; float* batch; float* h1; float* h2;
+};
 
-            // ---- style affine + BatchNorm fold; fused MLP ---------------------------------------
-            FoldParams fo;
-            memset(&fo, 0, sizeof(fo));
-            fo.frames = c.frames; fo.objects = K; fo.object_index = k;
-            fo.style = c.style; fo.S = m.style_features;
-            fo.affine1 = m.affine1; fo.bn1_mean = m.bn1_mean; fo.bn1_var = m.bn1_var;
-            fo.affine4 = m.affine4; fo.bn4_mean = m.bn4_mean; fo.bn4_var = m.bn4_var;
-            fo.eps = m.bn_eps;
-            fo.W = d.W; fo.Wpad = d.Wpad; fo.W2 = d.W2; fo.W2pad = d.W2pad;
-            fo.table = adain; fo.row_floats = adain_row_floats(d);
+// A level of the call: its objects and the host copies of what its grouped launches take.
+struct Level {
+    int t; const TypePlan* tp; const pr_noise_t* noise; const pr_outputs_t* out;
+    int32_t* totals; int32_t* head_counts;
+    ObjectLevel obj[PR_MAX_OBJECTS];
+    PlaceParams place[PR_MAX_OBJECTS]; FillParams fill[PR_MAX_OBJECTS]; int32_t* total_ptrs[PR_MAX_OBJECTS];
+    MlpParams jobs[PR_MAX_OBJECTS]; int job_rows[PR_MAX_OBJECTS]; FoldParams folds[PR_MAX_OBJECTS];
+    int njobs;            // jobs of the level's grouped MLP launch, packed in object order (a geometry-only call leaves skybox models out)
+    TrainJob train[PR_MAX_OBJECTS]; BnFoldJobs bn; DivChainJob div[PR_MAX_OBJECTS];
+};
+static thread_local Level g_level;
 
-            MlpParams mp;
-            memset(&mp, 0, sizeof(mp));
-            // training calls with PR_FLAG_SPLIT_BACKWARD: phase 1 of the grouped launches reads the fp16-pair packings
-            const bool split3 = train_grouped && (c.flags & PR_FLAG_SPLIT_BACKWARD) && (c.flags & PR_FLAG_SAVE_FOR_BACKWARD);
-            PR_TRY(build_mlp_layers(m, d, l, packed, &mp, split3));
-            mp.rec_pos = rec_pos; mp.rec_flat = rec_flat; mp.total = totals + k;
-            mp.samples_per_frame = c.rays * P; mp.positions = P; mp.rays = c.rays;
-            mp.canonical = (c.flags & PR_FLAG_CANONICAL_POSE) ? 1 : 0;
-            bbox_split(m, mp.lo, mp.hi, mp.size);
-            mp.empty_alpha = m.empty_space_alpha;
-            mp.in_scene = c.object_in_scene + k; mp.in_scene_stride = K;
-            mp.ray_directions = c.ray_directions; mp.ray_origins = c.ray_origins;
-            mp.w2o = c.w2o + (size_t)k * 12; mp.w2o_stride = K * 12;
-            mp.deformation = c.deformation + (size_t)k * m.deformation_features;
-            mp.deformation_stride = K * m.deformation_features;
-            mp.adain = adain; mp.adain_stride = fo.row_floats;
-            mp.sigma = sigma; mp.dispmag = dispmag; mp.feat = geo ? nullptr : feat;
-            if (defer) {     // the kernels stop behind features_head.4 and write [h | 1] rows
-                mp.n_layers = mp.n_backbone + 2;
-                mp.F = hidden_row_floats(d.W2);
-                mp.ones_col = d.W2;
-            }
-            if (gate) {
-                mp.gate = 1;
-                mp.pend_act = reinterpret_cast<float*>(ws + plan.pend_act);
-                mp.pend_meta = reinterpret_cast<int32_t*>(ws + plan.pend_meta);
-                mp.head_count = head_counts + k;
-            }
-            mp.tile_counter = head_counts + PR_MAX_OBJECTS + k;
-            if (outs[t] && outs[t]->sample_delta[k]) {
-                PR_TRY(launch_zero_fill(outs[t]->sample_delta[k], sizeof(float) * 3 * (size_t)c.frames * c.rays * P, s));
-                if (m.has_bender) mp.delta_dense = outs[t]->sample_delta[k];
-            }
-            const size_t cap = (size_t)c.frames * c.rays * P;
-            const int max_tiles = (int)cap;   // rows: every launcher derives its own tile count
-            if (geo) {
-                // no AdaIN fold (the table feeds the feature head only); a skybox model's constant density needs no MLP launch
-                const int terms = c.precision == PR_PRECISION_F16 ? 1 : 3;
-                mp.adain = nullptr;
-                if (m.kind == 1) {
-                    SkyboxSigmaParams sp;
-                    memset(&sp, 0, sizeof(sp));
-                    sp.samples = (long)cap; sp.samples_per_frame = c.rays * P;
-                    sp.slot = slot; sp.in_scene = c.object_in_scene + k; sp.in_scene_stride = K;
-                    sp.empty_alpha = m.empty_space_alpha; sp.sigma = sigma;
-                    PR_TRY(launch_skybox_sigma(sp, s));
-                } else if (grouped) {
-                    jobs[sigma_jobs] = mp;
-                    job_rows[sigma_jobs] = max_tiles;
-                    ++sigma_jobs;
-                } else if (c.precision != PR_PRECISION_FP32) {
-                    PR_TRY(launch_mlp_split_sigma(mp, max_tiles, terms, s));
-                } else {
-                    PR_TRY(launch_mlp_sigma(mp, max_tiles, s));
-                }
-                continue;
-            }
-            if (!(c.flags & (PR_FLAG_TRAIN_BN | PR_FLAG_SAVE_FOR_BACKWARD))) {
-                if (grouped) {
-                    fold_jobs[k] = fo;       // folded and evaluated together once every object of the type is prepared
-                    jobs[k] = mp;
-                    job_rows[k] = max_tiles;
-                    continue;
-                }
-                if (rc) PR_TRY(launch_retain_gate(*rc, totals, k, 1, s));
-                PR_TRY(launch_adain_fold(fo, s));
-                if (c.precision != PR_PRECISION_FP32 && !naive)
-                    PR_TRY(launch_mlp_split(mp, max_tiles, c.precision == PR_PRECISION_F16 ? 1 : 3, s));
-                else
-                    PR_TRY(launch_mlp(mp, max_tiles, naive, &m, s));
-            } else {
-                // BatchNorm in training mode: the batch statistics of the first (second) AdaIN layer are
-                // a reduction over every evaluated sample of this object call, between two matmuls.
-                // Differentiable eval-mode calls (SAVE without TRAIN_BN) use the same phases - they leave the pre-BatchNorm
-                // activations h1 / h2 behind for the backward pass - with the running statistics frozen.
-                const bool frozen = !(c.flags & PR_FLAG_TRAIN_BN);
-                PR_REQUIRE(!naive, "the scalar debugging kernel has no train-mode BatchNorm");
-                double* stats = reinterpret_cast<double*>(ws + sv.stats);               // (zeroed by the fill above)
-                int32_t* stat_count = reinterpret_cast<int32_t*>(ws + sv.stat_count);
-                float* batch = reinterpret_cast<float*>(ws + (save ? sv.batch : plan.batch_stats));
-                float* h1 = reinterpret_cast<float*>(ws + (save ? sv.h1 : plan.h1));
-                float* h2 = reinterpret_cast<float*>(ws + (save ? sv.h2 : plan.h2));
-                mp.row_flags = reinterpret_cast<int32_t*>(ws + (save ? sv.row_flags : plan.row_flags));
-                mp.stat_count = stat_count;
-                if (save) {
-                    const size_t cap_rows = (size_t)c.frames * c.rays * P;
-                    mp.save_enc = reinterpret_cast<float*>(ws + sv.enc);
-                    mp.save_act = reinterpret_cast<float*>(ws + sv.act);
-                    mp.save_act_stride = cap_rows * d.Wpad;
-                    mp.save_bits = reinterpret_cast<unsigned char*>(ws + sv.bits);
-                    mp.save_bits_stride = relu_bits_bytes(cap_rows, d.Wpad);
-                    if (m.has_bender) {
-                        mp.save_bin = reinterpret_cast<float*>(ws + sv.bin);
-                        mp.save_bact = reinterpret_cast<float*>(ws + sv.bact);
-                        mp.save_bact_stride = cap_rows * d.BWpad;
-                        mp.save_bbits = reinterpret_cast<unsigned char*>(ws + sv.bbits);
-                        mp.save_bbits_stride = relu_bits_bytes(cap_rows, d.BWpad);
-                        mp.save_braw = reinterpret_cast<float*>(ws + sv.braw);
-                        mp.save_delta = reinterpret_cast<float*>(ws + sv.delta);
-                    }
-                }
-                mp.phase = 1; mp.h_out = h1; mp.h_out_width = d.Wpad; mp.stats = stats;
-                TrainJob& J = train_jobs[k];
-                J.mp = mp; J.fo = fo; J.d = d; J.m = &m; J.sv = &sv;
-                J.stats = stats; J.stat_count = stat_count; J.batch = batch; J.h1 = h1; J.h2 = h2; J.rec_pos = rec_pos; J.rec_flat = rec_flat;
-                J.k = k; J.P = P; J.max_tiles = max_tiles; J.frozen = frozen; J.save = save;
-                if (train_grouped) {
-                    jobs[k] = mp;
-                    job_rows[k] = max_tiles;
-                } else {
-                    PR_TRY(launch_mlp(mp, max_tiles, false, &m, s));
-                    for (int stage = 1; stage <= 3; ++stage) PR_TRY(finish_object(J, stage, true));
-                }
-            }
-        }
-        }   // pass
-        if (train_grouped) {
-            PR_TRY(launch_mlp_group(jobs, job_rows, K, s));                  // phase 1 of every object
-            static thread_local BnFoldJobs bj;
-            for (int stage = 1; stage <= 2; ++stage) {                       // statistics + fold of all objects, then their next phase
-                for (int k = 0; k < K; ++k) {
-                    TrainJob& J = train_jobs[k];
-                    const pr_object_model_t& m = *J.m;
-                    BnFoldJob& b = bj.job[k];
-                    memset(&b, 0, sizeof(b));
-                    b.count = J.stat_count; b.momentum = 0.1f; b.frozen = J.frozen ? 1 : 0;
-                    b.style = c.style + (size_t)k * m.style_features; b.style_stride = K * m.style_features; b.S = m.style_features;
-                    b.frames = c.frames; b.eps = m.bn_eps;
-                    b.table = const_cast<float*>(J.mp.adain); b.row_floats = J.mp.adain_stride;
-                    if (stage == 1) {
-                        b.stats = J.stats; b.width = J.d.W; b.width_pad = J.d.Wpad;
-                        b.running_mean = m.bn1_mean; b.running_var = m.bn1_var; b.num_batches_tracked = (long long*)m.bn1_batches;
-                        b.batch_mean = J.batch; b.batch_var = J.batch + MAX_WIDTH;
-                        b.affine = m.affine1; b.g_off = 0; b.b_off = J.d.Wpad;
-                        J.mp.split3 = 0;     // (the head phases read fp32 fragments)
-                        J.mp.phase = 2; J.mp.h_in = J.h1; J.mp.h_in_width = J.d.Wpad; J.mp.h_out = J.h2; J.mp.h_out_width = J.d.W2pad;
-                        J.mp.stats = J.stats + 2 * MAX_WIDTH;
-                    } else {
-                        b.stats = J.stats + 2 * MAX_WIDTH; b.width = J.d.W2; b.width_pad = J.d.W2pad;
-                        b.running_mean = m.bn4_mean; b.running_var = m.bn4_var; b.num_batches_tracked = (long long*)m.bn4_batches;
-                        b.batch_mean = J.batch + 2 * MAX_WIDTH; b.batch_var = J.batch + 3 * MAX_WIDTH;
-                        b.affine = m.affine4; b.g_off = 2 * J.d.Wpad; b.b_off = 2 * J.d.Wpad + J.d.W2pad;
-                        b.normalised_out = (outs[t] && outs[t]->normalised_samples) ? outs[t]->normalised_samples + k : nullptr;
-                        J.mp.phase = 3; J.mp.h_in = J.h2; J.mp.h_in_width = J.d.W2pad; J.mp.h_out = nullptr;
-                    }
-                    PR_REQUIRE(b.affine.weight && b.affine.bias && b.running_mean && b.running_var, "AdaIN parameters missing");
-                    jobs[k] = J.mp;
-                }
-                PR_TRY(launch_bn_fold_group(bj, K, s));
-                PR_TRY(launch_mlp_group(jobs, job_rows, K, s));
-            }
-            // Hutchinson divergence of the displacement fields (train mode with a graph): the ray benders of the call as one launch
-            static thread_local DivChainJob dj[PR_MAX_OBJECTS];
-            long div_rows[PR_MAX_OBJECTS];
-            int div_jobs = 0;
-            for (int k = 0; k < K; ++k) {
-                TrainJob& J = train_jobs[k];
-                const pr_object_model_t& m = *J.m;
-                if (!(J.save && m.has_bender)) continue;
-                NoiseRef probes = make_noise(noise.divergence[k], c, NOISE_DIVERGENCE, t, k);
-                if (!(c.flags & PR_FLAG_TRAIN_BN)) probes.generate = 0;
-                if (!(probes.ptr || probes.generate)) continue;
-                if (!div_chain_supported(J.d.BWpad, J.d.bin_pad)) {
-                    PR_TRY(finish_object(J, 3, false));          // (unusually wide bender: one product per layer)
-                    continue;
-                }
-                PackedLayout l;
-                PR_TRY(compute_layout(m, J.d, &l));
-                const float* packed = static_cast<const float*>(t ? objs[k].packed_fine : objs[k].packed_coarse);
-                const size_t cap_rows = (size_t)c.frames * c.rays * J.P;
-                DivChainJob& q = dj[div_jobs];
-                memset(&q, 0, sizeof(q));
-                q.total = totals + k; q.rec_flat = J.rec_flat; q.row_flags = J.mp.row_flags; q.rec_pos = J.rec_pos;
-                q.noise = probes; q.positions = J.P;
-                q.bin = J.mp.save_bin; q.bin_pad = J.d.bin_pad; q.benc = J.d.benc; q.b_octaves = m.bender_octaves;
-                q.bbits = J.mp.save_bbits; q.bbits_stride = J.mp.save_bbits_stride;
-                q.BW = J.d.BW; q.BWpad = J.d.BWpad; q.b_count = m.bender_count; q.b_skip = m.bender_skip;
-                for (int j = 0; j < m.bender_count; ++j) q.seg0[j] = Seg{packed + l.b_seg_off[j][0], (j == 0 ? J.d.bin_pad : J.d.BWpad) / 8, 0};
-                q.seg1 = Seg{packed + l.b_seg_off[m.bender_skip][1], J.d.bin_pad / 8, 0};
-                q.w_out = packed + l.b_out_off;
-                q.braw = J.mp.save_braw;
-                bbox_split(m, q.lo, q.hi, nullptr);
-                q.canonical = (c.flags & PR_FLAG_CANONICAL_POSE) ? 1 : 0;
-                q.div = reinterpret_cast<float*>(ws + J.sv->div);
-                q.tile_counter = head_counts + 2 * PR_MAX_OBJECTS + k;
-                div_rows[div_jobs] = (long)cap_rows;
-                ++div_jobs;
-            }
-            if (div_jobs) PR_TRY(launch_div_chain_group(dj, div_rows, div_jobs, s));
-        }
+// ---- sampling: coarse placement or resampling, block scan, compaction ------------------------------------------------------
+// The part PlaceParams, ResampleParams and FillParams share: rays, pose, box, occupancy grid, retention flag.
+template <class Params> static Params sampling_params(const CallState& cs, const ObjectLevel& o) {
+    Params p;
+    memset(&p, 0, sizeof(p));
+    p.frames = cs.c.frames; p.rays = cs.c.rays; p.objects = cs.c.objects; p.object_index = o.k;
+    p.ray_origins = cs.c.ray_origins; p.ray_directions = cs.c.ray_directions; p.w2o = cs.c.w2o; p.in_scene = cs.c.object_in_scene;
+    bbox_split(*o.m, p.lo, p.hi, nullptr);
+    p.occ = o.occ; p.skip = o.skip;
+    return p;
+}
 
-        if (geo) {
-            if (grouped && sigma_jobs > 0) {
-                if (c.precision != PR_PRECISION_FP32)
-                    PR_TRY(launch_mlp_split_sigma_group(jobs, job_rows, sigma_jobs, c.precision == PR_PRECISION_F16 ? 1 : 3, s));
-                else
-                    PR_TRY(launch_mlp_sigma_group(jobs, job_rows, sigma_jobs, s));
-            }
-        } else if (grouped) {
-            if (rc) PR_TRY(launch_retain_gate(*rc, totals, 0, K, s));      // (behind the block scans of the level)
-            PR_TRY(launch_adain_fold_group(fold_jobs, K, s));
-            if (c.precision != PR_PRECISION_FP32)
-                PR_TRY(launch_mlp_split_group(jobs, job_rows, K, c.precision == PR_PRECISION_F16 ? 1 : 3, s));
-            else
-                PR_TRY(launch_mlp_group(jobs, job_rows, K, s));
-        }
+static PlaceParams place_params(const CallState& cs, const ObjectLevel& o) {
+    PlaceParams pp = sampling_params<PlaceParams>(cs, o);
+    pp.positions = o.P;
+    pp.z_near_min = o.m->z_near_min; pp.z_far_max = o.m->z_far_max; pp.empty_alpha = o.m->empty_space_alpha;
+    pp.linspace = cs.c.linspace_coarse[o.k];
+    pp.jitter = perturb_noise(cs.c.noise_coarse.jitter[o.k], cs.c, NOISE_JITTER, 0, o.k);
+    pp.t = o.arr.t; pp.sigma = o.arr.sigma; pp.dispmag = o.arr.dispmag; pp.block_sums = o.block_sums;
+    return pp;
+}
 
-        // ---- compositing ------------------------------------------------------------------------
-        const pr_outputs_t* out = outs[t];
-        CompositeParams cp;
-        memset(&cp, 0, sizeof(cp));
-        cp.frames = c.frames; cp.rays = c.rays; cp.objects = K; cp.static_objects = c.static_objects;
-        cp.F = objs[0].coarse.output_features;
-        cp.fix_overlaps = (c.flags & PR_FLAG_FIX_OVERLAPS) ? 1 : 0;
-        cp.sigmoid = (c.flags & PR_FLAG_SIGMOID_FEATURES) ? 1 : 0;
-        cp.total_positions = total_positions;
-        int ss = 64;
-        while (ss < total_positions) ss <<= 1;
-        cp.sort_size = ss;
-        cp.ray_directions = c.ray_directions;
-        cp.noise_global = perturb_noise(noise.integrate_global, c, NOISE_INTEGRATE_GLOBAL, t, 0);
-        for (int k = 0; k < K; ++k) {
-            const pr_object_model_t& m = t ? objs[k].fine : objs[k].coarse;
-            PR_REQUIRE(m.output_features == cp.F, "all objects must share output_features");
-            if (defer) {
-                ModelDims d;
-                PackedLayout l;
-                PR_TRY(compute_dims(m, &d));
-                PR_TRY(compute_layout(m, d, &l));
-                cp.proj_w[k] = static_cast<const float*>(t ? objs[k].packed_fine : objs[k].packed_coarse) + l.h6p_off;
-                cp.proj_k = projection_k(d.W2);
-            }
-            CompositeObject& o = cp.obj[k];
-            const SampleArrays arr = sample_arrays(plan, ws, rc, t, k, m.has_bender != 0);
-            o.t = arr.t;
-            o.sigma = arr.sigma;
-            o.slot = arr.slot;
-            o.dispmag = arr.dispmag;
-            o.divergence = ((c.flags & PR_FLAG_SAVE_FOR_BACKWARD) && m.has_bender)
-                               ? reinterpret_cast<const float*>(ws + tp.saved[k].div) : nullptr;
-            if (o.divergence) cp.any_divergence = 1;
-            o.feat = geo ? nullptr : arr.feat;
-            o.noise = perturb_noise(noise.integrate[k], c, NOISE_INTEGRATE, t, k);
-            o.positions = m.positions;
-            if (out) o.out = out->object[k];
-        }
-        if (out) {
-            cp.global = out->global;
-            cp.decoder = out->decoder;
-        }
-        if (defer) {
-            cp.out_features = cp.F;
-            cp.F = hidden_row_floats(objs[0].coarse.layers_width / 2);
-            cp.pooled = reinterpret_cast<float*>(ws + plan.pooled);
-        }
-        if (geo) {
-            cp.geometry = 1;
-            cp.sigmoid = 0;
-            if (geos[t]) {
-                cp.visibility = geos[t]->visibility;
-                cp.front_object = geos[t]->front_object;
-            }
-        }
-        PR_TRY(launch_composite(cp, s));
-        if (defer) PR_TRY(launch_projection(cp, s));
+static ResampleParams resample_params(const CallState& cs, const ObjectLevel& o) {
+    const pr_call_t& c = cs.c;
+    ResampleParams rp = sampling_params<ResampleParams>(cs, o);
+    rp.pc = cs.objs[o.k].coarse.positions; rp.pf = c.positions_fine[o.k];
+    rp.empty_alpha = o.m->empty_space_alpha;
+    rp.t_coarse = o.coarse.t; rp.sigma_coarse = o.coarse.sigma;
+    rp.alpha_noise = perturb_noise(c.noise_coarse.alpha[o.k], c, NOISE_ALPHA, 0, o.k);
+    rp.u_fixed = c.linspace_fine[o.k];
+    rp.u_random = perturb_noise(c.noise_coarse.pdf[o.k], c, NOISE_PDF, 0, o.k);
+    rp.t_fine = o.arr.t; rp.sigma_fine = o.arr.sigma; rp.dispmag_fine = o.arr.dispmag; rp.block_sums = o.block_sums;
+    if (o.keep) {
+        rp.keep = o.keep; rp.keep_words = o.keep_words; rp.guard = cs.guide->guard; rp.threshold = cs.guide->threshold;
+    }
+    return rp;
+}
 
-        // ---- optional exports -------------------------------------------------------------------
-        if (out) {
-            for (int k = 0; k < K; ++k) {
-                const size_t cap = (size_t)c.frames * c.rays * tp.positions[k];
-                const SampleArrays arr = sample_arrays(plan, ws, rc, t, k, false);      // (wherever the arrays live)
-                if (out->sample_t[k])
-                    PR_CHECK_HIP(hipMemcpyAsync(out->sample_t[k], arr.t, sizeof(float) * cap, hipMemcpyDeviceToDevice, s));
-                if (out->sample_sigma[k])
-                    PR_CHECK_HIP(hipMemcpyAsync(out->sample_sigma[k], arr.sigma, sizeof(float) * cap, hipMemcpyDeviceToDevice, s));
-                if (out->sample_slot[k])
-                    PR_CHECK_HIP(hipMemcpyAsync(out->sample_slot[k], arr.slot, sizeof(int32_t) * cap, hipMemcpyDeviceToDevice, s));
-            }
-            if (out->evaluated_samples)
-                PR_CHECK_HIP(hipMemcpyAsync(out->evaluated_samples, totals, sizeof(int32_t) * K, hipMemcpyDeviceToDevice, s));
-            if (out->head_samples && geo)     // no sample goes through the feature head (a kernel fill: no memset node)
-                PR_TRY(launch_zero_fill(out->head_samples, sizeof(int32_t) * K, s));
-            else if (out->head_samples)   // without the gate every evaluated sample goes through the feature head
-                PR_CHECK_HIP(hipMemcpyAsync(out->head_samples, gate ? head_counts : totals, sizeof(int32_t) * K,
-                                            hipMemcpyDeviceToDevice, s));
+static FillParams fill_params(const CallState& cs, const ObjectLevel& o) {
+    FillParams fp = sampling_params<FillParams>(cs, o);
+    fp.positions = o.P;
+    fp.t = o.arr.t; fp.block_offsets = o.block_offsets; fp.rec_pos = o.rec_pos; fp.rec_flat = o.rec_flat; fp.slot = o.arr.slot;
+    fp.keep = o.keep; fp.keep_words = o.keep_words;
+    return fp;
+}
+
+// One object: its three launches.
+static int sample_object(const CallState& cs, const Level& L, const ObjectLevel& o) {
+    if (L.t == 0) PR_TRY(launch_place_coarse(place_params(cs, o), cs.s));
+    else PR_TRY(launch_resample(resample_params(cs, o), cs.s));
+    PR_TRY(launch_scan(o.block_sums, o.block_offsets, o.total, cs.plan.nblocks256, cs.s));
+    return launch_fill(fill_params(cs, o), cs.s);
+}
+
+// Coarse placement, block scan and compaction of every object of the call: three launches for all of them.
+static int sample_level_grouped(const CallState& cs, Level& L) {
+    for (int k = 0; k < cs.c.objects; ++k) {
+        L.place[k] = place_params(cs, L.obj[k]);
+        L.fill[k] = fill_params(cs, L.obj[k]);
+        L.total_ptrs[k] = L.obj[k].total;
+    }
+    return launch_placement_group(L.place, L.fill, L.total_ptrs, cs.c.objects, cs.s);
+}
+
+// ---- evaluation: style affine + BatchNorm fold, the MLP --------------------------------------------------------------------
+// The fused (phase 0) launch parameters of an object and the fold of its AdaIN table.
+static int mlp_params(const CallState& cs, const Level& L, const ObjectLevel& o, MlpParams* mp_out, FoldParams* fo_out) {
+    const pr_call_t& c = cs.c;
+    const pr_object_model_t& m = *o.m;
+    const ModelDims& d = o.d;
+    const int K = c.objects, k = o.k;
+    FoldParams& fo = *fo_out;
+    memset(&fo, 0, sizeof(fo));
+    fo.frames = c.frames; fo.objects = K; fo.object_index = k;
+    fo.style = c.style; fo.S = m.style_features;
+    fo.affine1 = m.affine1; fo.bn1_mean = m.bn1_mean; fo.bn1_var = m.bn1_var;
+    fo.affine4 = m.affine4; fo.bn4_mean = m.bn4_mean; fo.bn4_var = m.bn4_var;
+    fo.eps = m.bn_eps;
+    fo.W = d.W; fo.Wpad = d.Wpad; fo.W2 = d.W2; fo.W2pad = d.W2pad;
+    fo.table = o.adain; fo.row_floats = adain_row_floats(d);
+    MlpParams& mp = *mp_out;
+    memset(&mp, 0, sizeof(mp));
+    // training calls with PR_FLAG_SPLIT_BACKWARD: phase 1 of the grouped launches reads the fp16-pair packings
+    const bool split3 = cs.train_grouped && (c.flags & PR_FLAG_SPLIT_BACKWARD) && cs.save;
+    PR_TRY(build_mlp_layers(m, d, o.l, o.packed, &mp, split3));
+    mp.rec_pos = o.rec_pos; mp.rec_flat = o.rec_flat; mp.total = o.total;
+    mp.samples_per_frame = c.rays * o.P; mp.positions = o.P; mp.rays = c.rays;
+    mp.canonical = (c.flags & PR_FLAG_CANONICAL_POSE) ? 1 : 0;
+    bbox_split(m, mp.lo, mp.hi, mp.size);
+    mp.empty_alpha = m.empty_space_alpha;
+    mp.in_scene = c.object_in_scene + k; mp.in_scene_stride = K;
+    mp.ray_directions = c.ray_directions; mp.ray_origins = c.ray_origins;
+    mp.w2o = c.w2o + (size_t)k * 12; mp.w2o_stride = K * 12;
+    mp.deformation = c.deformation + (size_t)k * m.deformation_features; mp.deformation_stride = K * m.deformation_features;
+    // (a geometry-only call folds no AdaIN table: it feeds the feature head only)
+    mp.adain = cs.geo ? nullptr : o.adain; mp.adain_stride = fo.row_floats;
+    mp.sigma = o.arr.sigma; mp.dispmag = o.arr.dispmag; mp.feat = cs.geo ? nullptr : o.arr.feat;
+    if (cs.defer) {     // the kernels stop behind features_head.4 and write [h | 1] rows
+        mp.n_layers = mp.n_backbone + 2;
+        mp.F = hidden_row_floats(d.W2);
+        mp.ones_col = d.W2;
+    }
+    if (cs.gate) {
+        mp.gate = 1; mp.head_count = L.head_counts + k;
+        mp.pend_act = cs.at<float>(cs.plan.pend_act);
+        mp.pend_meta = cs.at<int32_t>(cs.plan.pend_meta);
+    }
+    mp.tile_counter = L.head_counts + PR_MAX_OBJECTS + k;
+    if (L.out && L.out->sample_delta[k] && m.has_bender) mp.delta_dense = L.out->sample_delta[k];
+    return PR_OK;
+}
+
+// The job of the level's grouped launch (rows: every launcher derives its own tile count).
+static int add_job(Level& L, const ObjectLevel& o, const MlpParams& mp) {
+    L.jobs[L.njobs] = mp;
+    L.job_rows[L.njobs++] = (int)o.cap;
+    return PR_OK;
+}
+
+// Geometry-only: a skybox model's constant density needs no MLP launch, the others run the density-only kernels.
+static int evaluate_geometry_object(const CallState& cs, Level& L, const ObjectLevel& o, const MlpParams& mp) {
+    if (o.m->kind == 1) {
+        SkyboxSigmaParams sp;
+        memset(&sp, 0, sizeof(sp));
+        sp.samples = (long)o.cap; sp.samples_per_frame = cs.c.rays * o.P;
+        sp.slot = o.arr.slot; sp.in_scene = cs.c.object_in_scene + o.k; sp.in_scene_stride = cs.c.objects;
+        sp.empty_alpha = o.m->empty_space_alpha; sp.sigma = o.arr.sigma;
+        return launch_skybox_sigma(sp, cs.s);
+    }
+    if (cs.grouped) return add_job(L, o, mp);
+    if (cs.c.precision != PR_PRECISION_FP32) return launch_mlp_split_sigma(mp, (int)o.cap, cs.terms, cs.s);
+    return launch_mlp_sigma(mp, (int)o.cap, cs.s);
+}
+
+// Evaluation: the fused kernels - gated, stopping in front of the deferred projection, split precision or the scalar one.
+static int evaluate_fused_object(const CallState& cs, Level& L, const ObjectLevel& o, const MlpParams& mp, const FoldParams& fo) {
+    if (cs.grouped) {       // folded and evaluated together once every object of the level is prepared
+        L.folds[L.njobs] = fo;
+        return add_job(L, o, mp);
+    }
+    if (cs.rc) PR_TRY(launch_retain_gate(*cs.rc, L.totals, o.k, 1, cs.s));
+    PR_TRY(launch_adain_fold(fo, cs.s));
+    if (cs.c.precision != PR_PRECISION_FP32 && !cs.naive) return launch_mlp_split(mp, (int)o.cap, cs.terms, cs.s);
+    return launch_mlp(mp, (int)o.cap, cs.naive, o.m, cs.s);
+}
+
+// ---- the phased path -------------------------------------------------------------------------------------------------------
+// BatchNorm in training mode: the batch statistics of the first (second) AdaIN layer are a reduction over every evaluated sample
+// of this object call, between two matmuls.  Differentiable eval-mode calls (SAVE without TRAIN_BN) use the same phases - they
+// leave the pre-BatchNorm activations h1 / h2 behind for the backward pass - with the running statistics frozen.
+static void make_train_job(const CallState& cs, const ObjectLevel& o, const MlpParams& fused, const FoldParams& fo, TrainJob* J) {
+    const SavedPlan& sv = *o.sv;
+    const Plan& plan = cs.plan;
+    J->mp = fused; J->fo = fo; J->o = &o;
+    J->stats = cs.at<double>(sv.stats);               // (zeroed by the fill at the top of the level)
+    J->stat_count = cs.at<int32_t>(sv.stat_count);
+    J->batch = cs.at<float>(cs.save ? sv.batch : plan.batch_stats);
+    J->h1 = cs.at<float>(cs.save ? sv.h1 : plan.h1); J->h2 = cs.at<float>(cs.save ? sv.h2 : plan.h2);
+    MlpParams& mp = J->mp;
+    mp.row_flags = cs.at<int32_t>(cs.save ? sv.row_flags : plan.row_flags);
+    mp.stat_count = J->stat_count;
+    if (cs.save) {
+        mp.save_enc = cs.at<float>(sv.enc);
+        mp.save_act = cs.at<float>(sv.act); mp.save_act_stride = o.cap * o.d.Wpad;
+        mp.save_bits = cs.at<unsigned char>(sv.bits); mp.save_bits_stride = relu_bits_bytes(o.cap, o.d.Wpad);
+        if (o.m->has_bender) {
+            mp.save_bin = cs.at<float>(sv.bin);
+            mp.save_bact = cs.at<float>(sv.bact); mp.save_bact_stride = o.cap * o.d.BWpad;
+            mp.save_bbits = cs.at<unsigned char>(sv.bbits); mp.save_bbits_stride = relu_bits_bytes(o.cap, o.d.BWpad);
+            mp.save_braw = cs.at<float>(sv.braw); mp.save_delta = cs.at<float>(sv.delta);
         }
     }
-    // retention: the last launches store the keys of the camera and of every retained object this call rendered
-    if (rc) PR_TRY(launch_retain_commit(c, objs, *rc, s));
+    mp.phase = 1; mp.h_out = J->h1; mp.h_out_width = o.d.Wpad; mp.stats = J->stats;
+}
+
+// BatchNorm stage s of a job (1: behind phase 1, 2: behind phase 2): where the sums are, the running statistics and the affine
+// they belong to, where the batch values go and where the layer's scale and shift sit in a row of the AdaIN table.
+struct BnStage {
+    const double* stats; int width, width_pad;
+    float* running_mean; float* running_var; long long* batches; const pr_linear_t* affine;
+    float* batch_mean; float* batch_var;
+    int g_off, b_off;
+};
+// ... and the job's launch parameters advanced to phase s + 1.
+static BnStage next_bn_stage(TrainJob& J, int s) {
+    const ModelDims& d = J.o->d;
+    const pr_object_model_t& m = *J.o->m;
+    float* batch = J.batch + (s - 1) * 2 * MAX_WIDTH;
+    MlpParams& mp = J.mp;
+    if (s == 1) {
+        mp.phase = 2; mp.h_in = J.h1; mp.h_in_width = d.Wpad; mp.h_out = J.h2; mp.h_out_width = d.W2pad; mp.stats = J.stats + 2 * MAX_WIDTH;
+        return BnStage{J.stats, d.W, d.Wpad, m.bn1_mean, m.bn1_var, (long long*)m.bn1_batches, &m.affine1, batch, batch + MAX_WIDTH, 0, d.Wpad};
+    }
+    mp.phase = 3; mp.h_in = J.h2; mp.h_in_width = d.W2pad; mp.h_out = nullptr;
+    return BnStage{J.stats + 2 * MAX_WIDTH, d.W2, d.W2pad, m.bn4_mean, m.bn4_var, (long long*)m.bn4_batches, &m.affine4, batch,
+                   batch + MAX_WIDTH, 2 * d.Wpad, 2 * d.Wpad + d.W2pad};
+}
+
+// The fields BnFinalizeParams and BnFoldJob share.
+template <class Params> static void set_bn_stage(Params& p, const CallState& cs, const TrainJob& J, const BnStage& b) {
+    memset(&p, 0, sizeof(p));
+    p.stats = b.stats; p.count = J.stat_count; p.width = b.width; p.width_pad = b.width_pad; p.momentum = 0.1f;
+    p.running_mean = b.running_mean; p.running_var = b.running_var; p.num_batches_tracked = b.batches;
+    p.batch_mean = b.batch_mean; p.batch_var = b.batch_var;
+    p.frozen = (cs.c.flags & PR_FLAG_TRAIN_BN) ? 0 : 1;
+}
+
+// The Hutchinson probes of an object's divergence estimate: explicit, or generated for training calls with a graph (the reference
+// draws them whenever it trains with a graph, object_composer.py:597); neither: the divergence stays zero.
+static bool divergence_probes(const CallState& cs, const Level& L, const TrainJob& J, NoiseRef* probes) {
+    if (!(cs.save && J.o->m->has_bender)) return false;
+    *probes = make_noise(L.noise->divergence[J.o->k], cs.c, NOISE_DIVERGENCE, L.t, J.o->k);
+    if (!(cs.c.flags & PR_FLAG_TRAIN_BN)) probes->generate = 0;
+    return probes->ptr || probes->generate;
+}
+
+// The fields DivergenceParams and DivChainJob share.
+template <class Params> static void set_divergence(Params& q, const CallState& cs, const TrainJob& J, const NoiseRef& probes) {
+    const ObjectLevel& o = *J.o;
+    memset(&q, 0, sizeof(q));
+    q.total = o.total; q.rec_flat = o.rec_flat; q.row_flags = J.mp.row_flags; q.rec_pos = o.rec_pos;
+    q.noise = probes; q.positions = o.P;
+    q.bin = J.mp.save_bin; q.bin_pad = o.d.bin_pad; q.benc = o.d.benc; q.b_octaves = o.m->bender_octaves;
+    q.BW = o.d.BW; q.BWpad = o.d.BWpad; q.b_count = o.m->bender_count; q.b_skip = o.m->bender_skip;
+    q.braw = J.mp.save_braw;
+    bbox_split(*o.m, q.lo, q.hi, nullptr);
+    q.canonical = (cs.c.flags & PR_FLAG_CANONICAL_POSE) ? 1 : 0;
+    q.div = cs.at<float>(o.sv->div);      // (zeroed by the fill at the top of the level)
+}
+
+// What follows the last phase of one object: the normalised-sample count, and its divergence estimate one product per layer.
+static int finish_train_object(const CallState& cs, const Level& L, const TrainJob& J) {
+    if (L.out && L.out->normalised_samples)
+        PR_CHECK_HIP(hipMemcpyAsync(L.out->normalised_samples + J.o->k, J.stat_count, sizeof(int32_t), hipMemcpyDeviceToDevice, cs.s));
+    NoiseRef probes;
+    if (!divergence_probes(cs, L, J, &probes)) return PR_OK;
+    DivergenceParams dp;
+    set_divergence(dp, cs, J, probes);
+    dp.max_rows = (int)J.o->cap;
+    dp.bacts = J.mp.save_bact; dp.bact_stride = J.mp.save_bact_stride; dp.bin_real = J.o->d.bin;
+    dp.layers = J.o->m->bender; dp.out_head = J.o->m->bender_out;
+    dp.t0 = cs.at<float>(cs.plan.div_t0); dp.ta = cs.at<float>(cs.plan.div_ta); dp.tb = cs.at<float>(cs.plan.div_tb);
+    return launch_divergence(dp, cs.s);
+}
+
+// One object at a time: phase 1, statistics and fold, phase 2, statistics and fold, phase 3, divergence.
+static int evaluate_phased_object(const CallState& cs, const Level& L, TrainJob& J) {
+    const int rows = (int)J.o->cap;
+    PR_TRY(launch_mlp(J.mp, rows, false, J.o->m, cs.s));
+    for (int stage = 1; stage <= 2; ++stage) {
+        const BnStage b = next_bn_stage(J, stage);
+        BnFinalizeParams bf;
+        set_bn_stage(bf, cs, J, b);
+        PR_TRY(launch_bn_finalize(bf, cs.s));
+        // (behind stage 1 the second layer is still folded with the running statistics as placeholders)
+        if (stage == 1) { J.fo.bn1_mean = b.batch_mean; J.fo.bn1_var = b.batch_var; }
+        else { J.fo.bn4_mean = b.batch_mean; J.fo.bn4_var = b.batch_var; }
+        PR_TRY(launch_adain_fold(J.fo, cs.s));
+        PR_TRY(launch_mlp(J.mp, rows, false, J.o->m, cs.s));
+    }
+    return finish_train_object(cs, L, J);
+}
+
+// Differentiable calls with several objects: every phase, the statistics with their fold and the divergence chains of the ray
+// benders are one launch each for all objects.
+static int evaluate_phased_group(const CallState& cs, Level& L) {
+    const pr_call_t& c = cs.c;
+    const int K = c.objects;
+    PR_TRY(launch_mlp_group(L.jobs, L.job_rows, K, cs.s));                  // phase 1 of every object
+    for (int stage = 1; stage <= 2; ++stage) {
+        for (int k = 0; k < K; ++k) {
+            TrainJob& J = L.train[k];
+            const pr_object_model_t& m = *J.o->m;
+            const BnStage st = next_bn_stage(J, stage);
+            BnFoldJob& b = L.bn.job[k];
+            set_bn_stage(b, cs, J, st);
+            b.style = c.style + (size_t)k * m.style_features; b.style_stride = K * m.style_features; b.S = m.style_features;
+            b.frames = c.frames; b.eps = m.bn_eps;
+            b.table = J.o->adain; b.row_floats = J.mp.adain_stride;
+            b.affine = *st.affine; b.g_off = st.g_off; b.b_off = st.b_off;
+            if (stage == 2) b.normalised_out = (L.out && L.out->normalised_samples) ? L.out->normalised_samples + k : nullptr;
+            J.mp.split3 = 0;     // (the head phases read fp32 fragments)
+            L.jobs[k] = J.mp;
+        }
+        PR_TRY(launch_bn_fold_group(L.bn, K, cs.s));
+        PR_TRY(launch_mlp_group(L.jobs, L.job_rows, K, cs.s));
+    }
+    long div_rows[PR_MAX_OBJECTS];
+    int div_jobs = 0;
+    for (int k = 0; k < K; ++k) {
+        const TrainJob& J = L.train[k];
+        const ObjectLevel& o = *J.o;
+        NoiseRef probes;
+        if (!divergence_probes(cs, L, J, &probes)) continue;
+        if (!div_chain_supported(o.d.BWpad, o.d.bin_pad)) {
+            PR_TRY(finish_train_object(cs, L, J));          // (unusually wide bender: one product per layer)
+            continue;
+        }
+        DivChainJob& q = L.div[div_jobs];
+        set_divergence(q, cs, J, probes);
+        q.bbits = J.mp.save_bbits; q.bbits_stride = J.mp.save_bbits_stride;
+        for (int j = 0; j < o.m->bender_count; ++j) q.seg0[j] = Seg{o.packed + o.l.b_seg_off[j][0], (j == 0 ? o.d.bin_pad : o.d.BWpad) / 8, 0};
+        q.seg1 = Seg{o.packed + o.l.b_seg_off[o.m->bender_skip][1], o.d.bin_pad / 8, 0};
+        q.w_out = o.packed + o.l.b_out_off;
+        q.tile_counter = L.head_counts + 2 * PR_MAX_OBJECTS + k;
+        div_rows[div_jobs++] = (long)o.cap;
+    }
+    return div_jobs ? launch_div_chain_group(L.div, div_rows, div_jobs, cs.s) : PR_OK;
+}
+
+// ---- evaluation of a level -------------------------------------------------------------------------------------------------
+// Object k behind its sampling launches: its export fill, then its own MLP launches - or its job in the level's grouped ones.
+static int evaluate_object(const CallState& cs, Level& L, int k) {
+    const ObjectLevel& o = L.obj[k];
+    MlpParams mp; FoldParams fo;
+    PR_TRY(mlp_params(cs, L, o, &mp, &fo));
+    if (L.out && L.out->sample_delta[k]) PR_TRY(launch_zero_fill(L.out->sample_delta[k], sizeof(float) * 3 * o.cap, cs.s));
+    if (cs.geo) return evaluate_geometry_object(cs, L, o, mp);
+    if (!cs.phased) return evaluate_fused_object(cs, L, o, mp, fo);
+    TrainJob& J = L.train[k];
+    make_train_job(cs, o, mp, fo, &J);
+    if (!cs.train_grouped) return evaluate_phased_object(cs, L, J);
+    return add_job(L, o, J.mp);
+}
+
+// The grouped launches of a level, once every object is prepared.
+static int evaluate_grouped(const CallState& cs, Level& L) {
+    if (cs.train_grouped) return evaluate_phased_group(cs, L);
+    if (!cs.grouped || L.njobs == 0) return PR_OK;
+    const bool split = cs.c.precision != PR_PRECISION_FP32;
+    if (cs.geo)
+        return split ? launch_mlp_split_sigma_group(L.jobs, L.job_rows, L.njobs, cs.terms, cs.s)
+                     : launch_mlp_sigma_group(L.jobs, L.job_rows, L.njobs, cs.s);
+    if (cs.rc) PR_TRY(launch_retain_gate(*cs.rc, L.totals, 0, L.njobs, cs.s));      // (behind the block scans of the level)
+    PR_TRY(launch_adain_fold_group(L.folds, L.njobs, cs.s));
+    return split ? launch_mlp_split_group(L.jobs, L.job_rows, L.njobs, cs.terms, cs.s) : launch_mlp_group(L.jobs, L.job_rows, L.njobs, cs.s);
+}
+
+// ---- compositing -----------------------------------------------------------------------------------------------------------
+static int composite_level(const CallState& cs, const Level& L) {
+    const pr_call_t& c = cs.c;
+    const int K = c.objects, t = L.t;
+    CompositeParams cp;
+    memset(&cp, 0, sizeof(cp));
+    cp.frames = c.frames; cp.rays = c.rays; cp.objects = K; cp.static_objects = c.static_objects;
+    cp.F = cs.objs[0].coarse.output_features;
+    cp.fix_overlaps = (c.flags & PR_FLAG_FIX_OVERLAPS) ? 1 : 0; cp.sigmoid = (c.flags & PR_FLAG_SIGMOID_FEATURES) ? 1 : 0;
+    for (int k = 0; k < K; ++k) cp.total_positions += L.obj[k].P;
+    cp.sort_size = 64;
+    while (cp.sort_size < cp.total_positions) cp.sort_size <<= 1;
+    cp.ray_directions = c.ray_directions;
+    cp.noise_global = perturb_noise(L.noise->integrate_global, c, NOISE_INTEGRATE_GLOBAL, t, 0);
+    for (int k = 0; k < K; ++k) {
+        const ObjectLevel& ol = L.obj[k];
+        if (cs.defer) {
+            cp.proj_w[k] = ol.packed + ol.l.h6p_off;
+            cp.proj_k = projection_k(ol.d.W2);
+        }
+        CompositeObject& o = cp.obj[k];
+        o.t = ol.arr.t; o.sigma = ol.arr.sigma; o.slot = ol.arr.slot; o.dispmag = ol.arr.dispmag;
+        o.divergence = (cs.save && ol.m->has_bender) ? cs.at<const float>(ol.sv->div) : nullptr;
+        if (o.divergence) cp.any_divergence = 1;
+        o.feat = cs.geo ? nullptr : ol.arr.feat;
+        o.noise = perturb_noise(L.noise->integrate[k], c, NOISE_INTEGRATE, t, k);
+        o.positions = ol.P;
+        if (L.out) o.out = L.out->object[k];
+    }
+    if (L.out) { cp.global = L.out->global; cp.decoder = L.out->decoder; }
+    if (cs.defer) {
+        cp.out_features = cp.F;
+        cp.F = hidden_row_floats(cs.objs[0].coarse.layers_width / 2);
+        cp.pooled = cs.at<float>(cs.plan.pooled);
+    }
+    if (cs.geo) {
+        cp.geometry = 1;
+        cp.sigmoid = 0;
+        if (cs.geos[t]) { cp.visibility = cs.geos[t]->visibility; cp.front_object = cs.geos[t]->front_object; }
+    }
+    PR_TRY(launch_composite(cp, cs.s));
+    return cs.defer ? launch_projection(cp, cs.s) : PR_OK;
+}
+
+// ---- optional exports ------------------------------------------------------------------------------------------------------
+static int export_level(const CallState& cs, const Level& L) {
+    const pr_outputs_t* out = L.out;
+    if (!out) return PR_OK;
+    const int K = cs.c.objects;
+    auto copy = [&](void* dst, const void* src, size_t count) -> int {      // (count 4-byte elements; dst == NULL: not asked for)
+        if (dst) PR_CHECK_HIP(hipMemcpyAsync(dst, src, 4 * count, hipMemcpyDeviceToDevice, cs.s));
+        return PR_OK;
+    };
+    for (int k = 0; k < K; ++k) {
+        const ObjectLevel& o = L.obj[k];      // (wherever the arrays live)
+        PR_TRY(copy(out->sample_t[k], o.arr.t, o.cap));
+        PR_TRY(copy(out->sample_sigma[k], o.arr.sigma, o.cap));
+        PR_TRY(copy(out->sample_slot[k], o.arr.slot, o.cap));
+    }
+    PR_TRY(copy(out->evaluated_samples, L.totals, K));
+    if (out->head_samples && cs.geo)     // no sample goes through the feature head (a kernel fill: no memset node)
+        return launch_zero_fill(out->head_samples, sizeof(int32_t) * K, cs.s);
+    // without the gate every evaluated sample goes through the feature head
+    return copy(out->head_samples, cs.gate ? L.head_counts : L.totals, K);
+}
+
+// What the stages would otherwise refuse with kernels of the call already on the stream: host checks, no device work.
+static int validate_stages(const pr_call_t& c, const pr_object_t* objs) {
+    // (with PR_FLAG_SAVE_FOR_BACKWARD validate_call has refused the scalar kernel already)
+    PR_REQUIRE(!((c.flags & PR_FLAG_NAIVE_MLP) && (c.flags & PR_FLAG_TRAIN_BN)), "the scalar debugging kernel has no train-mode BatchNorm");
+    for (int t = 0; t < (c.use_fine ? 2 : 1); ++t)
+        for (int k = 0; k < c.objects; ++k) {
+            const pr_object_model_t& m = t ? objs[k].fine : objs[k].coarse;
+            PR_REQUIRE(m.output_features == objs[0].coarse.output_features, "all objects must share output_features");
+            if (group_train_active(c))      // (the grouped statistics-and-fold launch reads them unconditionally)
+                PR_REQUIRE(m.affine1.weight && m.affine1.bias && m.bn1_mean && m.bn1_var && m.affine4.weight && m.affine4.bias && m.bn4_mean &&
+                               m.bn4_var, "AdaIN parameters missing");
+        }
     return PR_OK;
+}
+
+// Per level: one fill, then per object sampling and evaluation - the launches of an object back to back, object after object,
+// unless the call groups a stage, which then follows the loop as one launch for all objects -, compositing, exports.
+static int render(const CallState& cs) {
+    const pr_call_t& c = cs.c;
+    const int K = c.objects;
+    // retention: the first launches compare the cached keys with this call's inputs and set the reuse flags
+    if (cs.rc) PR_TRY(launch_retain_probe(c, cs.objs, *cs.rc, cs.s));
+    Level& L = g_level;
+    for (int t = 0; t < (c.use_fine ? 2 : 1); ++t) {
+        L.t = t; L.tp = &cs.plan.type[t]; L.noise = t ? &c.noise_fine : &c.noise_coarse; L.out = cs.outs[t]; L.njobs = 0;
+        L.totals = cs.at<int32_t>(L.tp->totals); L.head_counts = cs.at<int32_t>(L.tp->head_counts);
+        for (int k = 0; k < K; ++k) PR_TRY(make_object_level(cs, t, k, &L.obj[k]));
+        // one fill: feature-head / tile counters, and - training / differentiable calls - every object's batch-statistics
+        // accumulators and divergence array
+        PR_TRY(launch_zero_fill(cs.ws + L.tp->zero_begin, L.tp->zero_bytes, cs.s));
+        // (every object has its own sample records in the calls that group a stage: their coarse placement is grouped too)
+        const bool placed = t == 0 && (cs.grouped || cs.train_grouped);
+        if (placed) PR_TRY(sample_level_grouped(cs, L));
+        for (int k = 0; k < K; ++k) {
+            if (!placed) PR_TRY(sample_object(cs, L, L.obj[k]));
+            PR_TRY(evaluate_object(cs, L, k));
+        }
+        PR_TRY(evaluate_grouped(cs, L));
+        PR_TRY(composite_level(cs, L));
+        PR_TRY(export_level(cs, L));
+    }
+    // retention: the last launches store the keys of the camera and of every retained object this call rendered
+    if (cs.rc) PR_TRY(launch_retain_commit(c, cs.objs, *cs.rc, cs.s));
+    return PR_OK;
+}
+
+// Host checks of a geometry-only call (PR_FLAG_GEOMETRY_ONLY): no device work, so that a refusal precedes everything else.
+static int validate_geometry(const pr_call_t& c, const pr_retained_t* retained, const pr_outputs_t* coarse, const pr_outputs_t* fine) {
+    PR_REQUIRE(!(c.flags & PR_FLAG_TRAIN_BN), "a geometry-only call runs no feature head: PR_FLAG_TRAIN_BN is set (batch statistics need the head)");
+    PR_REQUIRE(!(c.flags & PR_FLAG_SAVE_FOR_BACKWARD), "a geometry-only call has no backward pass: PR_FLAG_SAVE_FOR_BACKWARD is set");
+    PR_REQUIRE(!(c.flags & PR_FLAG_NAIVE_MLP), "a geometry-only call is not supported with PR_FLAG_NAIVE_MLP");
+    PR_REQUIRE(retained == nullptr, "a geometry-only call cannot be retained: pr_retained_t is not NULL (the cache layout holds feature rows)");
+    const pr_outputs_t* levels[2] = {coarse, c.use_fine ? fine : nullptr};
+    for (int t = 0; t < 2; ++t) {
+        const pr_outputs_t* o = levels[t];
+        if (!o) continue;
+        const char* level = t ? "fine" : "coarse";
+        for (int k = 0; k < PR_MAX_OBJECTS; ++k)
+            PR_REQUIRE(o->object[k].integrated_features == nullptr,
+                       "a geometry-only call writes no features: integrated_features of object %d (%s) is not NULL", k, level);
+        PR_REQUIRE(o->global.integrated_features == nullptr,
+                   "a geometry-only call writes no features: integrated_features of the global entry (%s) is not NULL", level);
+        PR_REQUIRE(o->decoder.groups <= 0, "a geometry-only call writes no features: decoder.groups is %d (%s)", o->decoder.groups, level);
+    }
+    return PR_OK;
+}
+
+// Every render entry point ends here (geometry_* : the extras of pr_render_geometry, NULL elsewhere): every refusal, then the stages.
+static int render_entry(const pr_call_t* call, const pr_object_t* objects, const pr_occupancy_t* occupancy,
+                        const pr_retained_t* retained, const pr_fine_guide_t* guide, const pr_outputs_t* coarse,
+                        const pr_outputs_t* fine, const pr_geometry_t* geometry_coarse, const pr_geometry_t* geometry_fine,
+                        void* workspace, size_t workspace_bytes, void* stream) {
+    PR_REQUIRE(call && objects && workspace, "pr_render_forward: NULL argument");
+    const pr_call_t& c = *call;
+    PR_TRY(validate_occupancy(c, objects, occupancy));
+    PR_TRY(validate_call(c, objects));
+    if (c.flags & PR_FLAG_GEOMETRY_ONLY) PR_TRY(validate_geometry(c, retained, coarse, fine));
+    if (guide && guide->object_mask == 0) guide = nullptr;
+    GuidePlan gplan;
+    if (guide) PR_TRY(validate_guide(c, objects, guide, &gplan));
+    static thread_local RetainCtx ctx;
+    if (retained) PR_TRY(validate_retained(c, objects, occupancy, guide, retained, coarse, fine, &ctx));
+    PR_TRY(validate_stages(c, objects));
+    Plan plan;
+    PR_TRY(make_plan(c, objects, &plan));
+    if (workspace_bytes < plan.bytes) {
+        set_error("workspace too small: %zu bytes given, %zu needed", workspace_bytes, plan.bytes);
+        return PR_ERR_WORKSPACE;
+    }
+    PR_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
+    const pr_outputs_t* outs[2] = {coarse, fine};
+    const pr_geometry_t* geos[2] = {geometry_coarse, geometry_fine};
+    const bool save = (c.flags & PR_FLAG_SAVE_FOR_BACKWARD) != 0;
+    const CallState cs = {c, objects, occupancy, retained ? &ctx : nullptr, guide, &gplan, outs, geos, static_cast<char*>(workspace), plan,
+                          (hipStream_t)stream, (c.flags & PR_FLAG_GEOMETRY_ONLY) != 0, (c.flags & PR_FLAG_NAIVE_MLP) != 0, gate_active(c),
+                          defer_active(c, objects), save, save || (c.flags & PR_FLAG_TRAIN_BN), group_active(c), group_train_active(c),
+                          c.precision == PR_PRECISION_F16 ? 1 : 3};
+    return render(cs);
 }
 
 }  // namespace pr
@@ -959,34 +1015,6 @@ extern "C" int pr_fine_guide_size(const pr_call_t* call, const pr_object_t* obje
     return PR_OK;
 }
 
-namespace pr {
-// Host checks of a geometry-only call (PR_FLAG_GEOMETRY_ONLY): no device work, so that a refusal precedes everything else.
-static int validate_geometry(const pr_call_t& c, const pr_retained_t* retained, const pr_outputs_t* coarse, const pr_outputs_t* fine) {
-    PR_REQUIRE(!(c.flags & PR_FLAG_TRAIN_BN), "a geometry-only call runs no feature head: PR_FLAG_TRAIN_BN is set (batch statistics need the head)");
-    PR_REQUIRE(!(c.flags & PR_FLAG_SAVE_FOR_BACKWARD), "a geometry-only call has no backward pass: PR_FLAG_SAVE_FOR_BACKWARD is set");
-    PR_REQUIRE(!(c.flags & PR_FLAG_NAIVE_MLP), "a geometry-only call is not supported with PR_FLAG_NAIVE_MLP");
-    PR_REQUIRE(retained == nullptr, "a geometry-only call cannot be retained: pr_retained_t is not NULL (the cache layout holds feature rows)");
-    const pr_outputs_t* levels[2] = {coarse, c.use_fine ? fine : nullptr};
-    for (int t = 0; t < 2; ++t) {
-        const pr_outputs_t* o = levels[t];
-        if (!o) continue;
-        const char* level = t ? "fine" : "coarse";
-        for (int k = 0; k < PR_MAX_OBJECTS; ++k)
-            PR_REQUIRE(o->object[k].integrated_features == nullptr,
-                       "a geometry-only call writes no features: integrated_features of object %d (%s) is not NULL", k, level);
-        PR_REQUIRE(o->global.integrated_features == nullptr,
-                   "a geometry-only call writes no features: integrated_features of the global entry (%s) is not NULL", level);
-        PR_REQUIRE(o->decoder.groups <= 0, "a geometry-only call writes no features: decoder.groups is %d (%s)", o->decoder.groups, level);
-    }
-    return PR_OK;
-}
-
-static int render_entry(const pr_call_t* call, const pr_object_t* objects, const pr_occupancy_t* occupancy, const pr_retained_t* retained,
-                        const pr_fine_guide_t* guide, const pr_outputs_t* coarse, const pr_outputs_t* fine,
-                        const pr_geometry_t* geometry_coarse, const pr_geometry_t* geometry_fine, void* workspace, size_t workspace_bytes,
-                        void* stream);
-}  // namespace pr
-
 extern "C" int pr_render_forward_guided(const pr_call_t* call, const pr_object_t* objects, const pr_occupancy_t* occupancy,
                                         const pr_retained_t* retained, const pr_fine_guide_t* guide, const pr_outputs_t* coarse,
                                         const pr_outputs_t* fine, void* workspace, size_t workspace_bytes, void* stream) {
@@ -1002,35 +1030,6 @@ extern "C" int pr_render_geometry(const pr_call_t* call, const pr_object_t* obje
     return pr::render_entry(call, objects, occupancy, nullptr, guide, coarse, fine, geometry_coarse, geometry_fine, workspace,
                             workspace_bytes, stream);
 }
-
-namespace pr {
-// Every render entry point ends here (geometry_* : the extras of pr_render_geometry, NULL elsewhere).
-static int render_entry(const pr_call_t* call, const pr_object_t* objects, const pr_occupancy_t* occupancy,
-                        const pr_retained_t* retained, const pr_fine_guide_t* guide, const pr_outputs_t* coarse,
-                        const pr_outputs_t* fine, const pr_geometry_t* geometry_coarse, const pr_geometry_t* geometry_fine,
-                        void* workspace, size_t workspace_bytes, void* stream) {
-    PR_REQUIRE(call && objects && workspace, "pr_render_forward: NULL argument");
-    PR_TRY(pr::validate_occupancy(*call, objects, occupancy));
-    PR_TRY(pr::validate_call(*call, objects));
-    if (call->flags & PR_FLAG_GEOMETRY_ONLY) PR_TRY(pr::validate_geometry(*call, retained, coarse, fine));
-    if (guide && guide->object_mask == 0) guide = nullptr;
-    pr::GuidePlan gplan;
-    if (guide) PR_TRY(pr::validate_guide(*call, objects, guide, &gplan));
-    static thread_local pr::RetainCtx ctx;
-    if (retained) PR_TRY(pr::validate_retained(*call, objects, occupancy, guide, retained, coarse, fine, &ctx));
-    pr::Plan plan;
-    PR_TRY(pr::make_plan(*call, objects, &plan));
-    if (workspace_bytes < plan.bytes) {
-        pr::set_error("workspace too small: %zu bytes given, %zu needed", workspace_bytes, plan.bytes);
-        return PR_ERR_WORKSPACE;
-    }
-    PR_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-    const pr_outputs_t* outs[2] = {coarse, fine};
-    const pr_geometry_t* geos[2] = {geometry_coarse, geometry_fine};
-    return pr::render(*call, objects, occupancy, retained ? &ctx : nullptr, guide, &gplan, outs, geos, static_cast<char*>(workspace), plan,
-                      (hipStream_t)stream);
-}
-}  // namespace pr
 
 namespace pr {
 __global__ __launch_bounds__(256) void k_noise_fill(NoiseRef n, int normal, long count, float* out) {

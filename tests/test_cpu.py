@@ -281,6 +281,36 @@ int main(void) {
     assert f"sizeof(pr_call_t) {C.sizeof(_lib.Call)}," in run.stdout and f"sizeof(pr_object_model_t) {C.sizeof(_lib.ObjectModel)}," in run.stdout
 
 
+def test_stage_refusals_precede_every_launch(built_library):
+    """What the render stages used to refuse with kernels of the same call already on the stream is refused by the host checks of
+    the entry point: the scalar kernel in training mode, objects with different ``output_features``, a grouped differentiable call
+    without AdaIN parameters - each with a workspace size that would pass, so only the order of the checks keeps this off the
+    device (which this machine does not have)."""
+    from tests.test_occupancy_cpu import _host_call
+    lib = built_library
+    comp = ObjectComposer(configs.tennis_config())
+    call, objs = _host_call(comp, 4)
+    outs = _lib.Outputs()
+
+    def status(size):
+        return lib.pr_render_forward(C.byref(call), objs, C.byref(outs), None, 256, size, None), lib.pr_last_error()
+
+    st, msg = status(0)                       # a well-formed request passes every host check and stops at the (zero-sized) workspace
+    assert st == -2 and b"workspace too small" in msg, (st, msg)
+    call.flags = _lib.PR_FLAG_NAIVE_MLP | _lib.PR_FLAG_TRAIN_BN
+    assert status(1 << 40) == (-1, b"the scalar debugging kernel has no train-mode BatchNorm")
+    call.flags = 0
+    objs[3].coarse.output_features += 1
+    assert status(1 << 40) == (-1, b"all objects must share output_features")
+    objs[3].coarse.output_features -= 1
+    call.flags = _lib.PR_FLAG_SAVE_FOR_BACKWARD
+    kept, objs[2].coarse.affine4.bias = objs[2].coarse.affine4.bias, None
+    assert status(1 << 40) == (-1, b"AdaIN parameters missing")
+    objs[2].coarse.affine4.bias = kept
+    st, msg = status(0)
+    assert st == -2 and b"workspace too small" in msg, (st, msg)
+
+
 def test_struct_sizes_match_header_layout():
     """ctypes mirrors must have the C sizes (pointer = 8, int32 = 4, natural alignment)."""
     assert C.sizeof(_lib.Linear) == 24
