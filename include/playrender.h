@@ -609,6 +609,83 @@ int pr_band_plan(const pr_band_t* s, void* workspace, size_t workspace_bytes, vo
 int pr_band_fill(const pr_band_t* s, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Simplification of extracted meshes by vertex clustering on a uniform grid (Rossignac-Borrel): every vertex goes to the grid cell
+ * that contains it, a cell's vertices become one vertex at their mean, triangles that lose a corner that way or repeat another one
+ * disappear.  Integer accumulation throughout: the result does not depend on the execution order.
+ *   Input: G meshes packed as pr_extract_surface leaves them - vertices (V, 3) fp32, optional normals (V, 3), triangles (T, 3) int32
+ *     LOCAL to their group, vertex_offsets (G + 1), triangle_offsets (G + 1), all on the device; group g owns the rows
+ *     [off[g], off[g+1]) and has V_g = off[g+1] - off[g] vertices.  total_vertices / total_triangles are V and T as host values
+ *     (vertex_offsets[G], triangle_offsets[G]): the host sizes the launches and the workspace with them; offsets that leave
+ *     [0, V] / [0, T] or decrease are clamped, never followed out of the arrays.
+ *   Grid: origin[3], cell[3] (finite, > 0), cells[3] (each >= 1, product <= PR_SIMPLIFY_MAX_CELLS = 2^21), shared by the groups.
+ *   Cell of a vertex, per axis in fp32 without contraction: q = (v - origin) / cell; q = 0 unless q >= 0 (NaN and negatives);
+ *     q = (float)cells if q > (float)cells; c = min((int)q, cells - 1); w = q - (float)c, in [0, 1]; f = (int64)(w 2^20) - the product
+ *     is exact, then truncated.  Flat cell index (c0 cells[1] + c1) cells[2] + c2.  Every vertex of a group's slice is clustered,
+ *     whether or not a triangle refers to it.
+ *   Cluster sums, per (group, cell): the member count n and the three int64 sums F of f.
+ *   Output vertices: one per occupied cell, ordered by group, then flat cell index.  Position per axis in fp64 without contraction,
+ *     then rounded to fp32: (double)origin + ((double)c + (double)F / ((double)n 1048576.0)) (double)cell - the mean of the members
+ *     up to the 2^-20-of-a-cell quantisation.
+ *   Output normals (optional; they need input normals): a component x of a member normal contributes llrint(x 2^20) if |x| <= 4,
+ *     else 0 (a NaN contributes 0).  With S the three int64 sums as doubles, len = sqrt((S0 S0 + S1 S1) + S2 S2); the normal is
+ *     (float)(S / len), and (0,0,0) when len == 0.
+ *   Triangles: one with an index outside [0, V_g) is dropped and counted.  Each corner is replaced by its cluster's output index, local
+ *     to the group; a triangle with two equal corners is dropped (degenerate).  The rest are rotated cyclically so that the smallest
+ *     index comes first - the orientation is kept.  Among triangles with the same rotated triple only the one with the lowest input
+ *     index survives; with PR_SIMPLIFY_KEEP_DUPLICATES all of them do.  (a,b,c) and (a,c,b) are not duplicates of each other: both
+ *     stay.  Output order is input order.  Output vertices that no surviving triangle refers to are kept.
+ *   Other outputs: vertex_map (V) int32, optional: the output index of every input vertex, local to its group.  counts (G, 4) int32,
+ *     always written: clusters, non-degenerate triangles, output triangles, triangles dropped for an index out of range.
+ *     out_vertex_offsets / out_triangle_offsets (G + 1), always written with the true totals.
+ * An element at or beyond its capacity is not written.  With out_vertices, out_normals, out_triangles and vertex_map all NULL the call
+ * only counts.
+ * Workspace bytes = the sum of these regions, each rounded up to 256 bytes, with C = cells[0] cells[1] cells[2], D = ceil(C / 256),
+ *   BV = ceil(V / 256) + G and BT = ceil(T / 256) + G (upper bounds of the blocks of 256 vertices / triangles, none across two groups):
+ *   4 G C (member counts, then output indices) + 24 G C (position sums) + 24 G C (normal sums; 0 without input normals) +
+ *   4 V (cell, then output index of every vertex) + 4 T (table slot of every triangle) + 16 T (table keys, 2 T slots) +
+ *   8 T (table minima) + 4 x 4 (G + 1) (per group: first vertex, first triangle, first vertex block, first triangle block) +
+ *   2 x 4 G D (block sums of the occupied cells and their scan) + 2 x 4 BT (block sums of the surviving triangles and their scan) +
+ *   8 (the totals).
+ * Twelve kernel launches on `stream` (eleven when counting), no memset, no memcpy, no allocation, no synchronisation: capturable into
+ * a HIP graph.  Integer atomics only.  The duplicate table's layout depends on the order of arrival, its minima - the result - do not.
+ * Refused (PR_ERR_INVALID, before any device work; by pr_simplify_workspace_size too, except the workspace itself): NULL vertices,
+ * triangles, offsets (in or out) or counts, groups < 1, a cells entry < 1 or a product above 2^21, a cell size that is not finite or
+ * not > 0, a non-finite origin, unknown flag bits, a negative capacity or total, out_normals without normals or without out_vertices,
+ * totals so large that an int32 count or the workspace sum overflows (V + 256 G or 2 T + 256 G at or above 2^31, a workspace of
+ * 2^62 bytes or more), a NULL, misaligned or too small workspace.
+ */
+#define PR_SIMPLIFY_KEEP_DUPLICATES 1u
+#define PR_SIMPLIFY_MAX_CELLS 2097152
+typedef struct pr_simplify_t {
+    int32_t groups;                       /* G >= 1 */
+    int32_t total_vertices;               /* V = vertex_offsets[G], as a host value, >= 0 */
+    int32_t total_triangles;              /* T = triangle_offsets[G], as a host value, >= 0 */
+    uint32_t flags;                       /* PR_SIMPLIFY_KEEP_DUPLICATES or 0 */
+    float origin[3];                      /* finite */
+    float cell[3];                        /* finite, > 0 */
+    int32_t cells[3];                     /* each >= 1, product <= PR_SIMPLIFY_MAX_CELLS */
+    int32_t max_vertices;                 /* rows of out_vertices / out_normals, >= 0 */
+    int32_t max_triangles;                /* rows of out_triangles, >= 0 */
+    uint32_t reserved_;
+    const float* vertices;                /* (V, 3) */
+    const float* normals;                 /* (V, 3) or NULL */
+    const int32_t* triangles;             /* (T, 3), indices local to the group */
+    const int32_t* vertex_offsets;        /* (G + 1) */
+    const int32_t* triangle_offsets;      /* (G + 1) */
+    float* out_vertices;                  /* (max_vertices, 3) or NULL */
+    float* out_normals;                   /* (max_vertices, 3) or NULL; needs normals and out_vertices */
+    int32_t* out_triangles;               /* (max_triangles, 3) or NULL; indices local to the group */
+    int32_t* vertex_map;                  /* (V) or NULL */
+    int32_t* counts;                      /* (G, 4), always written */
+    int32_t* out_vertex_offsets;          /* (G + 1), always written */
+    int32_t* out_triangle_offsets;        /* (G + 1), always written */
+} pr_simplify_t;
+/* Host computation, no device work; refuses everything above that does not concern the workspace. */
+int pr_simplify_workspace_size(const pr_simplify_t* s, size_t* bytes);
+/* `workspace`: 256-byte aligned, pr_simplify_workspace_size bytes. */
+int pr_simplify_mesh(const pr_simplify_t* s, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Backward pass of pr_render_forward (what torch.autograd does for the reference's op graph when
  * training/trainer_backpropagated_autoencoder.py:349 calls total_loss.backward()).  The forward call must
  * have run with PR_FLAG_SAVE_FOR_BACKWARD (with or without PR_FLAG_TRAIN_BN) on the same `call`, `objects` and

@@ -221,6 +221,20 @@ class Band(C.Structure):
                 ("point_index", C.c_void_p), ("positions", C.c_void_p), ("exact", C.c_void_p)]
 
 
+SIMPLIFY_KEEP_DUPLICATES = 1     # PR_SIMPLIFY_KEEP_DUPLICATES
+SIMPLIFY_MAX_CELLS = 1 << 21     # PR_SIMPLIFY_MAX_CELLS
+
+
+class Simplify(C.Structure):
+    """pr_simplify_t (include/playrender.h)."""
+    _fields_ = [("groups", C.c_int32), ("total_vertices", C.c_int32), ("total_triangles", C.c_int32), ("flags", C.c_uint32),
+                ("origin", C.c_float * 3), ("cell", C.c_float * 3), ("cells", C.c_int32 * 3), ("max_vertices", C.c_int32),
+                ("max_triangles", C.c_int32), ("reserved_", C.c_uint32), ("vertices", C.c_void_p), ("normals", C.c_void_p),
+                ("triangles", C.c_void_p), ("vertex_offsets", C.c_void_p), ("triangle_offsets", C.c_void_p), ("out_vertices", C.c_void_p),
+                ("out_normals", C.c_void_p), ("out_triangles", C.c_void_p), ("vertex_map", C.c_void_p), ("counts", C.c_void_p),
+                ("out_vertex_offsets", C.c_void_p), ("out_triangle_offsets", C.c_void_p)]
+
+
 # every exported symbol of include/playrender.h : (restype, argtypes)
 class SceneSetup(C.Structure):
     """pr_scene_setup_t (include/playrender.h)."""
@@ -262,6 +276,8 @@ SYMBOLS = {
     "pr_band_workspace_size": (C.c_int, [C.POINTER(Band), C.POINTER(C.c_size_t)]),
     "pr_band_plan": (C.c_int, [C.POINTER(Band), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_band_fill": (C.c_int, [C.POINTER(Band), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pr_simplify_workspace_size": (C.c_int, [C.POINTER(Simplify), C.POINTER(C.c_size_t)]),
+    "pr_simplify_mesh": (C.c_int, [C.POINTER(Simplify), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_backward_workspace_size": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(C.c_size_t)]),
     "pr_render_backward": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(OutputGrads), C.POINTER(OutputGrads),
                                      C.POINTER(InputGrads), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -13,10 +13,15 @@ the mesher and of ``pr_occupancy_build``.
 
 ``refine_band`` (``pr_band_plan`` / ``pr_band_fill``) fills a lattice from its coarse skeleton and evaluates the field only in a band
 around the level set - the opt-in approximation behind ``ObjectComposer.density_band`` and ``extract_mesh(stride=...)``.
+
+``simplify_meshes`` / ``Mesh.simplified`` (``pr_simplify_mesh``) reduce extracted meshes by vertex clustering on a uniform grid, on
+the device and independent of the execution order - what ``extract_surface(simplify=k)`` and ``extract_mesh(simplify=k)`` apply.
 """
 from __future__ import annotations
 
 import ctypes as C
+import math
+import operator
 from dataclasses import dataclass
 from typing import List, Optional, Sequence
 
@@ -57,6 +62,10 @@ class Mesh:
                 f.writelines("vn %.9g %.9g %.9g\n" % tuple(row) for row in n)
             for a, b, c in (self.triangles.detach().cpu() + 1).tolist():
                 f.write(f"f {a}//{a} {b}//{b} {c}//{c}\n" if n is not None else f"f {a} {b} {c}\n")
+
+    def simplified(self, origin, cell, cells, **kw) -> "Mesh":
+        """The mesh clustered on the grid ``origin`` / ``cell`` / ``cells``: ``simplify_meshes`` of this one mesh."""
+        return simplify_meshes([self], origin, cell, cells, **kw)[0]
 
 
 def surface_struct(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float, vertex_offsets: torch.Tensor,
@@ -261,8 +270,137 @@ def refine_band(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float,
     return sigma, exact, counts
 
 
+def simplify_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offsets: torch.Tensor, triangle_offsets: torch.Tensor,
+                    total_vertices: int, total_triangles: int, origin, cell, cells, counts: torch.Tensor, out_vertex_offsets: torch.Tensor,
+                    out_triangle_offsets: torch.Tensor, *, normals: Optional[torch.Tensor] = None,
+                    out_vertices: Optional[torch.Tensor] = None, out_normals: Optional[torch.Tensor] = None,
+                    out_triangles: Optional[torch.Tensor] = None, vertex_map: Optional[torch.Tensor] = None,
+                    keep_duplicates: bool = False) -> _lib.Simplify:
+    """``pr_simplify_t`` over prepared tensors (fp32 / int32, contiguous, one device); the capacities are the outputs' rows."""
+    s = _lib.Simplify()
+    s.groups = vertex_offsets.numel() - 1
+    s.total_vertices = int(total_vertices)
+    s.total_triangles = int(total_triangles)
+    s.flags = _lib.SIMPLIFY_KEEP_DUPLICATES if keep_duplicates else 0
+    for a in range(3):
+        s.origin[a] = float(origin[a])
+        s.cell[a] = float(cell[a])
+        s.cells[a] = int(cells[a])
+    s.max_vertices = 0 if out_vertices is None else out_vertices.size(0)
+    s.max_triangles = 0 if out_triangles is None else out_triangles.size(0)
+    for name, t in (("vertices", vertices), ("normals", normals), ("triangles", triangles), ("vertex_offsets", vertex_offsets),
+                    ("triangle_offsets", triangle_offsets), ("out_vertices", out_vertices), ("out_normals", out_normals),
+                    ("out_triangles", out_triangles), ("vertex_map", vertex_map), ("counts", counts),
+                    ("out_vertex_offsets", out_vertex_offsets), ("out_triangle_offsets", out_triangle_offsets)):
+        setattr(s, name, None if t is None else t.data_ptr())
+    return s
+
+
+def _cluster_grid(origin, cell, cells):
+    """The host values of a cluster grid, checked as ``pr_simplify_mesh`` checks them."""
+    try:
+        origin, cell, cells = [float(x) for x in origin], [float(x) for x in cell], [operator.index(x) for x in cells]
+    except TypeError:
+        raise ValueError("origin and cell must be three numbers each, cells three integers") from None
+    if not len(origin) == len(cell) == len(cells) == 3:
+        raise ValueError("origin, cell and cells must have three entries each")
+    if not all(math.isfinite(x) for x in origin):
+        raise ValueError(f"origin must be finite, got {origin}")
+    if not all(math.isfinite(x) and x > 0 for x in cell):
+        raise ValueError(f"cell sizes must be finite and > 0, got {cell}")
+    if not all(n >= 1 for n in cells) or cells[0] * cells[1] * cells[2] > _lib.SIMPLIFY_MAX_CELLS:
+        raise ValueError(f"cells must be >= 1 per axis with a product of at most 2^21 = {_lib.SIMPLIFY_MAX_CELLS}, got {cells}")
+    return origin, cell, cells
+
+
+def lattice_cluster_grid(axes: Sequence, k: int):
+    """The cluster grid aligned with a lattice, ``k`` lattice steps per cell: per axis ``origin = axes[a][0]``,
+    ``cell = k (axes[a][-1] - axes[a][0]) / (n_a - 1)``, ``cells = ceil((n_a - 1) / k)``.  Reads the ends of the axes back."""
+    k = operator.index(k)
+    if k < 1:
+        raise ValueError(f"the cells of a lattice-aligned grid span k >= 1 lattice steps, got {k}")
+    origin, cell, cells = [], [], []
+    for a in axes:
+        a = torch.as_tensor(a).detach().to(torch.float32).reshape(-1)
+        if a.numel() < 2:
+            raise ValueError("a lattice has at least 2 points per axis")
+        first, last = a[[0, -1]].cpu().tolist()
+        origin.append(first)
+        cell.append(k * (last - first) / (a.numel() - 1))
+        cells.append(-(-(a.numel() - 1) // k))
+    return origin, cell, cells
+
+
+def _simplify_packed(vertices, normals, triangles, vertex_offsets, triangle_offsets, origin, cell, cells, keep_duplicates):
+    """``pr_simplify_mesh`` on packed meshes (device tensors; ``vertex_offsets`` / ``triangle_offsets`` are host lists): a counting
+    call, one read-back of the two offset arrays, an exactly sized emitting call.  Returns the list of meshes."""
+    lib = _lib.load()
+    dev = vertices.device
+    G, V, T = len(vertex_offsets) - 1, vertex_offsets[-1], triangle_offsets[-1]
+    if vertices.size(0) == 0:                                      # (an empty tensor has no address: the library refuses NULL)
+        vertices = torch.empty((1, 3), dtype=torch.float32, device=dev)
+        normals = None if normals is None else torch.empty((1, 3), dtype=torch.float32, device=dev)
+    if triangles.size(0) == 0:
+        triangles = torch.empty((1, 3), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        offsets_in = torch.tensor([vertex_offsets, triangle_offsets], dtype=torch.int32).to(dev)
+        offsets = torch.empty((2, G + 1), dtype=torch.int32, device=dev)
+        counts = torch.empty((G, 4), dtype=torch.int32, device=dev)
+        common = (vertices, triangles, offsets_in[0], offsets_in[1], V, T, origin, cell, cells, counts, offsets[0], offsets[1])
+        count = simplify_struct(*common, normals=normals, keep_duplicates=keep_duplicates)
+        size = C.c_size_t()
+        _lib.check(lib.pr_simplify_workspace_size(C.byref(count), C.byref(size)), "pr_simplify_workspace_size")
+        workspace = torch.empty(size.value, dtype=torch.uint8, device=dev)
+        _lib.check(lib.pr_simplify_mesh(C.byref(count), workspace.data_ptr(), size.value, stream), "pr_simplify_mesh")
+        out_vo, out_to = offsets.cpu().tolist()                             # (the host synchronisation)
+        out_v = torch.empty((out_vo[G], 3), dtype=torch.float32, device=dev)
+        out_n = None if normals is None else torch.empty((out_vo[G], 3), dtype=torch.float32, device=dev)
+        out_t = torch.empty((out_to[G], 3), dtype=torch.int32, device=dev)
+        if out_vo[G] > 0:
+            emit = simplify_struct(*common, normals=normals, out_vertices=out_v, out_normals=out_n,
+                                   out_triangles=out_t if out_to[G] > 0 else None, keep_duplicates=keep_duplicates)
+            _lib.check(lib.pr_simplify_mesh(C.byref(emit), workspace.data_ptr(), size.value, stream), "pr_simplify_mesh")
+    return [Mesh(out_v[out_vo[g]:out_vo[g + 1]], out_t[out_to[g]:out_to[g + 1]], None if out_n is None else out_n[out_vo[g]:out_vo[g + 1]])
+            for g in range(G)]
+
+
+def simplify_meshes(meshes: Sequence[Mesh], origin, cell, cells, *, keep_duplicates: bool = False) -> List[Mesh]:
+    """The meshes simplified by vertex clustering on one uniform grid (``pr_simplify_mesh``, include/playrender.h): the grid has
+    ``cells[a]`` cells of size ``cell[a]`` from ``origin[a]`` on along every axis (at most 2^21 cells); a vertex outside it goes to the
+    nearest border cell.  All vertices of a cell become one vertex at their mean (normals: the normalised sum), triangles that lose a
+    corner that way disappear, and of the triangles that end up with the same corners in the same orientation only the first stays
+    (``keep_duplicates=True``: all stay).  The result is fixed by the rule - integer sums, no dependence on the execution order.
+
+    The meshes are packed, counted, and - after reading the two offset arrays back, the ONE host synchronisation - emitted into
+    exactly sized tensors.  Returns one mesh per input; they have normals iff every input has them; ``features`` are not carried
+    over.  There is no CPU fallback."""
+    meshes = list(meshes)
+    if not meshes:
+        raise ValueError("simplify_meshes needs at least one mesh")
+    if not all(m.vertices.is_cuda and m.triangles.is_cuda for m in meshes):
+        raise RuntimeError(NO_CPU)
+    origin, cell, cells = _cluster_grid(origin, cell, cells)
+    dev = meshes[0].vertices.device
+    for m in meshes:
+        if m.vertices.dim() != 2 or m.vertices.size(1) != 3 or m.triangles.dim() != 2 or m.triangles.size(1) != 3:
+            raise ValueError(f"a mesh has vertices (V, 3) and triangles (T, 3), got {list(m.vertices.shape)} / {list(m.triangles.shape)}")
+    with_normals = all(m.normals is not None for m in meshes)
+    pack = lambda parts, dtype: torch.cat([p.detach().to(device=dev, dtype=dtype).reshape(-1, 3) for p in parts]).contiguous()
+    vertices = pack([m.vertices for m in meshes], torch.float32)
+    triangles = pack([m.triangles for m in meshes], torch.int32)
+    normals = pack([m.normals for m in meshes], torch.float32) if with_normals else None
+    if normals is not None and normals.size(0) != vertices.size(0):
+        raise ValueError("normals must have one row per vertex")
+    vertex_offsets, triangle_offsets = [0], [0]
+    for m in meshes:
+        vertex_offsets.append(vertex_offsets[-1] + m.vertices.size(0))
+        triangle_offsets.append(triangle_offsets[-1] + m.triangles.size(0))
+    return _simplify_packed(vertices, normals, triangles, vertex_offsets, triangle_offsets, origin, cell, cells, keep_duplicates)
+
+
 def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float, *, normals: bool = True, keep_largest: int = 0,
-                    min_points: int = 0, close_border: bool = False) -> List[Mesh]:
+                    min_points: int = 0, close_border: bool = False, simplify: int = 0) -> List[Mesh]:
     """Meshes of the level set ``sigma = level`` of ``sigma (G, nx, ny, nz)`` (device tensor, z fastest - what ``density_grid``
     returns); ``axes``: the coordinates of the lattice points along x, y, z (``nx``, ``ny``, ``nz`` values).  Returns G meshes.
 
@@ -271,13 +409,23 @@ def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: fl
 
     ``keep_largest`` / ``min_points`` / ``close_border``: with any of them set the lattice goes through ``clean_lattice`` (fill =
     ``level``) first - floaters are dropped, the surface is capped at the lattice border.  Positions and triangles of the kept
-    components do not change; normals near a removed component can, because the gradient stencil reads the blanked values."""
+    components do not change; normals near a removed component can, because the gradient stencil reads the blanked values.
+
+    ``simplify = k >= 1``: the meshes are then clustered (``simplify_meshes``) on the grid aligned with the lattice whose cells span
+    ``k`` lattice steps (``lattice_cluster_grid``) - evaluate the field finely, keep a mesh of a coarser lattice's size.  Two more
+    read-backs (the ends of the axes, the simplified sizes).  At 0 (the default) nothing changes."""
     if not sigma.is_cuda:
         raise RuntimeError(NO_CPU)
     if sigma.dim() != 4:
         raise ValueError(f"sigma must be (G, nx, ny, nz), got {list(sigma.shape)}")
     if len(axes) != 3:
         raise ValueError("axes must be the three coordinate vectors of the lattice")
+    try:
+        simplify = operator.index(simplify)
+    except TypeError:
+        raise ValueError(f"simplify must be an integer >= 0, got {simplify!r}") from None
+    if simplify < 0:
+        raise ValueError(f"simplify must be an integer >= 0, got {simplify}")
     dev = sigma.device
     sigma = sigma.detach().to(torch.float32).contiguous()
     if keep_largest or min_points or close_border:
@@ -304,6 +452,9 @@ def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: fl
         if V > 0:
             emit = surface_struct(sigma, axes, level, offsets[0], offsets[1], vertices, vertex_normals, triangles)
             _lib.check(lib.pr_extract_surface(C.byref(emit), workspace.data_ptr(), size.value, stream), "pr_extract_surface")
+    if simplify:
+        grid = _cluster_grid(*lattice_cluster_grid(axes, simplify))
+        return _simplify_packed(vertices, vertex_normals, triangles, vertex_offsets, triangle_offsets, *grid, False)
     meshes = []
     for g in range(G):
         v0, v1, t0, t1 = vertex_offsets[g], vertex_offsets[g + 1], triangle_offsets[g], triangle_offsets[g + 1]
