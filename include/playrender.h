@@ -686,6 +686,101 @@ int pr_simplify_workspace_size(const pr_simplify_t* s, size_t* bytes);
 int pr_simplify_mesh(const pr_simplify_t* s, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Closest-hit ray queries against packed meshes: pr_raycast_build sorts the triangles of G meshes into a uniform cell grid,
+ * pr_raycast_query casts N rays per group through it.  The result is DEFINED as that of the exhaustive search below; the grid may
+ * change the time and never the bits (inside the domain stated under "Guarantee").
+ *   Mesh input, read as pr_simplify_mesh reads it: vertices (V, 3) fp32, triangles (T, 3) int32 LOCAL to their group, vertex_offsets
+ *     (G + 1), triangle_offsets (G + 1), all on the device; total_vertices / total_triangles are V and T as host values; offsets that
+ *     leave [0, V] / [0, T] or decrease are clamped, never followed.  A triangle with an index outside [0, V_g) is never hit.
+ *   Rays: origins (G, N, 3) and directions (G, N, 3) fp32 in the meshes' frame, not normalised; t_min, t_max: two fp32 per call, not
+ *     NaN, +-inf allowed.
+ *   The test of one ray (o, d) against one triangle (a, b, c): fp32, no contraction, dot products as (x0 y0 + x1 y1) + x2 y2, cross
+ *     products componentwise ((x cross y)_0 = x1 y2 - x2 y1, cyclic):
+ *       e1 = b - a, e2 = c - a, p = d cross e2, det = e1 . p, s = o - a,
+ *       u = (s . p) / det, q = s cross e1, v = (d . q) / det, t = (e2 . q) / det.
+ *     Accepted iff det < 0 or det > 0 (with PR_RAYCAST_CULL_BACK: det > 0 - the ray enters matter; the mesher orients triangles from
+ *     matter to empty space), and u >= 0, v >= 0, u + v <= 1, t >= t_min, t <= t_max.  Every comparison is false on a NaN: a NaN or
+ *     zero direction, a NaN origin, or a triangle with a == b or a == c never hits.
+ *   Result per ray: among the accepted triangles of the ray's own group, the one with the smallest t, and among equal t (as numbers)
+ *     the one with the lowest index.  Outputs: t (G, N) fp32, +inf for a miss; triangle (G, N) int32 local to the group, -1 for a
+ *     miss, optional; barycentric (G, N, 2) = (u, v), zeros for a miss, optional (needs triangle).
+ *   NOT WATERTIGHT: a ray through a shared edge or vertex can be accepted by both neighbours (then the lower index wins) or by neither.
+ *   Grid: origin[3], cell[3] (finite, > 0), cells[3] (each 1 .. PR_RAYCAST_MAX_AXIS_CELLS = 1024, product <= PR_RAYCAST_MAX_CELLS =
+ *     2^21), shared by the groups.  Grid coordinate of x on axis k: (x_k - origin_k) / cell_k in fp32; cell (i0, i1, i2) is the cube
+ *     [i, i + 1] of grid coordinates and has the flat index (i0 cells[1] + i1) cells[2] + i2.
+ *   Lists: every group has C + 1 of them, C = cells[0] cells[1] cells[2]: one per cell and, last (list C), the LOOSE list, which
+ *     every ray of the group tests.  A triangle is
+ *       dead  (in no list) iff it has an index outside [0, V_g), or a == b or a == c as values (det is then exactly zero);
+ *       tight iff n = e1 cross e2 has n . n > 2^-20 ((e1 . e1) (e2 . e2)) and on every axis its three grid coordinates are finite
+ *             and low = min - 1/16 >= 0, high = max + 1/16 <= cells_k; it is then in the list of every cell with
+ *             (int)low <= i_k <= min((int)high, cells_k - 1) on all three axes - the box padded by a sixteenth of a cell;
+ *       loose otherwise (a vertex that is not finite, a sliver, a padded box that is not inside the grid's box).
+ *     A triangle may overlap any number of cells, at the price of a serial loop in its lane.
+ *   Build outputs, caller-owned: cell_offsets (G (C + 1) + 1) int32, always written - list l of group g owns references
+ *     [cell_offsets[g (C + 1) + l], cell_offsets[g (C + 1) + l + 1]), and the last element is R, the number of references;
+ *     references (max_references) int32 or NULL: triangle indices local to the group.  The order inside a list is the order of arrival
+ *     and differs from run to run; the query's result does not, because it takes a minimum.  R is only known on the device: a call
+ *     with references == NULL only counts, one read-back of cell_offsets[G (C + 1)] follows, then an exactly sized emitting call.
+ *     Nothing at or beyond max_references is written.  R must stay below 2^31.  A built grid serves any number of queries.
+ *   Query: one lane per ray.  A ray with a component that is not finite or with d = 0 is a miss.  Otherwise the lane tests the loose
+ *     list, clips [t_min, t_max] to the grid's box in grid coordinates (og = (o - origin) / cell, dg = d / cell; an axis with
+ *     dg = 0 only checks 0 <= og <= cells), starts in the cell of og + t dg at the clipped start, and walks: the exit time of the
+ *     current cell is the smallest (plane - og_k) / dg_k over the axes with dg_k != 0, plane = i_k + 1 for dg_k > 0 and i_k otherwise;
+ *     it tests the cell's list, stops if the best t so far is <= the exit time or the exit time is >= the clipped end, and otherwise
+ *     steps along that axis, stopping when it leaves the grid.  At most cells[0] + cells[1] + cells[2] steps; no lane waits for another.
+ *     References outside [0, max_references) or [0, T_g) are skipped: a stale or foreign grid costs correctness, never memory safety.
+ *   Guarantee (argument: DESIGN.md 21.2): the outputs equal the exhaustive search bit for bit if (1) the ray's origin lies within
+ *     2^12 cells of the grid's origin on every axis and the clip times are finite, and (2) every test of a TIGHT triangle that the
+ *     exhaustive search accepts is well conditioned: with L = max(|o - a|, |e1|, |e2|) and rho = |det| / (|e1| |e2| |d|) (Euclidean),
+ *     rho >= 2^-16 and L / rho <= 2^12 min(cell).  Loose triangles need no condition.  Outside this domain the call is memory-safe and
+ *     terminates, and a hit it reports is a hit of the rule - but a closer one may have been missed.
+ * pr_raycast_workspace_size / pr_raycast_build workspace bytes = the sum of these regions, each rounded up to 256 bytes, with
+ *   NB = floor(G (C + 1) / 256) + 1: 4 G (C + 1) (list counts, then cursors) + 3 x 4 (G + 1) (per group: first vertex, first triangle,
+ *   first triangle block) + 2 x 4 NB (block sums of the counts and their scan) + 4 (the total).  The query needs no workspace.
+ * Kernels only on `stream` (six for a counting build, seven for an emitting one, one for a query): no memset, no memcpy, no allocation,
+ * no synchronisation - build and query are each capturable into a HIP graph.  Integer atomics only.
+ * Refused (PR_ERR_INVALID, before any device work, by all three entry points): NULL vertices, triangles, offsets or cell_offsets,
+ * groups < 1, a cells entry outside 1 .. 1024 or a product above 2^21, a cell size that is not finite or not > 0, a non-finite origin,
+ * unknown flag bits, a negative total, capacity or ray count, a NaN t_min or t_max, totals at which an int32 count overflows
+ * (T + 256 G, G (C + 1) + 256 or G (N + 256) at or above 2^31); by the build a NULL, misaligned or too small workspace; by the query a
+ * NULL t, barycentric without triangle, NULL origins or directions, NULL references with max_references > 0.  rays == 0 and
+ * total_triangles == 0 are valid: nothing is launched, or every ray misses.
+ */
+#define PR_RAYCAST_CULL_BACK 1u
+#define PR_RAYCAST_MAX_AXIS_CELLS 1024
+#define PR_RAYCAST_MAX_CELLS 2097152
+typedef struct pr_raycast_t {
+    int32_t groups;                       /* G >= 1 */
+    int32_t total_vertices;               /* V = vertex_offsets[G], as a host value, >= 0 */
+    int32_t total_triangles;              /* T = triangle_offsets[G], as a host value, >= 0 */
+    uint32_t flags;                       /* PR_RAYCAST_CULL_BACK or 0 (read by the query) */
+    float origin[3];                      /* finite */
+    float cell[3];                        /* finite, > 0 */
+    int32_t cells[3];                     /* each 1 .. PR_RAYCAST_MAX_AXIS_CELLS, product <= PR_RAYCAST_MAX_CELLS */
+    int32_t max_references;               /* rows of references, >= 0 */
+    int32_t rays;                         /* N per group, >= 0 (query) */
+    float t_min;                          /* not NaN (query) */
+    float t_max;                          /* not NaN (query) */
+    uint32_t reserved_;
+    const float* vertices;                /* (V, 3) */
+    const int32_t* triangles;             /* (T, 3), indices local to the group */
+    const int32_t* vertex_offsets;        /* (G + 1) */
+    const int32_t* triangle_offsets;      /* (G + 1) */
+    int32_t* cell_offsets;                /* (G (C + 1) + 1): written by the build, read by the query */
+    int32_t* references;                  /* (max_references): written by the build (NULL: count only), read by the query */
+    const float* origins;                 /* query: (G, N, 3) */
+    const float* directions;              /* query: (G, N, 3) */
+    float* t;                             /* query: (G, N), always written */
+    int32_t* triangle;                    /* query: (G, N) or NULL */
+    float* barycentric;                   /* query: (G, N, 2) or NULL; needs triangle */
+} pr_raycast_t;
+/* Host computation, no device work; refuses everything above that does not concern the workspace. */
+int pr_raycast_workspace_size(const pr_raycast_t* s, size_t* bytes);
+/* `workspace`: 256-byte aligned, pr_raycast_workspace_size bytes. */
+int pr_raycast_build(const pr_raycast_t* s, void* workspace, size_t workspace_bytes, void* stream);
+int pr_raycast_query(const pr_raycast_t* s, void* stream);
+
+/*
  * Backward pass of pr_render_forward (what torch.autograd does for the reference's op graph when
  * training/trainer_backpropagated_autoencoder.py:349 calls total_loss.backward()).  The forward call must
  * have run with PR_FLAG_SAVE_FOR_BACKWARD (with or without PR_FLAG_TRAIN_BN) on the same `call`, `objects` and

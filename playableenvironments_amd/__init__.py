@@ -14,7 +14,8 @@ Public surface (mirrors the reference's modules for the renderer hot path only):
                             ObjectComposer.extract_mesh), with floater removal and capping on the same lattice
                             (surface.label_components, surface.clean_lattice); surface.refine_band / ObjectComposer.density_band
                             evaluate a lattice only in a band around the level set; surface.simplify_meshes reduces
-                            extracted meshes by vertex clustering (extract_mesh(simplify=k))
+                            extracted meshes by vertex clustering (extract_mesh(simplify=k)); surface.RayGrid casts rays
+                            against them (closest hits on a cell grid)
   ray_sampling, wire_format pixel / ray samplers and the renderer <-> decoder tensor glue of the reference
   parallel                  frame shards, overlapped feature all-gather, gradient all-reduce (torch.distributed / RCCL)
   configs / synthetic       shipped renderer configurations and seeded synthetic scenes
@@ -23,8 +24,8 @@ from . import batching, configs, encoders, geometry, parallel, ray_sampling, sur
 from .environment_model import EnvironmentModel  # noqa: F401
 from .frame_graph import FrameGraph  # noqa: F401
 from .object_composer import ObjectComposer, ObjectIDsHelper  # noqa: F401
-from .surface import Mesh, clean_lattice, label_components, simplify_meshes  # noqa: F401
+from .surface import Mesh, RayGrid, clean_lattice, label_components, simplify_meshes  # noqa: F401
 
 __all__ = ["ObjectComposer", "ObjectIDsHelper", "EnvironmentModel", "FrameGraph", "configs", "synthetic", "parallel",
            "ray_sampling", "wire_format", "encoders", "batching", "geometry", "surface", "Mesh", "label_components",
-           "clean_lattice", "simplify_meshes"]
+           "clean_lattice", "simplify_meshes", "RayGrid"]

@@ -235,6 +235,21 @@ class Simplify(C.Structure):
                 ("out_vertex_offsets", C.c_void_p), ("out_triangle_offsets", C.c_void_p)]
 
 
+RAYCAST_CULL_BACK = 1            # PR_RAYCAST_CULL_BACK
+RAYCAST_MAX_AXIS_CELLS = 1024    # PR_RAYCAST_MAX_AXIS_CELLS
+RAYCAST_MAX_CELLS = 1 << 21      # PR_RAYCAST_MAX_CELLS
+
+
+class Raycast(C.Structure):
+    """pr_raycast_t (include/playrender.h)."""
+    _fields_ = [("groups", C.c_int32), ("total_vertices", C.c_int32), ("total_triangles", C.c_int32), ("flags", C.c_uint32),
+                ("origin", C.c_float * 3), ("cell", C.c_float * 3), ("cells", C.c_int32 * 3), ("max_references", C.c_int32),
+                ("rays", C.c_int32), ("t_min", C.c_float), ("t_max", C.c_float), ("reserved_", C.c_uint32), ("vertices", C.c_void_p),
+                ("triangles", C.c_void_p), ("vertex_offsets", C.c_void_p), ("triangle_offsets", C.c_void_p), ("cell_offsets", C.c_void_p),
+                ("references", C.c_void_p), ("origins", C.c_void_p), ("directions", C.c_void_p), ("t", C.c_void_p),
+                ("triangle", C.c_void_p), ("barycentric", C.c_void_p)]
+
+
 # every exported symbol of include/playrender.h : (restype, argtypes)
 class SceneSetup(C.Structure):
     """pr_scene_setup_t (include/playrender.h)."""
@@ -278,6 +293,9 @@ SYMBOLS = {
     "pr_band_fill": (C.c_int, [C.POINTER(Band), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_simplify_workspace_size": (C.c_int, [C.POINTER(Simplify), C.POINTER(C.c_size_t)]),
     "pr_simplify_mesh": (C.c_int, [C.POINTER(Simplify), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pr_raycast_workspace_size": (C.c_int, [C.POINTER(Raycast), C.POINTER(C.c_size_t)]),
+    "pr_raycast_build": (C.c_int, [C.POINTER(Raycast), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pr_raycast_query": (C.c_int, [C.POINTER(Raycast), C.c_void_p]),
     "pr_backward_workspace_size": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(C.c_size_t)]),
     "pr_render_backward": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(OutputGrads), C.POINTER(OutputGrads),
                                      C.POINTER(InputGrads), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),

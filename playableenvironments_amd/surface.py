@@ -16,6 +16,9 @@ around the level set - the opt-in approximation behind ``ObjectComposer.density_
 
 ``simplify_meshes`` / ``Mesh.simplified`` (``pr_simplify_mesh``) reduce extracted meshes by vertex clustering on a uniform grid, on
 the device and independent of the execution order - what ``extract_surface(simplify=k)`` and ``extract_mesh(simplify=k)`` apply.
+
+``RayGrid`` / ``Mesh.ray_grid`` (``pr_raycast_build`` / ``pr_raycast_query``) answer closest-hit ray queries against such meshes on a
+uniform cell grid: ``RayGrid.build(meshes, *bounding_grid(meshes, 32)).cast(origins, directions)``.
 """
 from __future__ import annotations
 
@@ -66,6 +69,10 @@ class Mesh:
     def simplified(self, origin, cell, cells, **kw) -> "Mesh":
         """The mesh clustered on the grid ``origin`` / ``cell`` / ``cells``: ``simplify_meshes`` of this one mesh."""
         return simplify_meshes([self], origin, cell, cells, **kw)[0]
+
+    def ray_grid(self, origin, cell, cells) -> "RayGrid":
+        """This one mesh sorted into the grid ``origin`` / ``cell`` / ``cells`` for ray queries: ``RayGrid.build([self], ...)``."""
+        return RayGrid.build([self], origin, cell, cells)
 
 
 def surface_struct(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float, vertex_offsets: torch.Tensor,
@@ -397,6 +404,186 @@ def simplify_meshes(meshes: Sequence[Mesh], origin, cell, cells, *, keep_duplica
         vertex_offsets.append(vertex_offsets[-1] + m.vertices.size(0))
         triangle_offsets.append(triangle_offsets[-1] + m.triangles.size(0))
     return _simplify_packed(vertices, normals, triangles, vertex_offsets, triangle_offsets, origin, cell, cells, keep_duplicates)
+
+
+def raycast_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offsets: torch.Tensor, triangle_offsets: torch.Tensor,
+                   total_vertices: int, total_triangles: int, origin, cell, cells, cell_offsets: torch.Tensor, *,
+                   references: Optional[torch.Tensor] = None, origins: Optional[torch.Tensor] = None,
+                   directions: Optional[torch.Tensor] = None, t: Optional[torch.Tensor] = None, triangle: Optional[torch.Tensor] = None,
+                   barycentric: Optional[torch.Tensor] = None, t_min: float = 0.0, t_max: float = math.inf,
+                   cull_back: bool = False) -> _lib.Raycast:
+    """``pr_raycast_t`` over prepared tensors (fp32 / int32, contiguous, one device); ``max_references`` is the rows of ``references``,
+    ``rays`` the second dimension of ``origins (G, N, 3)``."""
+    s = _lib.Raycast()
+    s.groups = vertex_offsets.numel() - 1
+    s.total_vertices = int(total_vertices)
+    s.total_triangles = int(total_triangles)
+    s.flags = _lib.RAYCAST_CULL_BACK if cull_back else 0
+    for a in range(3):
+        s.origin[a] = float(origin[a])
+        s.cell[a] = float(cell[a])
+        s.cells[a] = int(cells[a])
+    s.max_references = 0 if references is None else references.size(0)
+    s.rays = 0 if origins is None else origins.size(1)
+    s.t_min = float(t_min)
+    s.t_max = float(t_max)
+    for name, x in (("vertices", vertices), ("triangles", triangles), ("vertex_offsets", vertex_offsets),
+                    ("triangle_offsets", triangle_offsets), ("cell_offsets", cell_offsets), ("references", references),
+                    ("origins", origins), ("directions", directions), ("t", t), ("triangle", triangle), ("barycentric", barycentric)):
+        setattr(s, name, None if x is None else x.data_ptr())
+    return s
+
+
+def _ray_grid(origin, cell, cells):
+    """The host values of a ray grid, checked as ``pr_raycast_build`` checks them."""
+    origin, cell, cells = _cluster_grid(origin, cell, cells)
+    if not all(n <= _lib.RAYCAST_MAX_AXIS_CELLS for n in cells):
+        raise ValueError(f"a ray grid has at most {_lib.RAYCAST_MAX_AXIS_CELLS} cells per axis, got {cells}")
+    return origin, cell, cells
+
+
+@dataclass
+class RayHits:
+    """What ``RayGrid.cast`` returns: ``t (G, N)`` (``+inf``: a miss), ``triangle (G, N)`` int32 local to the group (-1: a miss),
+    ``barycentric (G, N, 2)`` = ``(u, v)`` of the hit (the point is ``a + u (b - a) + v (c - a)``) or None; with ``nearest=True``
+    also ``nearest_t (N)`` and ``group (N)`` int64: the closest hit over the groups and the group it belongs to (-1: none hits)."""
+    t: torch.Tensor
+    triangle: torch.Tensor
+    barycentric: Optional[torch.Tensor] = None
+    nearest_t: Optional[torch.Tensor] = None
+    group: Optional[torch.Tensor] = None
+
+
+class RayGrid:
+    """G meshes sorted into a uniform cell grid for closest-hit ray queries (``pr_raycast_build`` / ``pr_raycast_query``,
+    include/playrender.h).  ``RayGrid.build`` makes one; it holds the packed meshes, the per-cell lists and nothing else, and serves
+    any number of ``cast`` calls.  The results are those of the exhaustive search over all triangles, bit for bit (the header states the
+    domain of that guarantee).  There is no CPU fallback."""
+
+    def __init__(self, vertices, triangles, vertex_offsets, triangle_offsets, totals, grid, cell_offsets, references):
+        self.vertices, self.triangles = vertices, triangles
+        self.vertex_offsets, self.triangle_offsets = vertex_offsets, triangle_offsets
+        self.total_vertices, self.total_triangles = totals
+        self.origin, self.cell, self.cells = grid
+        self.cell_offsets, self.references = cell_offsets, references
+
+    @property
+    def groups(self) -> int:
+        return self.vertex_offsets.numel() - 1
+
+    @classmethod
+    def build(cls, meshes: Sequence[Mesh], origin, cell, cells) -> "RayGrid":
+        """Packs the meshes as ``simplify_meshes`` does and sorts their triangles into the grid of ``cells[a]`` cells of size ``cell[a]``
+        from ``origin[a]`` on (at most 1024 per axis, 2^21 in all; ``bounding_grid`` and ``lattice_cluster_grid`` supply one): a
+        counting call, one read-back of the number of references - the ONE host synchronisation - and an exactly sized emitting call.
+        A triangle that is not inside the grid's box is tested by every ray: a grid around the meshes is the fast one."""
+        meshes = list(meshes)
+        if not meshes:
+            raise ValueError("RayGrid.build needs at least one mesh")
+        if not all(m.vertices.is_cuda and m.triangles.is_cuda for m in meshes):
+            raise RuntimeError(NO_CPU)
+        grid = _ray_grid(origin, cell, cells)
+        dev = meshes[0].vertices.device
+        for m in meshes:
+            if m.vertices.dim() != 2 or m.vertices.size(1) != 3 or m.triangles.dim() != 2 or m.triangles.size(1) != 3:
+                raise ValueError(f"a mesh has vertices (V, 3) and triangles (T, 3), got {list(m.vertices.shape)} / {list(m.triangles.shape)}")
+        pack = lambda parts, dtype: torch.cat([p.detach().to(device=dev, dtype=dtype).reshape(-1, 3) for p in parts]).contiguous()
+        vertices = pack([m.vertices for m in meshes], torch.float32)
+        triangles = pack([m.triangles for m in meshes], torch.int32)
+        vo, to = [0], [0]
+        for m in meshes:
+            vo.append(vo[-1] + m.vertices.size(0))
+            to.append(to[-1] + m.triangles.size(0))
+        if vertices.size(0) == 0:                                      # (an empty tensor has no address: the library refuses NULL)
+            vertices = torch.empty((1, 3), dtype=torch.float32, device=dev)
+        if triangles.size(0) == 0:
+            triangles = torch.empty((1, 3), dtype=torch.int32, device=dev)
+        G = len(meshes)
+        lists = G * (grid[2][0] * grid[2][1] * grid[2][2] + 1)
+        lib = _lib.load()
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            offsets = torch.tensor([vo, to], dtype=torch.int32).to(dev)
+            cell_offsets = torch.empty(lists + 1, dtype=torch.int32, device=dev)
+            common = (vertices, triangles, offsets[0], offsets[1], vo[-1], to[-1], *grid, cell_offsets)
+            count = raycast_struct(*common)
+            size = C.c_size_t()
+            _lib.check(lib.pr_raycast_workspace_size(C.byref(count), C.byref(size)), "pr_raycast_workspace_size")
+            workspace = torch.empty(size.value, dtype=torch.uint8, device=dev)
+            _lib.check(lib.pr_raycast_build(C.byref(count), workspace.data_ptr(), size.value, stream), "pr_raycast_build")
+            R = int(cell_offsets[lists].item())                                 # (the host synchronisation)
+            if R < 0:
+                raise RuntimeError("the grid holds 2^31 or more references: use a coarser grid")
+            references = torch.empty(R, dtype=torch.int32, device=dev)
+            if R > 0:
+                emit = raycast_struct(*common, references=references)
+                _lib.check(lib.pr_raycast_build(C.byref(emit), workspace.data_ptr(), size.value, stream), "pr_raycast_build")
+        return cls(vertices, triangles, offsets[0], offsets[1], (vo[-1], to[-1]), grid, cell_offsets, references)
+
+    def cast(self, origins: torch.Tensor, directions: torch.Tensor, *, t_min: float = 0.0, t_max: float = math.inf,
+             cull_back: bool = False, barycentric: bool = False, nearest: bool = False) -> RayHits:
+        """The closest hit of every ray ``o + t d``, ``t_min <= t <= t_max``, with the meshes: ``origins`` / ``directions`` are
+        ``(G, N, 3)`` - group g's rays meet group g's mesh - or ``(N, 3)``, used for every group; in the meshes' frame, not normalised.
+        ``cull_back``: only triangles the ray meets from their front (it enters matter) count.  ``nearest``: also the closest hit over
+        the groups - the cross-object front surface, as ``front_object`` is for renders.  One kernel on the current stream, no host
+        synchronisation."""
+        if not (origins.is_cuda and directions.is_cuda):
+            raise RuntimeError(NO_CPU)
+        if math.isnan(float(t_min)) or math.isnan(float(t_max)):
+            raise ValueError(f"t_min and t_max must not be NaN, got {t_min}, {t_max}")
+        G, dev = self.groups, self.vertices.device
+        if origins.shape != directions.shape or origins.dim() not in (2, 3) or origins.size(-1) != 3:
+            raise ValueError(f"origins and directions must both be (G, N, 3) or (N, 3), got {list(origins.shape)} / {list(directions.shape)}")
+        if origins.dim() == 3 and origins.size(0) != G:
+            raise ValueError(f"the grid holds {G} groups, the rays are {list(origins.shape)}")
+        prepare = lambda x: (x if x.dim() == 3 else x.unsqueeze(0).expand(G, -1, -1)).detach().to(device=dev, dtype=torch.float32).contiguous()
+        origins, directions = prepare(origins), prepare(directions)
+        N = origins.size(1)
+        hits = RayHits(torch.empty((G, N), dtype=torch.float32, device=dev), torch.empty((G, N), dtype=torch.int32, device=dev),
+                       torch.empty((G, N, 2), dtype=torch.float32, device=dev) if barycentric else None)
+        if N > 0:
+            with torch.cuda.device(dev):
+                s = raycast_struct(self.vertices, self.triangles, self.vertex_offsets, self.triangle_offsets, self.total_vertices,
+                                   self.total_triangles, self.origin, self.cell, self.cells, self.cell_offsets,
+                                   references=self.references if self.references.numel() else None, origins=origins, directions=directions,
+                                   t=hits.t, triangle=hits.triangle, barycentric=hits.barycentric, t_min=t_min, t_max=t_max,
+                                   cull_back=cull_back)
+                _lib.check(_lib.load().pr_raycast_query(C.byref(s), torch.cuda.current_stream(dev).cuda_stream), "pr_raycast_query")
+        if nearest:
+            hits.nearest_t, group = torch.min(hits.t, dim=0)
+            hit = hits.triangle.gather(0, group.unsqueeze(0)).squeeze(0) >= 0
+            hits.group = torch.where(hit, group, torch.full_like(group, -1))
+        return hits
+
+
+def bounding_grid(meshes: Sequence[Mesh], cells):
+    """A grid of ``cells`` cells (one integer, or three) around the joint bounding box of the meshes' finite vertices, for
+    ``RayGrid.build``: per axis ``cell = extent / (cells - 1/4)`` and ``origin = lowest - cell / 8`` - the box is widened by an eighth
+    of a cell on every side, so that no vertex lies on its faces and no triangle's padded box (a sixteenth of a cell) leaves it.  An
+    axis without extent gets the extent ``2^-10 max(1, |lowest|)``.  Reads the box back: one host synchronisation."""
+    meshes = list(meshes)
+    try:
+        cells = [operator.index(cells)] * 3
+    except TypeError:
+        cells = [operator.index(n) for n in cells]
+    if not all(m.vertices.is_cuda for m in meshes):
+        raise RuntimeError(NO_CPU)
+    rows = [m.vertices.detach().to(torch.float32).reshape(-1, 3) for m in meshes if m.vertices.numel()]
+    if not rows:
+        raise ValueError("bounding_grid needs at least one vertex")
+    v = torch.cat(rows)
+    finite = torch.isfinite(v)
+    box = torch.stack([torch.where(finite, v, torch.full_like(v, math.inf)).amin(0),
+                       torch.where(finite, v, torch.full_like(v, -math.inf)).amax(0)]).cpu().tolist()      # (the host synchronisation)
+    origin, cell = [], []
+    for a in range(3):
+        lowest, highest = box[0][a], box[1][a]
+        if not lowest <= highest:
+            raise ValueError("bounding_grid needs a finite vertex on every axis")
+        extent = max(highest - lowest, 2.0 ** -10 * max(1.0, abs(lowest)))
+        cell.append(extent / (cells[a] - 0.25))
+        origin.append(lowest - cell[a] / 8)
+    return _ray_grid(origin, cell, cells)
 
 
 def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float, *, normals: bool = True, keep_largest: int = 0,
