@@ -781,6 +781,93 @@ int pr_raycast_build(const pr_raycast_t* s, void* workspace, size_t workspace_by
 int pr_raycast_query(const pr_raycast_t* s, void* stream);
 
 /*
+ * Closest-point queries against packed meshes on the grid of pr_raycast_build: pr_closest_query finds, for N points per group, the
+ * closest point of the group's mesh within max_distance.  It reads the mesh, the grid and the lists (cell_offsets, references) that a
+ * finished EMITTING pr_raycast_build left with the caller, and builds nothing of its own.  The result is DEFINED as that of the
+ * exhaustive search below; the grid may change the time and never the bits (inside the domain stated under "Guarantee").
+ *   Mesh and grid input: as pr_raycast_t (same fields, same clamping of offsets, same grid coordinates and lists).
+ *   Points: points (G, N, 3) fp32 in the meshes' frame, N = count; max_distance: one fp32 per call, not NaN, >= 0, +inf allowed.
+ *   Candidates of a point of group g: the triangles of group g that pr_raycast_build does not classify as dead.  DEAD triangles - an
+ *     index outside [0, V_g), or a == b or a == c as values - are in no list and are no candidates here either (they are segments or
+ *     points; where the mesher emits them its neighbouring triangles cover their edges).
+ *   The closest point q of one triangle (a, b, c) to p is Ericson's region walk: fp32, no contraction, every operation rounded on its
+ *     own, dot products as (x0 y0 + x1 y1) + x2 y2:
+ *       ab = b - a, ac = c - a, bc = c - b, ap = p - a, bp = p - b, cp = p - c,
+ *       d1 = ab . ap, d2 = ac . ap, d3 = ab . bp, d4 = ac . bp, d5 = ab . cp, d6 = ac . cp,
+ *       vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4.
+ *     The first condition that holds, in this order, decides (every comparison is false on a NaN, which ends in the last line):
+ *       vertex a   d1 <= 0 and d2 <= 0                            (v, w) = (0, 0)                       q = a (copied)
+ *       vertex b   d3 >= 0 and d4 <= d3                           (v, w) = (1, 0)                       q = b (copied)
+ *       edge ab    vc <= 0 and d1 >= 0 and d3 <= 0                v = d1 / (d1 - d3), w = 0             q = a + v ab
+ *       vertex c   d6 >= 0 and d5 <= d6                           (v, w) = (0, 1)                       q = c (copied)
+ *       edge ac    vb <= 0 and d2 >= 0 and d6 <= 0                v = 0, w = d2 / (d2 - d6)             q = a + w ac
+ *       edge bc    va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0      w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), v = 1 - w
+ *                                                                                                       q = b + w bc
+ *       interior   otherwise                                      v = vb / ((va + vb) + vc), w = vc / ((va + vb) + vc), then clamped:
+ *                                                                 v = 0 unless v >= 0, v = 1 if v > 1, w = 0 unless w >= 0,
+ *                                                                 w = 1 - v if w > 1 - v              q = (a + v ab) + w ac
+ *     componentwise, each product and sum rounded.  In every line 0 <= v, w and v + w <= 1 up to one rounding: q is a point of the
+ *     triangle whatever region the rounded conditions chose (a wrong region costs optimality, never membership).
+ *     r = p - q, dist2 = r . r.  Accepted iff dist2 <= max_distance * max_distance (one fp32 product) and dist2 < +inf.  A point with a component that is not finite is accepted by nothing (r is then infinite or
+ *     NaN): it is a miss, and nothing is tested for it.
+ *   Result per point: among the accepted candidates of the point's own group, the one with the smallest dist2, and among equal dist2
+ *     (as numbers) the one with the lowest index - a point whose closest feature is a shared vertex gets bit-equal dist2 from every
+ *     triangle around it, because q is a copy.  Outputs: distance (G, N) fp32 = sqrt(dist2) correctly rounded, +inf for a miss, always
+ *     written; triangle (G, N) int32 local to the group, -1 for a miss, optional; point (G, N, 3) = q, zeros for a miss, optional
+ *     (needs triangle); barycentric (G, N, 2) = (v, w), with q = a + v (b - a) + w (c - a) up to rounding, zeros for a miss, optional
+ *     (needs triangle).
+ *   Query: one lane per point.  The lane tests the group's loose list.  If the group has a reference outside its loose list, it takes
+ *     the start cell s_k = the integer part of (p_k - origin_k) / cell_k (fp32), clamped into [0, cells_k - 1], and visits the grid's
+ *     cells shell by shell: shell r = 0, 1, ... holds the cells inside the grid at Chebyshev index distance exactly r from s.  It tests
+ *     the list of every cell of the shell and then stops if, with reach2 = (r cmin) (r cmin) in fp32 (r as fp32, cmin = the smallest
+ *     cell[k]; two products),
+ *       a candidate was accepted and the best dist2 <= reach2,  or  reach2 > max_distance * max_distance,  or
+ *       r = max_k max(s_k, cells_k - 1 - s_k) (no shell is left).
+ *     References outside [0, max_references) or [0, T_g), triangle indices outside [0, V_g) and dead triangles are skipped where they
+ *     are read: a stale or foreign grid costs correctness, never memory safety.  A triangle listed in several cells is tested several
+ *     times; a minimum is idempotent.  A wave runs as long as its slowest point.  With max_distance = +inf a point far from the mesh
+ *     visits every shell up to its distance - (2 r + 1)^3 cells; give a finite radius where one is known.
+ *   Guarantee (argument: DESIGN.md 22.2): the outputs equal the exhaustive search bit for bit if every coordinate of the point, of
+ *     the grid's origin and of the grid's far corner origin + cells cell is at most 2^12 cmin in magnitude (so the point lies within
+ *     2^13 cells of the grid's origin, and one fp32 ulp of any coordinate that occurs is at most 2^-11 of a cell), and cmin >= 2^-40
+ *     (no squared distance of interest underflows).  There is no conditioning requirement: slivers are loose.  Outside this
+ *     domain the call is memory-safe and terminates (the shell loop has the bound above), and a result it reports is an accepted
+ *     candidate of the rule - but a closer one may have been missed.
+ * One kernel on `stream`, no workspace: no memset, no memcpy, no allocation, no synchronisation, no atomics - capturable as a one-node
+ * HIP graph.  sizeof(pr_closest_t) = 152.
+ * Refused (PR_ERR_INVALID, before any device work): everything pr_raycast_query refuses about mesh, grid and capacities (NULL
+ * vertices, triangles, offsets or cell_offsets, groups < 1, a cells entry outside 1 .. 1024 or a product above 2^21, a cell size that
+ * is not finite or not > 0, a non-finite origin, a negative total, capacity or count, NULL references with max_references > 0, T + 256 G
+ * or G (C + 1) + 256 at or above 2^31), a NULL distance or points, point or barycentric without triangle, a NaN or negative
+ * max_distance, flags other than 0, G (N + 256) at or above 2^31.  count == 0 launches nothing; total_triangles == 0 makes every
+ * point a miss.
+ */
+typedef struct pr_closest_t {
+    int32_t groups;                       /* G >= 1 */
+    int32_t total_vertices;               /* V = vertex_offsets[G], as a host value, >= 0 */
+    int32_t total_triangles;              /* T = triangle_offsets[G], as a host value, >= 0 */
+    uint32_t flags;                       /* no flag is defined: 0 */
+    float origin[3];                      /* the grid of the build: finite */
+    float cell[3];                        /* finite, > 0 */
+    int32_t cells[3];                     /* each 1 .. PR_RAYCAST_MAX_AXIS_CELLS, product <= PR_RAYCAST_MAX_CELLS */
+    int32_t max_references;               /* rows of references, >= 0 */
+    int32_t count;                        /* N per group, >= 0 */
+    float max_distance;                   /* not NaN, >= 0, +inf allowed */
+    const float* vertices;                /* (V, 3) */
+    const int32_t* triangles;             /* (T, 3), indices local to the group */
+    const int32_t* vertex_offsets;        /* (G + 1) */
+    const int32_t* triangle_offsets;      /* (G + 1) */
+    const int32_t* cell_offsets;          /* (G (C + 1) + 1), as pr_raycast_build wrote them */
+    const int32_t* references;            /* (max_references), as an emitting pr_raycast_build wrote them (NULL: max_references 0) */
+    const float* points;                  /* (G, N, 3) */
+    float* distance;                      /* (G, N), always written */
+    int32_t* triangle;                    /* (G, N) or NULL */
+    float* point;                         /* (G, N, 3) or NULL; needs triangle */
+    float* barycentric;                   /* (G, N, 2) or NULL; needs triangle */
+} pr_closest_t;
+int pr_closest_query(const pr_closest_t* s, void* stream);
+
+/*
  * Backward pass of pr_render_forward (what torch.autograd does for the reference's op graph when
  * training/trainer_backpropagated_autoencoder.py:349 calls total_loss.backward()).  The forward call must
  * have run with PR_FLAG_SAVE_FOR_BACKWARD (with or without PR_FLAG_TRAIN_BN) on the same `call`, `objects` and

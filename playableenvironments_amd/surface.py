@@ -18,7 +18,9 @@ around the level set - the opt-in approximation behind ``ObjectComposer.density_
 the device and independent of the execution order - what ``extract_surface(simplify=k)`` and ``extract_mesh(simplify=k)`` apply.
 
 ``RayGrid`` / ``Mesh.ray_grid`` (``pr_raycast_build`` / ``pr_raycast_query``) answer closest-hit ray queries against such meshes on a
-uniform cell grid: ``RayGrid.build(meshes, *bounding_grid(meshes, 32)).cast(origins, directions)``.
+uniform cell grid: ``RayGrid.build(meshes, *bounding_grid(meshes, 32)).cast(origins, directions)``.  ``RayGrid.closest``
+(``pr_closest_query``) finds the closest point of a mesh to a point on the same grid, and ``Mesh.distance_to`` measures how far one mesh
+lies from another with it.
 """
 from __future__ import annotations
 
@@ -73,6 +75,16 @@ class Mesh:
     def ray_grid(self, origin, cell, cells) -> "RayGrid":
         """This one mesh sorted into the grid ``origin`` / ``cell`` / ``cells`` for ray queries: ``RayGrid.build([self], ...)``."""
         return RayGrid.build([self], origin, cell, cells)
+
+    def distance_to(self, other, *, max_distance: float, cells=32) -> torch.Tensor:
+        """The distance ``(V)`` of every vertex of this mesh from ``other`` - a ``RayGrid`` of one group, or a ``Mesh``, which is
+        sorted into ``bounding_grid([other], cells)`` first - within ``max_distance`` (``+inf`` beyond it): the one-sided deviation of
+        this mesh from the other, e.g. of a simplified mesh from the one it came from (``RayGrid.closest``)."""
+        if isinstance(other, Mesh):
+            other = RayGrid.build([other], *bounding_grid([other], cells))
+        if other.groups != 1:
+            raise ValueError(f"distance_to needs a grid of one group, got {other.groups}")
+        return other.closest(self.vertices, max_distance=max_distance).distance[0]
 
 
 def surface_struct(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float, vertex_offsets: torch.Tensor,
@@ -554,6 +566,84 @@ class RayGrid:
             hit = hits.triangle.gather(0, group.unsqueeze(0)).squeeze(0) >= 0
             hits.group = torch.where(hit, group, torch.full_like(group, -1))
         return hits
+
+    def closest(self, points: torch.Tensor, *, max_distance: float, point: bool = False, barycentric: bool = False,
+                nearest: bool = False) -> "ClosestPoints":
+        """The closest point of the meshes to every point, within ``max_distance``: ``points`` is ``(G, N, 3)`` - group g's points
+        meet group g's mesh - or ``(N, 3)``, used for every group; in the meshes' frame.  ``max_distance`` has no default: the caller
+        decides how far is too far to matter.  ``math.inf`` is allowed, but a point r cells from the mesh then visits the
+        ``(2 r + 1)^3`` cells around it before it may stop, and its whole wave waits for it - a finite radius ends the search at that
+        radius.  ``point`` / ``barycentric``: also the closest point itself and its ``(v, w)``.  ``nearest``: also the smallest
+        distance over the groups and the group it belongs to.  The results are those of the exhaustive search over all triangles,
+        bit for bit.  One kernel on the current stream, no host synchronisation."""
+        if not points.is_cuda:
+            raise RuntimeError(NO_CPU)
+        if math.isnan(float(max_distance)) or float(max_distance) < 0:
+            raise ValueError(f"max_distance must be >= 0 and not NaN, got {max_distance}")
+        G, dev = self.groups, self.vertices.device
+        if points.dim() not in (2, 3) or points.size(-1) != 3:
+            raise ValueError(f"points must be (G, N, 3) or (N, 3), got {list(points.shape)}")
+        if points.dim() == 3 and points.size(0) != G:
+            raise ValueError(f"the grid holds {G} groups, the points are {list(points.shape)}")
+        points = (points if points.dim() == 3 else points.unsqueeze(0).expand(G, -1, -1)).detach().to(device=dev, dtype=torch.float32).contiguous()
+        N = points.size(1)
+        found = ClosestPoints(torch.empty((G, N), dtype=torch.float32, device=dev), torch.empty((G, N), dtype=torch.int32, device=dev),
+                              torch.empty((G, N, 3), dtype=torch.float32, device=dev) if point else None,
+                              torch.empty((G, N, 2), dtype=torch.float32, device=dev) if barycentric else None)
+        if N > 0:
+            with torch.cuda.device(dev):
+                s = closest_struct(self.vertices, self.triangles, self.vertex_offsets, self.triangle_offsets, self.total_vertices,
+                                   self.total_triangles, self.origin, self.cell, self.cells, self.cell_offsets,
+                                   references=self.references if self.references.numel() else None, points=points,
+                                   distance=found.distance, triangle=found.triangle, point=found.point, barycentric=found.barycentric,
+                                   max_distance=max_distance)
+                _lib.check(_lib.load().pr_closest_query(C.byref(s), torch.cuda.current_stream(dev).cuda_stream), "pr_closest_query")
+        if nearest:
+            found.nearest_distance, group = torch.min(found.distance, dim=0)
+            hit = found.triangle.gather(0, group.unsqueeze(0)).squeeze(0) >= 0
+            found.group = torch.where(hit, group, torch.full_like(group, -1))
+        return found
+
+
+def closest_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offsets: torch.Tensor, triangle_offsets: torch.Tensor,
+                   total_vertices: int, total_triangles: int, origin, cell, cells, cell_offsets: torch.Tensor, *,
+                   references: Optional[torch.Tensor] = None, points: Optional[torch.Tensor] = None,
+                   distance: Optional[torch.Tensor] = None, triangle: Optional[torch.Tensor] = None,
+                   point: Optional[torch.Tensor] = None, barycentric: Optional[torch.Tensor] = None,
+                   max_distance: float = math.inf) -> _lib.Closest:
+    """``pr_closest_t`` over prepared tensors (fp32 / int32, contiguous, one device); ``max_references`` is the rows of ``references``,
+    ``count`` the second dimension of ``points (G, N, 3)``."""
+    s = _lib.Closest()
+    s.groups = vertex_offsets.numel() - 1
+    s.total_vertices = int(total_vertices)
+    s.total_triangles = int(total_triangles)
+    s.flags = 0
+    for a in range(3):
+        s.origin[a] = float(origin[a])
+        s.cell[a] = float(cell[a])
+        s.cells[a] = int(cells[a])
+    s.max_references = 0 if references is None else references.size(0)
+    s.count = 0 if points is None else points.size(1)
+    s.max_distance = float(max_distance)
+    for name, x in (("vertices", vertices), ("triangles", triangles), ("vertex_offsets", vertex_offsets),
+                    ("triangle_offsets", triangle_offsets), ("cell_offsets", cell_offsets), ("references", references),
+                    ("points", points), ("distance", distance), ("triangle", triangle), ("point", point), ("barycentric", barycentric)):
+        setattr(s, name, None if x is None else x.data_ptr())
+    return s
+
+
+@dataclass
+class ClosestPoints:
+    """What ``RayGrid.closest`` returns: ``distance (G, N)`` (``+inf``: nothing within ``max_distance``), ``triangle (G, N)`` int32 local
+    to the group (-1: a miss), ``point (G, N, 3)`` - the closest point, zeros for a miss - or None, ``barycentric (G, N, 2)`` =
+    ``(v, w)`` (the point is ``a + v (b - a) + w (c - a)``) or None; with ``nearest=True`` also ``nearest_distance (N)`` and ``group
+    (N)`` int64: the smallest distance over the groups and the group it belongs to (-1: none found)."""
+    distance: torch.Tensor
+    triangle: torch.Tensor
+    point: Optional[torch.Tensor] = None
+    barycentric: Optional[torch.Tensor] = None
+    nearest_distance: Optional[torch.Tensor] = None
+    group: Optional[torch.Tensor] = None
 
 
 def bounding_grid(meshes: Sequence[Mesh], cells):
