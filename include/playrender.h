@@ -868,6 +868,81 @@ typedef struct pr_closest_t {
 int pr_closest_query(const pr_closest_t* s, void* stream);
 
 /*
+ * Inside / outside queries against packed meshes on the grid of pr_raycast_build: pr_inside_query computes, for N points per group,
+ * the winding number of the group's mesh around the point along one coordinate axis - the signed count of the triangles the ray from
+ * the point in the +axis direction passes through.  It reads what pr_closest_query reads and builds nothing.  It is WATERTIGHT BY
+ * CONSTRUCTION: every decision on which the topology depends is taken in exact arithmetic.  The result is DEFINED as that of the
+ * exhaustive sum over all candidates below; the grid may change the time and never the bits - without any domain restriction.
+ *   Mesh and grid input: as pr_closest_t (same fields, same clamping of offsets, same grid coordinates and lists, from a finished
+ *     EMITTING pr_raycast_build).
+ *   Points: points (G, N, 3) fp32 in the meshes' frame, N = count.  axis = k in {0, 1, 2}, one per call; i = (k + 1) mod 3,
+ *     j = (k + 2) mod 3.
+ *   Candidates of a point of group g: the triangles of group g that pr_raycast_build does not classify as dead (an index outside
+ *     [0, V_g), or a == b or a == c as values) and whose nine coordinates are finite.
+ *   Edge sign s(u, v) of a directed edge u -> v for the point p: the sign of the EXACT real value of
+ *       E = (v_i - u_i) (p_j - u_j) - (v_j - u_j) (p_i - u_i)
+ *     - every fp32 input is a rational, nothing is rounded.  If E = 0: the sign of u_j - v_j; if that is 0 too, the sign of
+ *     v_i - u_i; if both are 0 (u and v project to one point), 0.  This is the symbolic perturbation p' = (p_i + eps, p_j + eps^2):
+ *     s(u, v) = -s(v, u) exactly, and a perturbed point lies on no edge.
+ *   Orientation of a candidate (a, b, c): o = s(a, b) if s(a, b) = s(b, c) = s(c, a) != 0, else 0.  Exact: of two triangles that
+ *     share an edge by vertex values, with opposite directions, never both and never neither claim a point across that edge.
+ *   A candidate with o != 0 is AHEAD of p iff max(a_k, b_k, c_k) > p_k (an exact fp32 comparison) and sign(S) = -o, where S is
+ *     computed in float64, every fp32 converted first, no contraction, in this order:
+ *       e1 = b - a, e2 = c - a, n = e1 cross e2 ((x cross y)_0 = x1 y2 - x2 y1, cyclic; each component one difference of two
+ *       products), d = p - a, S = (n_0 d_0 + n_1 d_1) + n_2 d_2.       S = 0: not ahead.
+ *   Result per point: winding (G, N) int32 = the sum of o over the ahead candidates of the point's own group, always written;
+ *     crossings (G, N) int32 = their number, optional.  With the mesher's orientation (normals out of matter) a point inside a
+ *     closed mesh gets +1.  A point with a component that is not finite gets 0 / 0 and tests nothing.
+ *   What is guaranteed: the 2-D decisions are exact.  For a mesh in which every directed edge (by vertex VALUES) occurs as often
+ *     as its reverse, the signed coverage of every point - the sum of o over ALL candidates - is 0, and the winding is a
+ *     topological invariant up to the float64 ahead test, which can only err for a point within float64 rounding of a triangle's
+ *     plane.  For such points - points ON the surface - the three axes may legitimately differ.  What is not: an open mesh (one
+ *     that reaches the border of its lattice: cap it, PR_COMPONENTS_CLOSE_BORDER / close_border=True) and a mesh simplified with
+ *     its duplicate triangles removed (keep them: PR_SIMPLIFY_KEEP_DUPLICATES / keep_duplicates=True) leave directed edges
+ *     unpaired; they get the rule's result, which is then no statement about a solid.
+ *   Query: one lane per point.  The lane tests the group's loose list with the rule.  With g_m = (p_m - origin_m) / cell_m in fp32
+ *     (the build's two roundings) and the start cell s_m = (int)g_m: if g_i or g_j is outside [0, cells), or g_k >= cells_k, no tight
+ *     triangle is tested.  Otherwise the lane visits the cells (s_i, s_j, m), m = max(s_k, 0) .. cells_k - 1, of its column, and a
+ *     triangle found in the list of cell m is tested there iff m = max(lo_k, max(s_k, 0)), lo_k = (int)(min of its three grid
+ *     coordinates on axis k - 1/16) recomputed with the build's own expression: a triangle listed in several cells of the column
+ *     is summed once.  Nothing is missed (argument: DESIGN.md 23.2 - only the monotonicity of fp32 subtraction and division is
+ *     used, and the first ahead condition, which rejects every triangle whose cells lie below the start cell).  Per candidate:
+ *     exact fp32 rejections first (p_i < min_i, p_i > max_i, likewise on j, max_k <= p_k - closed intervals, the perturbation can
+ *     move a boundary point in but never a strictly outside point), then per edge E in float64 with a forward error bound
+ *     ((3 + 16 e) e (|left| + |right|), e = 2^-53), then - where the bound does not decide - the exact sign of the six products
+ *     of the expanded determinant, each exact in a double, by an expansion sum of fifteen error-free additions.
+ *     References outside [0, max_references) or [0, T_g) and triangle indices outside [0, V_g) are skipped where they are read,
+ *     and the column loop is bounded by cells_k: a stale or foreign grid costs correctness, never memory safety.
+ * One kernel on `stream`, no workspace: no memset, no memcpy, no allocation, no synchronisation, no atomics - capturable as a one-node
+ * HIP graph.  Additive entry point: PR_ABI_VERSION is unchanged.  sizeof(pr_inside_t) = 136.
+ * Refused (PR_ERR_INVALID, before any device work): everything pr_closest_query refuses about mesh, grid and capacities, NULL points
+ * or winding, an axis outside 0 .. 2, flags other than 0, G (N + 256) at or above 2^31.  count == 0 launches nothing;
+ * total_triangles == 0 gives zeros.
+ */
+typedef struct pr_inside_t {
+    int32_t groups;                       /* G >= 1 */
+    int32_t total_vertices;               /* V = vertex_offsets[G], as a host value, >= 0 */
+    int32_t total_triangles;              /* T = triangle_offsets[G], as a host value, >= 0 */
+    uint32_t flags;                       /* no flag is defined: 0 */
+    float origin[3];                      /* the grid of the build: finite */
+    float cell[3];                        /* finite, > 0 */
+    int32_t cells[3];                     /* each 1 .. PR_RAYCAST_MAX_AXIS_CELLS, product <= PR_RAYCAST_MAX_CELLS */
+    int32_t max_references;               /* rows of references, >= 0 */
+    int32_t count;                        /* N per group, >= 0 */
+    int32_t axis;                         /* k: 0, 1 or 2 - the ray runs from the point in the +k direction */
+    const float* vertices;                /* (V, 3) */
+    const int32_t* triangles;             /* (T, 3), indices local to the group */
+    const int32_t* vertex_offsets;        /* (G + 1) */
+    const int32_t* triangle_offsets;      /* (G + 1) */
+    const int32_t* cell_offsets;          /* (G (C + 1) + 1), as pr_raycast_build wrote them */
+    const int32_t* references;            /* (max_references), as an emitting pr_raycast_build wrote them (NULL: max_references 0) */
+    const float* points;                  /* (G, N, 3) */
+    int32_t* winding;                     /* (G, N), always written */
+    int32_t* crossings;                   /* (G, N) or NULL */
+} pr_inside_t;
+int pr_inside_query(const pr_inside_t* s, void* stream);
+
+/*
  * Backward pass of pr_render_forward (what torch.autograd does for the reference's op graph when
  * training/trainer_backpropagated_autoencoder.py:349 calls total_loss.backward()).  The forward call must
  * have run with PR_FLAG_SAVE_FOR_BACKWARD (with or without PR_FLAG_TRAIN_BN) on the same `call`, `objects` and

@@ -16,7 +16,8 @@ Public surface (mirrors the reference's modules for the renderer hot path only):
                             evaluate a lattice only in a band around the level set; surface.simplify_meshes reduces
                             extracted meshes by vertex clustering (extract_mesh(simplify=k)); surface.RayGrid casts rays
                             against them (closest hits on a cell grid) and finds the closest point of a mesh to a point
-                            (RayGrid.closest, Mesh.distance_to)
+                            (RayGrid.closest, Mesh.distance_to) and whether a point lies inside one (RayGrid.winding /
+                            contains / signed_distance: watertight, exact where the topology depends on it)
   ray_sampling, wire_format pixel / ray samplers and the renderer <-> decoder tensor glue of the reference
   parallel                  frame shards, overlapped feature all-gather, gradient all-reduce (torch.distributed / RCCL)
   configs / synthetic       shipped renderer configurations and seeded synthetic scenes

@@ -260,6 +260,15 @@ class Closest(C.Structure):
                 ("point", C.c_void_p), ("barycentric", C.c_void_p)]
 
 
+class Inside(C.Structure):
+    """pr_inside_t (include/playrender.h)."""
+    _fields_ = [("groups", C.c_int32), ("total_vertices", C.c_int32), ("total_triangles", C.c_int32), ("flags", C.c_uint32),
+                ("origin", C.c_float * 3), ("cell", C.c_float * 3), ("cells", C.c_int32 * 3), ("max_references", C.c_int32),
+                ("count", C.c_int32), ("axis", C.c_int32), ("vertices", C.c_void_p), ("triangles", C.c_void_p),
+                ("vertex_offsets", C.c_void_p), ("triangle_offsets", C.c_void_p), ("cell_offsets", C.c_void_p),
+                ("references", C.c_void_p), ("points", C.c_void_p), ("winding", C.c_void_p), ("crossings", C.c_void_p)]
+
+
 # every exported symbol of include/playrender.h : (restype, argtypes)
 class SceneSetup(C.Structure):
     """pr_scene_setup_t (include/playrender.h)."""
@@ -307,6 +316,7 @@ SYMBOLS = {
     "pr_raycast_build": (C.c_int, [C.POINTER(Raycast), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_raycast_query": (C.c_int, [C.POINTER(Raycast), C.c_void_p]),
     "pr_closest_query": (C.c_int, [C.POINTER(Closest), C.c_void_p]),
+    "pr_inside_query": (C.c_int, [C.POINTER(Inside), C.c_void_p]),
     "pr_backward_workspace_size": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(C.c_size_t)]),
     "pr_render_backward": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(OutputGrads), C.POINTER(OutputGrads),
                                      C.POINTER(InputGrads), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -20,7 +20,9 @@ the device and independent of the execution order - what ``extract_surface(simpl
 ``RayGrid`` / ``Mesh.ray_grid`` (``pr_raycast_build`` / ``pr_raycast_query``) answer closest-hit ray queries against such meshes on a
 uniform cell grid: ``RayGrid.build(meshes, *bounding_grid(meshes, 32)).cast(origins, directions)``.  ``RayGrid.closest``
 (``pr_closest_query``) finds the closest point of a mesh to a point on the same grid, and ``Mesh.distance_to`` measures how far one mesh
-lies from another with it.
+lies from another with it.  ``RayGrid.winding`` / ``contains`` / ``signed_distance`` (``pr_inside_query``) decide on the same grid whether
+a point lies inside a mesh - watertight by construction, for capped meshes (``close_border=True``) that kept their duplicates when
+simplified (``keep_duplicates=True``).
 """
 from __future__ import annotations
 
@@ -604,6 +606,95 @@ class RayGrid:
             found.group = torch.where(hit, group, torch.full_like(group, -1))
         return found
 
+    def winding(self, points: torch.Tensor, *, axis: int = 2, crossings: bool = False) -> "Winding":
+        """The winding number of the meshes around every point, along the coordinate axis ``axis`` (``pr_inside_query``): the
+        signed count of the triangles that the ray from the point in the ``+axis`` direction passes through, +1 inside a closed mesh
+        of the mesher's orientation.  ``points`` is ``(G, N, 3)`` or ``(N, 3)`` as for ``closest``.  ``crossings``: also the unsigned
+        count.  Watertight by construction - the decisions the topology depends on are exact -, and equal to the exhaustive sum over
+        all triangles whatever the grid.  The answer is a statement about a solid only for a mesh whose directed edges pair up: a
+        mesh extracted with ``close_border=True`` (an uncapped mesh is open where it reaches the lattice border), simplified - if at
+        all - with ``keep_duplicates=True``.  For a point on the surface itself the three axes may differ.  One kernel on the current
+        stream, no host synchronisation."""
+        if not points.is_cuda:
+            raise RuntimeError(NO_CPU)
+        G, dev = self.groups, self.vertices.device
+        if points.dim() not in (2, 3) or points.size(-1) != 3:
+            raise ValueError(f"points must be (G, N, 3) or (N, 3), got {list(points.shape)}")
+        if points.dim() == 3 and points.size(0) != G:
+            raise ValueError(f"the grid holds {G} groups, the points are {list(points.shape)}")
+        points = (points if points.dim() == 3 else points.unsqueeze(0).expand(G, -1, -1)).detach().to(device=dev, dtype=torch.float32).contiguous()
+        try:
+            axis = operator.index(axis)
+        except TypeError:
+            raise ValueError(f"axis must be 0, 1 or 2, got {axis!r}") from None
+        if axis not in (0, 1, 2):
+            raise ValueError(f"axis must be 0, 1 or 2, got {axis}")
+        N = points.size(1)
+        found = Winding(torch.empty((G, N), dtype=torch.int32, device=dev),
+                        torch.empty((G, N), dtype=torch.int32, device=dev) if crossings else None)
+        if N > 0:
+            with torch.cuda.device(dev):
+                s = inside_struct(self.vertices, self.triangles, self.vertex_offsets, self.triangle_offsets, self.total_vertices,
+                                  self.total_triangles, self.origin, self.cell, self.cells, self.cell_offsets,
+                                  references=self.references if self.references.numel() else None, points=points, axis=axis,
+                                  winding=found.winding, crossings=found.crossings)
+                _lib.check(_lib.load().pr_inside_query(C.byref(s), torch.cuda.current_stream(dev).cuda_stream), "pr_inside_query")
+        return found
+
+    def contains(self, points: torch.Tensor, *, axis: int = 2, any: bool = False):
+        """Whether every point lies inside its group's mesh: bool ``(G, N)``, ``winding != 0``.  With ``any=True`` a triple: that,
+        bool ``(N)`` - inside any group's mesh - and int64 ``(N)``, the lowest containing group or -1.  Meaningful for the meshes
+        ``winding`` is meaningful for (capped with ``close_border=True``, duplicates kept when simplified); a point on the surface
+        may fall on either side.  No host synchronisation."""
+        inside = self.winding(points, axis=axis).winding != 0
+        if not any:
+            return inside
+        anywhere = inside.any(dim=0)
+        lowest = torch.argmax(inside.to(torch.uint8), dim=0)             # (the first maximum: the lowest group that contains the point)
+        return inside, anywhere, torch.where(anywhere, lowest, torch.full_like(lowest, -1))
+
+    def signed_distance(self, points: torch.Tensor, *, max_distance: float, axis: int = 2, nearest: bool = False) -> torch.Tensor:
+        """``closest``'s distance ``(G, N)``, negative where ``contains``; beyond ``max_distance`` it is ``-inf`` inside and ``+inf``
+        outside.  ``nearest=True``: the minimum over the groups, ``(N)`` - the signed distance of the union of the solids.  Two
+        launches (``pr_closest_query``, ``pr_inside_query``), no host synchronisation.  The sign is that of ``contains``: meaningful
+        for capped meshes (``close_border=True``) that kept their duplicates when simplified (``keep_duplicates=True``)."""
+        distance = self.closest(points, max_distance=max_distance).distance
+        signed = torch.where(self.contains(points, axis=axis), -distance, distance)
+        return signed.amin(dim=0) if nearest else signed
+
+
+@dataclass
+class Winding:
+    """What ``RayGrid.winding`` returns: ``winding (G, N)`` int32 and ``crossings (G, N)`` int32 - how many triangles the ray from
+    the point passes through - or None."""
+    winding: torch.Tensor
+    crossings: Optional[torch.Tensor] = None
+
+
+def inside_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offsets: torch.Tensor, triangle_offsets: torch.Tensor,
+                  total_vertices: int, total_triangles: int, origin, cell, cells, cell_offsets: torch.Tensor, *,
+                  references: Optional[torch.Tensor] = None, points: Optional[torch.Tensor] = None, axis: int = 2,
+                  winding: Optional[torch.Tensor] = None, crossings: Optional[torch.Tensor] = None) -> _lib.Inside:
+    """``pr_inside_t`` over prepared tensors (fp32 / int32, contiguous, one device); ``max_references`` is the rows of ``references``,
+    ``count`` the second dimension of ``points (G, N, 3)``."""
+    s = _lib.Inside()
+    s.groups = vertex_offsets.numel() - 1
+    s.total_vertices = int(total_vertices)
+    s.total_triangles = int(total_triangles)
+    s.flags = 0
+    for a in range(3):
+        s.origin[a] = float(origin[a])
+        s.cell[a] = float(cell[a])
+        s.cells[a] = int(cells[a])
+    s.max_references = 0 if references is None else references.size(0)
+    s.count = 0 if points is None else points.size(1)
+    s.axis = int(axis)
+    for name, x in (("vertices", vertices), ("triangles", triangles), ("vertex_offsets", vertex_offsets),
+                    ("triangle_offsets", triangle_offsets), ("cell_offsets", cell_offsets), ("references", references),
+                    ("points", points), ("winding", winding), ("crossings", crossings)):
+        setattr(s, name, None if x is None else x.data_ptr())
+    return s
+
 
 def closest_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offsets: torch.Tensor, triangle_offsets: torch.Tensor,
                    total_vertices: int, total_triangles: int, origin, cell, cells, cell_offsets: torch.Tensor, *,
@@ -677,7 +768,7 @@ def bounding_grid(meshes: Sequence[Mesh], cells):
 
 
 def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float, *, normals: bool = True, keep_largest: int = 0,
-                    min_points: int = 0, close_border: bool = False, simplify: int = 0) -> List[Mesh]:
+                    min_points: int = 0, close_border: bool = False, simplify: int = 0, keep_duplicates: bool = False) -> List[Mesh]:
     """Meshes of the level set ``sigma = level`` of ``sigma (G, nx, ny, nz)`` (device tensor, z fastest - what ``density_grid``
     returns); ``axes``: the coordinates of the lattice points along x, y, z (``nx``, ``ny``, ``nz`` values).  Returns G meshes.
 
@@ -690,7 +781,9 @@ def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: fl
 
     ``simplify = k >= 1``: the meshes are then clustered (``simplify_meshes``) on the grid aligned with the lattice whose cells span
     ``k`` lattice steps (``lattice_cluster_grid``) - evaluate the field finely, keep a mesh of a coarser lattice's size.  Two more
-    read-backs (the ends of the axes, the simplified sizes).  At 0 (the default) nothing changes."""
+    read-backs (the ends of the axes, the simplified sizes).  At 0 (the default) nothing changes.  ``keep_duplicates`` is
+    ``simplify_meshes``'s: duplicate triangles stay, so that every directed edge keeps its partner - what ``RayGrid.winding`` /
+    ``contains`` need of a simplified mesh."""
     if not sigma.is_cuda:
         raise RuntimeError(NO_CPU)
     if sigma.dim() != 4:
@@ -731,7 +824,7 @@ def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: fl
             _lib.check(lib.pr_extract_surface(C.byref(emit), workspace.data_ptr(), size.value, stream), "pr_extract_surface")
     if simplify:
         grid = _cluster_grid(*lattice_cluster_grid(axes, simplify))
-        return _simplify_packed(vertices, vertex_normals, triangles, vertex_offsets, triangle_offsets, *grid, False)
+        return _simplify_packed(vertices, vertex_normals, triangles, vertex_offsets, triangle_offsets, *grid, bool(keep_duplicates))
     meshes = []
     for g in range(G):
         v0, v1, t0, t1 = vertex_offsets[g], vertex_offsets[g + 1], triangle_offsets[g], triangle_offsets[g + 1]
