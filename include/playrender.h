@@ -943,6 +943,80 @@ typedef struct pr_inside_t {
 int pr_inside_query(const pr_inside_t* s, void* stream);
 
 /*
+ * Audit of packed meshes: pr_mesh_audit says, per group, how a mesh is made up - whether its directed edges balance (what
+ * pr_inside_query's guarantee asks of a mesh), its boundary and non-manifold edges, Euler characteristic, connected shells, area,
+ * signed volume and centroid, and optionally the shell of every triangle.  It reads a mesh and changes nothing; there is no grid.
+ *   Input: G meshes packed as pr_extract_surface / pr_simplify_mesh leave them - vertices (V, 3) fp32, triangles (T, 3) int32 LOCAL
+ *     to their group, vertex_offsets (G + 1), triangle_offsets (G + 1), all on the device; total_vertices / total_triangles are V and
+ *     T as host values.  Offsets that leave [0, V] / [0, T] or decrease are clamped as pr_simplify_mesh clamps them, never followed.
+ *   Candidates: EXACTLY pr_inside_query's - a triangle (a, b, c) of group g whose three indices lie in [0, V_g), whose nine
+ *     coordinates are finite, and with neither a == b nor a == c as values.  This is the one definition; pr_inside_query states the
+ *     same.  Every other triangle of the group is DROPPED: it is counted and takes no further part.  (b == c is a candidate.)
+ *   Vertex identity is by VALUE: two vertices of a group are the same iff their three fp32 components compare equal with ==, so -0
+ *     equals +0.  (The mesher gives coinciding vertices where lattice values equal the level; identity by index would call such a
+ *     mesh open although pr_inside_query treats it as closed.)  The representative of a class is its lowest vertex index.
+ *   Edges: an undirected edge is a pair {r, s} of distinct representatives, r < s.  A candidate has the three sides a -> b, b -> c,
+ *     c -> a; a side whose ends have one representative (possible only for b == c) is no edge and is skipped.  Per edge, f is the
+ *     number of candidate sides that run r -> s and b the number that run s -> r.
+ *   counts (G, 12) int32, always and fully written:
+ *       [0] candidates F                    [1] dropped triangles
+ *       [2] distinct vertices by value that a side of a candidate refers to, Vr       [3] undirected edges E
+ *       [4] unbalanced edges, f != b        [5] boundary edges, f + b == 1            [6] non-manifold edges, f + b > 2
+ *       [7] Euler characteristic Vr - E + F [8] shells                                [9] triangles of the largest shell
+ *       [10], [11] reserved, 0
+ *     "Every directed edge occurs as often as its reverse" holds exactly when counts[4] == 0; a closed oriented manifold - every
+ *     directed edge once, its reverse once - also needs counts[5] == counts[6] == 0.
+ *   Shells: two candidates are connected if they have a side on the same undirected edge; the shells are the classes of the
+ *     transitive closure.  labels (T) int32, optional: for a candidate the lowest triangle index (local to the group) of its shell,
+ *     -1 for a dropped triangle and for a row that no clamped group owns.  Neither the algorithm nor the order of arrival shows.
+ *   measures (G, 8) fp64, optional: area, signed volume, the three components of the area-weighted centroid of the surface, three
+ *     reserved zeros.  Per candidate, in fp64 with every fp32 converted first, no contraction, in this order:
+ *       e1 = b - a, e2 = c - a, n = e1 cross e2 ((x cross y)_0 = x1 y2 - x2 y1, cyclic; a component is one difference of two products),
+ *       area term    0.5 sqrt((n_0 n_0 + n_1 n_1) + n_2 n_2),
+ *       volume term  ((a_0 m_0 + a_1 m_1) + a_2 m_2) / 6 with m = b cross c,
+ *       centroid term, per axis k   area (((a_k + b_k) + c_k) / 3).
+ *     The sums are taken in a FIXED TREE, so that they are equal from run to run: triangle t of the group (local index) is lane
+ *     t mod 256 of block t / 256, lanes without a candidate hold 0; in each of the block's four waves of 64 lanes, for d = 32, 16, 8,
+ *     4, 2, 1 in turn lane i takes x_i + x_(i + d) (i + d < 64), and lane 0 then holds the wave's sum w; the block's partial is
+ *     ((w_0 + w_1) + w_2) + w_3.  One block per group then sums the partials: its lane j adds, starting from 0, the partials of the
+ *     blocks j, j + 256, j + 512, ... in that order, and the 256 lane sums go through the same tree.  The result lies within
+ *     T_g 2^-52 sum|term| of the exact sum.  The centroid sums are divided by the area at the end; the centroid is 0 where the area
+ *     is not > 0.  No floating-point atomic anywhere.
+ *   T = 0 or an empty group gives zeros: its Euler characteristic and shell count are 0.
+ *   Memory safety: every index read from the mesh or from a table is range-checked where it is read.  Hostile input may cost the
+ *     correctness of the hostile group, never memory safety, and never another group's rows.
+ * Workspace bytes = the sum of these regions, each rounded up to 256 bytes, with BV = ceil(V / 256) + G and BT = ceil(T / 256) + G
+ *   (upper bounds of the blocks of 256 vertices / triangles, none across two groups): 4 x 4 (G + 1) (per group:
+ *   first vertex, first triangle, first vertex block, first triangle block) + 8 V (weld table, 2 V slots) + 4 V (representatives) +
+ *   4 V (referenced flags) + 48 T (edge keys, 6 T slots) + 48 T (forward and backward counters) + 24 T (edge owners) + 12 T (the three
+ *   slots of a triangle) + 4 T (union-find parents) + 4 T (shell sizes) + 40 BT (fp64 block partials) + 32 BT + 4 BV (integer block
+ *   partials): 16 bytes per vertex, 140 per triangle.
+ * Nine kernel launches on `stream` (eight without measures), no memset, no memcpy, no allocation, no synchronisation: capturable into
+ * a HIP graph.  Integer atomics only.  The tables' layouts depend on the order of arrival; no output does.
+ * Additive entry points: PR_ABI_VERSION is unchanged.  sizeof(pr_mesh_audit_t) = 72.
+ * Refused (PR_ERR_INVALID, before any device work; by pr_mesh_audit_workspace_size too, except the workspace itself): NULL vertices,
+ * triangles, offsets or counts, groups < 1, a negative total, flags other than 0 (no flag is defined), 2 V + 256 G or 6 T + 256 G at or
+ * above 2^31 (the table slots are int32); by the call only: a NULL, misaligned or too small workspace.
+ */
+typedef struct pr_mesh_audit_t {
+    int32_t groups;                       /* G >= 1 */
+    int32_t total_vertices;               /* V = vertex_offsets[G], as a host value, >= 0 */
+    int32_t total_triangles;              /* T = triangle_offsets[G], as a host value, >= 0 */
+    uint32_t flags;                       /* no flag is defined: 0 */
+    const float* vertices;                /* (V, 3) */
+    const int32_t* triangles;             /* (T, 3), indices local to the group */
+    const int32_t* vertex_offsets;        /* (G + 1) */
+    const int32_t* triangle_offsets;      /* (G + 1) */
+    int32_t* counts;                      /* (G, 12), always written */
+    double* measures;                     /* (G, 8) or NULL */
+    int32_t* labels;                      /* (T) or NULL */
+} pr_mesh_audit_t;
+/* Host computation, no device work; refuses everything above that does not concern the workspace. */
+int pr_mesh_audit_workspace_size(const pr_mesh_audit_t* s, size_t* bytes);
+/* `workspace`: 256-byte aligned, pr_mesh_audit_workspace_size bytes. */
+int pr_mesh_audit(const pr_mesh_audit_t* s, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Backward pass of pr_render_forward (what torch.autograd does for the reference's op graph when
  * training/trainer_backpropagated_autoencoder.py:349 calls total_loss.backward()).  The forward call must
  * have run with PR_FLAG_SAVE_FOR_BACKWARD (with or without PR_FLAG_TRAIN_BN) on the same `call`, `objects` and

@@ -269,6 +269,17 @@ class Inside(C.Structure):
                 ("references", C.c_void_p), ("points", C.c_void_p), ("winding", C.c_void_p), ("crossings", C.c_void_p)]
 
 
+class MeshAudit(C.Structure):
+    """pr_mesh_audit_t (include/playrender.h)."""
+    _fields_ = [("groups", C.c_int32), ("total_vertices", C.c_int32), ("total_triangles", C.c_int32), ("flags", C.c_uint32),
+                ("vertices", C.c_void_p), ("triangles", C.c_void_p), ("vertex_offsets", C.c_void_p), ("triangle_offsets", C.c_void_p),
+                ("counts", C.c_void_p), ("measures", C.c_void_p), ("labels", C.c_void_p)]
+
+
+AUDIT_COUNTS = 12                # columns of pr_mesh_audit_t.counts
+AUDIT_MEASURES = 8               # columns of pr_mesh_audit_t.measures
+
+
 # every exported symbol of include/playrender.h : (restype, argtypes)
 class SceneSetup(C.Structure):
     """pr_scene_setup_t (include/playrender.h)."""
@@ -317,6 +328,8 @@ SYMBOLS = {
     "pr_raycast_query": (C.c_int, [C.POINTER(Raycast), C.c_void_p]),
     "pr_closest_query": (C.c_int, [C.POINTER(Closest), C.c_void_p]),
     "pr_inside_query": (C.c_int, [C.POINTER(Inside), C.c_void_p]),
+    "pr_mesh_audit_workspace_size": (C.c_int, [C.POINTER(MeshAudit), C.POINTER(C.c_size_t)]),
+    "pr_mesh_audit": (C.c_int, [C.POINTER(MeshAudit), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_backward_workspace_size": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(C.c_size_t)]),
     "pr_render_backward": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(OutputGrads), C.POINTER(OutputGrads),
                                      C.POINTER(InputGrads), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),

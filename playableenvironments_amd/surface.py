@@ -23,6 +23,10 @@ uniform cell grid: ``RayGrid.build(meshes, *bounding_grid(meshes, 32)).cast(orig
 lies from another with it.  ``RayGrid.winding`` / ``contains`` / ``signed_distance`` (``pr_inside_query``) decide on the same grid whether
 a point lies inside a mesh - watertight by construction, for capped meshes (``close_border=True``) that kept their duplicates when
 simplified (``keep_duplicates=True``).
+
+``audit_meshes`` / ``Mesh.audit`` / ``RayGrid.audit`` (``pr_mesh_audit``) say how a mesh is made up - whether its directed edges balance
+by vertex value (what ``contains`` needs), boundary and non-manifold edges, Euler characteristic, shells, area, signed volume, centroid -
+and ``Mesh.keep_shells`` drops the fragments that a simplification detached.
 """
 from __future__ import annotations
 
@@ -87,6 +91,37 @@ class Mesh:
         if other.groups != 1:
             raise ValueError(f"distance_to needs a grid of one group, got {other.groups}")
         return other.closest(self.vertices, max_distance=max_distance).distance[0]
+
+    def audit(self, labels: bool = False) -> "MeshAudit":
+        """How this one mesh is made up: ``audit_meshes([self], labels=labels)[0]``."""
+        return audit_meshes([self], labels=labels)[0]
+
+    def keep_shells(self, n: int) -> "Mesh":
+        """The mesh restricted to its ``n`` largest shells by triangle count (ties: the lower label first; ``MeshAudit.labels``):
+        floater removal AFTER simplification, which can detach fragments that ``clean_lattice`` never saw.  Dropped triangles (an
+        index out of range, a vertex that is not finite, ``a == b`` or ``a == c`` as values) belong to no shell and go.  The
+        triangles that stay keep their order; vertices, normals and features are kept whole, as the simplifier keeps unreferenced
+        vertices.  One audit, a ``bincount`` / ``topk`` over its labels and a boolean selection, which reads the number of kept
+        triangles back: ONE host synchronisation."""
+        try:
+            n = operator.index(n)
+        except TypeError:
+            raise ValueError(f"n must be an integer >= 1, got {n!r}") from None
+        if n < 1:
+            raise ValueError(f"n must be an integer >= 1, got {n}")
+        labels = self.audit(labels=True).labels.to(torch.int64)
+        T = labels.numel()
+        if T == 0:
+            return Mesh(self.vertices, self.triangles, self.normals, self.features)
+        candidate = labels >= 0
+        sizes = torch.bincount(labels[candidate], minlength=T)                # (at the shell's label, its lowest triangle)
+        index = torch.arange(T, device=labels.device)
+        key = torch.where(sizes > 0, sizes * (T + 1) + (T - index), torch.zeros_like(sizes))      # size first, then the lower label
+        best = torch.topk(key, min(n, T)).indices
+        kept_label = torch.zeros(T, dtype=torch.bool, device=labels.device)
+        kept_label[best] = sizes[best] > 0
+        keep = candidate & kept_label[labels.clamp(min=0)]
+        return Mesh(self.vertices, self.triangles[keep], self.normals, self.features)
 
 
 def surface_struct(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float, vertex_offsets: torch.Tensor,
@@ -532,7 +567,23 @@ class RayGrid:
             if R > 0:
                 emit = raycast_struct(*common, references=references)
                 _lib.check(lib.pr_raycast_build(C.byref(emit), workspace.data_ptr(), size.value, stream), "pr_raycast_build")
-        return cls(vertices, triangles, offsets[0], offsets[1], (vo[-1], to[-1]), grid, cell_offsets, references)
+        grid_ = cls(vertices, triangles, offsets[0], offsets[1], (vo[-1], to[-1]), grid, cell_offsets, references)
+        grid_.host_triangle_offsets = to
+        return grid_
+
+    def audit(self, labels: bool = False) -> List["MeshAudit"]:
+        """How the meshes this grid holds are made up (``pr_mesh_audit`` on the packed arrays, one ``MeshAudit`` per group): the
+        question to ask before trusting ``contains`` - ``report()["balanced"]`` says whether every directed edge, by vertex value,
+        occurs as often as its reverse.  One call on the current stream, no host synchronisation (``labels=True`` on a grid that
+        was not made by ``build`` reads the triangle offsets back)."""
+        if not self.vertices.is_cuda:
+            raise RuntimeError(NO_CPU)
+        counts, measures, shell = _audit_packed(self.vertices, self.triangles, self.vertex_offsets, self.triangle_offsets,
+                                                self.total_vertices, self.total_triangles, bool(labels))
+        to = None
+        if labels:
+            to = getattr(self, "host_triangle_offsets", None) or self.triangle_offsets.cpu().tolist()
+        return [MeshAudit(counts[g], measures[g], shell[to[g]:to[g + 1]] if labels else None) for g in range(self.groups)]
 
     def cast(self, origins: torch.Tensor, directions: torch.Tensor, *, t_min: float = 0.0, t_max: float = math.inf,
              cull_back: bool = False, barycentric: bool = False, nearest: bool = False) -> RayHits:
@@ -613,8 +664,8 @@ class RayGrid:
         count.  Watertight by construction - the decisions the topology depends on are exact -, and equal to the exhaustive sum over
         all triangles whatever the grid.  The answer is a statement about a solid only for a mesh whose directed edges pair up: a
         mesh extracted with ``close_border=True`` (an uncapped mesh is open where it reaches the lattice border), simplified - if at
-        all - with ``keep_duplicates=True``.  For a point on the surface itself the three axes may differ.  One kernel on the current
-        stream, no host synchronisation."""
+        all - with ``keep_duplicates=True``; ``RayGrid.audit`` says whether the mesh in hand is one (``balanced``).  For a point on the
+        surface itself the three axes may differ.  One kernel on the current stream, no host synchronisation."""
         if not points.is_cuda:
             raise RuntimeError(NO_CPU)
         G, dev = self.groups, self.vertices.device
@@ -645,7 +696,7 @@ class RayGrid:
         """Whether every point lies inside its group's mesh: bool ``(G, N)``, ``winding != 0``.  With ``any=True`` a triple: that,
         bool ``(N)`` - inside any group's mesh - and int64 ``(N)``, the lowest containing group or -1.  Meaningful for the meshes
         ``winding`` is meaningful for (capped with ``close_border=True``, duplicates kept when simplified); a point on the surface
-        may fall on either side.  No host synchronisation."""
+        may fall on either side.  ``RayGrid.audit`` checks the mesh in hand (``balanced``).  No host synchronisation."""
         inside = self.winding(points, axis=axis).winding != 0
         if not any:
             return inside
@@ -657,7 +708,8 @@ class RayGrid:
         """``closest``'s distance ``(G, N)``, negative where ``contains``; beyond ``max_distance`` it is ``-inf`` inside and ``+inf``
         outside.  ``nearest=True``: the minimum over the groups, ``(N)`` - the signed distance of the union of the solids.  Two
         launches (``pr_closest_query``, ``pr_inside_query``), no host synchronisation.  The sign is that of ``contains``: meaningful
-        for capped meshes (``close_border=True``) that kept their duplicates when simplified (``keep_duplicates=True``)."""
+        for capped meshes (``close_border=True``) that kept their duplicates when simplified (``keep_duplicates=True``).
+        ``RayGrid.audit`` checks the mesh in hand (``balanced``)."""
         distance = self.closest(points, max_distance=max_distance).distance
         signed = torch.where(self.contains(points, axis=axis), -distance, distance)
         return signed.amin(dim=0) if nearest else signed
@@ -735,6 +787,102 @@ class ClosestPoints:
     barycentric: Optional[torch.Tensor] = None
     nearest_distance: Optional[torch.Tensor] = None
     group: Optional[torch.Tensor] = None
+
+
+AUDIT_COUNT_FIELDS = ("candidates", "dropped", "vertices", "edges", "unbalanced_edges", "boundary_edges", "non_manifold_edges",
+                      "euler_characteristic", "shells", "largest_shell")
+
+
+@dataclass
+class MeshAudit:
+    """What ``audit_meshes`` returns per mesh, on the device: ``counts (12)`` int32 and ``measures (8)`` fp64 as ``pr_mesh_audit``
+    (include/playrender.h) defines them, and ``labels (T)`` int32 - per triangle the lowest triangle index of its shell, -1 for a
+    dropped triangle - or None.  ``report()`` reads them back."""
+    counts: torch.Tensor
+    measures: torch.Tensor
+    labels: Optional[torch.Tensor] = None
+
+    def report(self) -> dict:
+        """The audit as a plain dict - ONE read-back: the ten counts by name (``AUDIT_COUNT_FIELDS``), ``area``, ``signed_volume``,
+        ``centroid`` (three floats), ``balanced`` - every directed edge, by vertex value, occurs as often as its reverse: what
+        ``RayGrid.contains`` needs - and ``closed_manifold`` - also no boundary and no non-manifold edge."""
+        host = torch.cat([self.counts.reshape(-1).to(torch.float64), self.measures.reshape(-1).to(torch.float64)]).cpu().tolist()      # (int32 is exact in fp64)
+        out = {name: int(host[i]) for i, name in enumerate(AUDIT_COUNT_FIELDS)}
+        m = host[_lib.AUDIT_COUNTS:]
+        out["area"], out["signed_volume"], out["centroid"] = m[0], m[1], m[2:5]
+        out["balanced"] = out["unbalanced_edges"] == 0
+        out["closed_manifold"] = out["balanced"] and out["boundary_edges"] == 0 and out["non_manifold_edges"] == 0
+        return out
+
+
+def audit_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offsets: torch.Tensor, triangle_offsets: torch.Tensor,
+                 total_vertices: int, total_triangles: int, counts: torch.Tensor, *, measures: Optional[torch.Tensor] = None,
+                 labels: Optional[torch.Tensor] = None) -> _lib.MeshAudit:
+    """``pr_mesh_audit_t`` over prepared tensors (fp32 / int32 / fp64, contiguous, one device)."""
+    s = _lib.MeshAudit()
+    s.groups = vertex_offsets.numel() - 1
+    s.total_vertices = int(total_vertices)
+    s.total_triangles = int(total_triangles)
+    s.flags = 0
+    for name, x in (("vertices", vertices), ("triangles", triangles), ("vertex_offsets", vertex_offsets),
+                    ("triangle_offsets", triangle_offsets), ("counts", counts), ("measures", measures), ("labels", labels)):
+        setattr(s, name, None if x is None else x.data_ptr())
+    return s
+
+
+def _audit_packed(vertices, triangles, vertex_offsets, triangle_offsets, V: int, T: int, labels: bool):
+    """One ``pr_mesh_audit`` call on packed device tensors, on the current stream: ``(counts (G, 12), measures (G, 8), labels (T) or
+    None)``.  The workspace is sized on the host; nothing is read back."""
+    lib = _lib.load()
+    dev = vertices.device
+    G = vertex_offsets.numel() - 1
+    with torch.cuda.device(dev):
+        counts = torch.empty((G, _lib.AUDIT_COUNTS), dtype=torch.int32, device=dev)
+        measures = torch.empty((G, _lib.AUDIT_MEASURES), dtype=torch.float64, device=dev)
+        shell = torch.empty(T, dtype=torch.int32, device=dev) if labels else None
+        s = audit_struct(vertices, triangles, vertex_offsets, triangle_offsets, V, T, counts, measures=measures,
+                         labels=shell if labels and T > 0 else None)
+        size = C.c_size_t()
+        _lib.check(lib.pr_mesh_audit_workspace_size(C.byref(s), C.byref(size)), "pr_mesh_audit_workspace_size")
+        workspace = torch.empty(size.value, dtype=torch.uint8, device=dev)
+        _lib.check(lib.pr_mesh_audit(C.byref(s), workspace.data_ptr(), size.value, torch.cuda.current_stream(dev).cuda_stream),
+                   "pr_mesh_audit")
+    return counts, measures, shell
+
+
+def audit_meshes(meshes: Sequence[Mesh], *, labels: bool = False) -> List[MeshAudit]:
+    """How the meshes are made up (``pr_mesh_audit``, include/playrender.h), one ``MeshAudit`` per mesh.  Vertices are identified by
+    VALUE, as ``RayGrid.contains`` sees them, so the coinciding vertices the mesher emits for lattice values equal to the level do
+    not make a mesh look open.  ``counts``: candidate and dropped triangles, distinct referenced vertices, undirected edges,
+    unbalanced / boundary / non-manifold edges, Euler characteristic, shells, triangles of the largest shell.  ``measures``: area,
+    signed volume (positive for the mesher's orientation), area-weighted centroid - float64 sums in a fixed tree, equal from run to
+    run.  ``labels=True``: also the shell of every triangle (``Mesh.keep_shells`` uses them).
+
+    The meshes are packed as ``simplify_meshes`` packs them; the workspace is sized on the host; one call on the current stream
+    and NO host synchronisation - ``MeshAudit.report()`` is the read-back.  There is no CPU fallback."""
+    meshes = list(meshes)
+    if not meshes:
+        raise ValueError("audit_meshes needs at least one mesh")
+    if not all(m.vertices.is_cuda and m.triangles.is_cuda for m in meshes):
+        raise RuntimeError(NO_CPU)
+    dev = meshes[0].vertices.device
+    for m in meshes:
+        if m.vertices.dim() != 2 or m.vertices.size(1) != 3 or m.triangles.dim() != 2 or m.triangles.size(1) != 3:
+            raise ValueError(f"a mesh has vertices (V, 3) and triangles (T, 3), got {list(m.vertices.shape)} / {list(m.triangles.shape)}")
+    pack = lambda parts, dtype: torch.cat([p.detach().to(device=dev, dtype=dtype).reshape(-1, 3) for p in parts]).contiguous()
+    vertices = pack([m.vertices for m in meshes], torch.float32)
+    triangles = pack([m.triangles for m in meshes], torch.int32)
+    vo, to = [0], [0]
+    for m in meshes:
+        vo.append(vo[-1] + m.vertices.size(0))
+        to.append(to[-1] + m.triangles.size(0))
+    if vertices.size(0) == 0:                                      # (an empty tensor has no address: the library refuses NULL)
+        vertices = torch.empty((1, 3), dtype=torch.float32, device=dev)
+    if triangles.size(0) == 0:
+        triangles = torch.empty((1, 3), dtype=torch.int32, device=dev)
+    offsets = torch.tensor([vo, to], dtype=torch.int32).to(dev)
+    counts, measures, shell = _audit_packed(vertices, triangles, offsets[0], offsets[1], vo[-1], to[-1], bool(labels))
+    return [MeshAudit(counts[g], measures[g], shell[to[g]:to[g + 1]] if labels else None) for g in range(len(meshes))]
 
 
 def bounding_grid(meshes: Sequence[Mesh], cells):
