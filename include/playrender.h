@@ -1017,6 +1017,89 @@ int pr_mesh_audit_workspace_size(const pr_mesh_audit_t* s, size_t* bytes);
 int pr_mesh_audit(const pr_mesh_audit_t* s, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Welding and compaction of packed meshes: pr_mesh_weld returns meshes in which identity by index IS identity by value, every vertex
+ * is referenced and every triangle is a candidate of pr_mesh_audit - what an OBJ viewer, an adjacency builder or any other reader
+ * that trusts indices needs of the meshes that pr_extract_surface, pr_simplify_mesh and Mesh.keep_shells leave.
+ *   Input: G meshes packed as pr_extract_surface / pr_simplify_mesh leave them - vertices (V, 3) fp32, optional normals (V, 3) fp32,
+ *     optional attributes (V, A) fp32 with attribute_width = A, triangles (T, 3) int32 LOCAL to their group, vertex_offsets (G + 1),
+ *     triangle_offsets (G + 1), all on the device; total_vertices / total_triangles are V and T as host values.  Offsets that leave
+ *     [0, V] / [0, T] or decrease are clamped as pr_simplify_mesh and pr_mesh_audit clamp them, never followed.
+ *   Definitions: pr_mesh_audit's.  The CLASS of a finite vertex is the set of its group's vertices whose three fp32 components
+ *     compare equal with == (so -0 equals +0); its REPRESENTATIVE is the lowest index of the class; a vertex with a component that is
+ *     not finite has no class.  With the flag PR_WELD_COMPACT_ONLY every finite vertex is its own representative: nothing is merged
+ *     and only dead rows go.  A KEPT triangle is exactly a candidate of pr_mesh_audit, in both modes: three indices in [0, V_g), nine
+ *     finite coordinates, neither a == b nor a == c as VALUES (b == c stays kept, so that the output's audit equals the input's).
+ *     Every other triangle of the group is dropped and counted.
+ *   Output vertices: one per representative that at least one kept triangle refers to, ordered by group and then by the
+ *     representative's index; the row is the representative's three fp32 words copied bit for bit.  out_normals / out_attributes hold
+ *     the REPRESENTATIVE's rows copied bit for bit, NaNs included: there is NO averaging over a class - the rows of the other members
+ *     are not read.
+ *   Output triangles: the kept ones in input order, each corner replaced by the output index of its representative, local to the
+ *     group.  No rotation.
+ *   vertex_map (V) int32, optional: the output index (local) of the vertex's representative; -1 if the vertex is not finite or its
+ *     representative is unreferenced.  triangle_map (T) int32, optional: the output index (local) of a kept triangle, -1 for a dropped
+ *     one.  Rows of either map that no clamped group owns get -1, as labels in pr_mesh_audit.
+ *   counts (G, 8) int32, always and fully written:
+ *       [0] output vertices        [1] output triangles        [2] dropped triangles        [3] vertices that are not finite
+ *       [4] finite vertices merged into a lower index (0 with PR_WELD_COMPACT_ONLY)
+ *       [5] representatives that no kept triangle refers to    [6], [7] reserved, 0
+ *     V_g = [0] + [3] + [4] + [5] for every group.  Without PR_WELD_COMPACT_ONLY, [0], [1], [2] equal pr_mesh_audit's counts[2], [0],
+ *     [1] of the same input.
+ *   out_vertex_offsets / out_triangle_offsets (G + 1), always written with the true totals.
+ *   An element at or beyond its capacity (max_vertices rows of out_vertices / out_normals / out_attributes, max_triangles rows of
+ *     out_triangles) is not written.  With out_vertices, out_normals, out_attributes, out_triangles, vertex_map and triangle_map all
+ *     NULL the call only counts.
+ *   Memory safety: every index read from the mesh or from a table is range-checked where it is read; rows that no clamped group owns
+ *     are never touched apart from the -1 of the maps.  Hostile input may cost the correctness of the hostile group, never memory
+ *     safety, and never another group's rows.
+ * Workspace bytes = the sum of these regions, each rounded up to 256 bytes, with BV = ceil(V / 256) + G and BT = ceil(T / 256) + G
+ *   (upper bounds of the blocks of 256 vertices / triangles, none across two groups): 4 x 4 (G + 1) (per group: first vertex, first
+ *   triangle, first vertex block, first triangle block) + 8 V (weld table, 2 V slots; reserved but unused with PR_WELD_COMPACT_ONLY) +
+ *   4 V (representatives) + 4 V (referenced flags) + 4 V (output indices) + 4 T (kept flags) + 4 BV (vertex block sums) +
+ *   4 (BV + 1) (their scan and the total) + 4 BT (triangle block sums) + 4 (BT + 1) (their scan and the total) + 12 BV (per vertex
+ *   block: not finite, merged, unreferenced): 20 bytes per vertex, 4 per triangle.
+ * Eight kernel launches on `stream` (seven with PR_WELD_COMPACT_ONLY), the same number whether the call emits or only counts; no
+ * memset, no memcpy, no allocation, no synchronisation: capturable into a HIP graph.  Integer atomics only.  The table's layout
+ * depends on the order of arrival; no output does: a second call gives equal bits everywhere.
+ * Additive entry points: PR_ABI_VERSION is unchanged.  sizeof(pr_mesh_weld_t) = 152.
+ * Refused (PR_ERR_INVALID, before any device work; by pr_mesh_weld_workspace_size too, except the workspace itself): NULL vertices,
+ * triangles, offsets (in or out) or counts, groups < 1, a negative total or capacity, unknown flag bits, attribute_width < 0 or above
+ * 4096, out_attributes without attributes or with attribute_width == 0, out_normals without normals, out_normals or out_attributes
+ * without out_vertices, 2 V + 256 G or T + 256 G at or above 2^31 (the table slots and the block counts are int32; the workspace sum
+ * then stays far below 2^62); by the call only, and last: a NULL, misaligned or too small workspace.
+ */
+#define PR_WELD_COMPACT_ONLY 1u
+typedef struct pr_mesh_weld_t {
+    int32_t groups;                       /* G >= 1 */
+    int32_t total_vertices;               /* V = vertex_offsets[G], as a host value, >= 0 */
+    int32_t total_triangles;              /* T = triangle_offsets[G], as a host value, >= 0 */
+    uint32_t flags;                       /* PR_WELD_COMPACT_ONLY or 0 */
+    int32_t attribute_width;              /* A, 0 .. 4096 */
+    int32_t max_vertices;                 /* rows of out_vertices / out_normals / out_attributes, >= 0 */
+    int32_t max_triangles;                /* rows of out_triangles, >= 0 */
+    uint32_t reserved_;
+    const float* vertices;                /* (V, 3) */
+    const float* normals;                 /* (V, 3) or NULL */
+    const float* attributes;              /* (V, A) or NULL */
+    const int32_t* triangles;             /* (T, 3), indices local to the group */
+    const int32_t* vertex_offsets;        /* (G + 1) */
+    const int32_t* triangle_offsets;      /* (G + 1) */
+    float* out_vertices;                  /* (max_vertices, 3) or NULL */
+    float* out_normals;                   /* (max_vertices, 3) or NULL; needs normals and out_vertices */
+    float* out_attributes;                /* (max_vertices, A) or NULL; needs attributes, A > 0 and out_vertices */
+    int32_t* out_triangles;               /* (max_triangles, 3) or NULL; indices local to the group */
+    int32_t* vertex_map;                  /* (V) or NULL */
+    int32_t* triangle_map;                /* (T) or NULL */
+    int32_t* counts;                      /* (G, 8), always written */
+    int32_t* out_vertex_offsets;          /* (G + 1), always written */
+    int32_t* out_triangle_offsets;        /* (G + 1), always written */
+} pr_mesh_weld_t;
+/* Host computation, no device work; refuses everything above that does not concern the workspace. */
+int pr_mesh_weld_workspace_size(const pr_mesh_weld_t* s, size_t* bytes);
+/* `workspace`: 256-byte aligned, pr_mesh_weld_workspace_size bytes. */
+int pr_mesh_weld(const pr_mesh_weld_t* s, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Backward pass of pr_render_forward (what torch.autograd does for the reference's op graph when
  * training/trainer_backpropagated_autoencoder.py:349 calls total_loss.backward()).  The forward call must
  * have run with PR_FLAG_SAVE_FOR_BACKWARD (with or without PR_FLAG_TRAIN_BN) on the same `call`, `objects` and

@@ -280,6 +280,22 @@ AUDIT_COUNTS = 12                # columns of pr_mesh_audit_t.counts
 AUDIT_MEASURES = 8               # columns of pr_mesh_audit_t.measures
 
 
+class MeshWeld(C.Structure):
+    """pr_mesh_weld_t (include/playrender.h)."""
+    _fields_ = [("groups", C.c_int32), ("total_vertices", C.c_int32), ("total_triangles", C.c_int32), ("flags", C.c_uint32),
+                ("attribute_width", C.c_int32), ("max_vertices", C.c_int32), ("max_triangles", C.c_int32), ("reserved_", C.c_uint32),
+                ("vertices", C.c_void_p), ("normals", C.c_void_p), ("attributes", C.c_void_p), ("triangles", C.c_void_p),
+                ("vertex_offsets", C.c_void_p), ("triangle_offsets", C.c_void_p), ("out_vertices", C.c_void_p),
+                ("out_normals", C.c_void_p), ("out_attributes", C.c_void_p), ("out_triangles", C.c_void_p), ("vertex_map", C.c_void_p),
+                ("triangle_map", C.c_void_p), ("counts", C.c_void_p), ("out_vertex_offsets", C.c_void_p),
+                ("out_triangle_offsets", C.c_void_p)]
+
+
+WELD_COMPACT_ONLY = 1            # PR_WELD_COMPACT_ONLY
+WELD_COUNTS = 8                  # columns of pr_mesh_weld_t.counts
+WELD_MAX_ATTRIBUTE_WIDTH = 4096
+
+
 # every exported symbol of include/playrender.h : (restype, argtypes)
 class SceneSetup(C.Structure):
     """pr_scene_setup_t (include/playrender.h)."""
@@ -330,6 +346,8 @@ SYMBOLS = {
     "pr_inside_query": (C.c_int, [C.POINTER(Inside), C.c_void_p]),
     "pr_mesh_audit_workspace_size": (C.c_int, [C.POINTER(MeshAudit), C.POINTER(C.c_size_t)]),
     "pr_mesh_audit": (C.c_int, [C.POINTER(MeshAudit), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pr_mesh_weld_workspace_size": (C.c_int, [C.POINTER(MeshWeld), C.POINTER(C.c_size_t)]),
+    "pr_mesh_weld": (C.c_int, [C.POINTER(MeshWeld), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_backward_workspace_size": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(C.c_size_t)]),
     "pr_render_backward": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(OutputGrads), C.POINTER(OutputGrads),
                                      C.POINTER(InputGrads), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),

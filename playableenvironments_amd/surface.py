@@ -27,6 +27,9 @@ simplified (``keep_duplicates=True``).
 ``audit_meshes`` / ``Mesh.audit`` / ``RayGrid.audit`` (``pr_mesh_audit``) say how a mesh is made up - whether its directed edges balance
 by vertex value (what ``contains`` needs), boundary and non-manifold edges, Euler characteristic, shells, area, signed volume, centroid -
 and ``Mesh.keep_shells`` drops the fragments that a simplification detached.
+
+``weld_meshes`` / ``Mesh.welded`` / ``Mesh.compacted`` (``pr_mesh_weld``) merge the vertices with equal values into the lowest one and
+drop unreferenced vertices and dropped triangles: the mesh for readers that trust indices (``extract_surface(weld=True)``).
 """
 from __future__ import annotations
 
@@ -93,16 +96,33 @@ class Mesh:
         return other.closest(self.vertices, max_distance=max_distance).distance[0]
 
     def audit(self, labels: bool = False) -> "MeshAudit":
-        """How this one mesh is made up: ``audit_meshes([self], labels=labels)[0]``."""
+        """How this one mesh is made up: ``audit_meshes([self], labels=labels)[0]``.  A welded mesh (``welded``) answers
+        identically, except that it has no dropped triangles."""
         return audit_meshes([self], labels=labels)[0]
 
-    def keep_shells(self, n: int) -> "Mesh":
+    def welded(self, **kw):
+        """This one mesh with one vertex per value, no unreferenced vertex and no dropped triangle: ``weld_meshes([self], **kw)``,
+        the mesh itself - or, with ``maps=True``, the triple ``(mesh, vertex_map, triangle_map)``."""
+        if kw.get("maps"):
+            meshes, vertex_maps, triangle_maps = weld_meshes([self], **kw)
+            return meshes[0], vertex_maps[0], triangle_maps[0]
+        return weld_meshes([self], **kw)[0]
+
+    def compacted(self) -> "Mesh":
+        """This one mesh without its unreferenced vertices and its dropped triangles; no vertices are merged:
+        ``weld_meshes([self], merge=False)[0]``."""
+        return weld_meshes([self], merge=False)[0]
+
+    def keep_shells(self, n: int, compact: bool = False) -> "Mesh":
         """The mesh restricted to its ``n`` largest shells by triangle count (ties: the lower label first; ``MeshAudit.labels``):
         floater removal AFTER simplification, which can detach fragments that ``clean_lattice`` never saw.  Dropped triangles (an
         index out of range, a vertex that is not finite, ``a == b`` or ``a == c`` as values) belong to no shell and go.  The
         triangles that stay keep their order; vertices, normals and features are kept whole, as the simplifier keeps unreferenced
         vertices.  One audit, a ``bincount`` / ``topk`` over its labels and a boolean selection, which reads the number of kept
-        triangles back: ONE host synchronisation."""
+        triangles back: ONE host synchronisation.  ``compact=True``: the result then goes through ``compacted()``, which drops the
+        vertex, normal and feature rows that no kept triangle refers to (one more synchronisation; features come back as fp32)."""
+        if compact:
+            return self.keep_shells(n).compacted()
         try:
             n = operator.index(n)
         except TypeError:
@@ -696,7 +716,8 @@ class RayGrid:
         """Whether every point lies inside its group's mesh: bool ``(G, N)``, ``winding != 0``.  With ``any=True`` a triple: that,
         bool ``(N)`` - inside any group's mesh - and int64 ``(N)``, the lowest containing group or -1.  Meaningful for the meshes
         ``winding`` is meaningful for (capped with ``close_border=True``, duplicates kept when simplified); a point on the surface
-        may fall on either side.  ``RayGrid.audit`` checks the mesh in hand (``balanced``).  No host synchronisation."""
+        may fall on either side.  ``RayGrid.audit`` checks the mesh in hand (``balanced``).  A welded mesh (``weld_meshes``) answers
+        identically.  No host synchronisation."""
         inside = self.winding(points, axis=axis).winding != 0
         if not any:
             return inside
@@ -885,6 +906,129 @@ def audit_meshes(meshes: Sequence[Mesh], *, labels: bool = False) -> List[MeshAu
     return [MeshAudit(counts[g], measures[g], shell[to[g]:to[g + 1]] if labels else None) for g in range(len(meshes))]
 
 
+def weld_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offsets: torch.Tensor, triangle_offsets: torch.Tensor,
+                total_vertices: int, total_triangles: int, counts: torch.Tensor, out_vertex_offsets: torch.Tensor,
+                out_triangle_offsets: torch.Tensor, *, normals: Optional[torch.Tensor] = None,
+                attributes: Optional[torch.Tensor] = None, out_vertices: Optional[torch.Tensor] = None,
+                out_normals: Optional[torch.Tensor] = None, out_attributes: Optional[torch.Tensor] = None,
+                out_triangles: Optional[torch.Tensor] = None, vertex_map: Optional[torch.Tensor] = None,
+                triangle_map: Optional[torch.Tensor] = None, merge: bool = True) -> _lib.MeshWeld:
+    """``pr_mesh_weld_t`` over prepared tensors (fp32 / int32, contiguous, one device); the capacities are the outputs' rows and the
+    attribute width is the second dimension of ``attributes``."""
+    s = _lib.MeshWeld()
+    s.groups = vertex_offsets.numel() - 1
+    s.total_vertices = int(total_vertices)
+    s.total_triangles = int(total_triangles)
+    s.flags = 0 if merge else _lib.WELD_COMPACT_ONLY
+    s.attribute_width = 0 if attributes is None else attributes.size(1)
+    s.max_vertices = 0 if out_vertices is None else out_vertices.size(0)
+    s.max_triangles = 0 if out_triangles is None else out_triangles.size(0)
+    for name, t in (("vertices", vertices), ("normals", normals), ("attributes", attributes), ("triangles", triangles),
+                    ("vertex_offsets", vertex_offsets), ("triangle_offsets", triangle_offsets), ("out_vertices", out_vertices),
+                    ("out_normals", out_normals), ("out_attributes", out_attributes), ("out_triangles", out_triangles),
+                    ("vertex_map", vertex_map), ("triangle_map", triangle_map), ("counts", counts),
+                    ("out_vertex_offsets", out_vertex_offsets), ("out_triangle_offsets", out_triangle_offsets)):
+        setattr(s, name, None if t is None else t.data_ptr())
+    return s
+
+
+def _weld_packed(vertices, normals, attributes, triangles, vertex_offsets, triangle_offsets, merge: bool, maps: bool):
+    """``pr_mesh_weld`` on packed meshes (device tensors; ``vertex_offsets`` / ``triangle_offsets`` are host lists), on
+    ``_simplify_packed``'s route: a counting call, one read-back of the two offset arrays, an exactly sized emitting call.  Returns
+    ``(meshes, vertex_maps, triangle_maps)``; the maps are None without ``maps``."""
+    lib = _lib.load()
+    dev = vertices.device
+    G, V, T = len(vertex_offsets) - 1, vertex_offsets[-1], triangle_offsets[-1]
+    A = 0 if attributes is None else attributes.size(1)
+    if A == 0:
+        attributes = None
+    if vertices.size(0) == 0:                                      # (an empty tensor has no address: the library refuses NULL)
+        vertices = torch.empty((1, 3), dtype=torch.float32, device=dev)
+        normals = None if normals is None else torch.empty((1, 3), dtype=torch.float32, device=dev)
+        attributes = None if attributes is None else torch.empty((1, A), dtype=torch.float32, device=dev)
+    if triangles.size(0) == 0:
+        triangles = torch.empty((1, 3), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        offsets_in = torch.tensor([vertex_offsets, triangle_offsets], dtype=torch.int32).to(dev)
+        offsets = torch.empty((2, G + 1), dtype=torch.int32, device=dev)
+        counts = torch.empty((G, _lib.WELD_COUNTS), dtype=torch.int32, device=dev)
+        common = (vertices, triangles, offsets_in[0], offsets_in[1], V, T, counts, offsets[0], offsets[1])
+        count = weld_struct(*common, normals=normals, attributes=attributes, merge=merge)
+        size = C.c_size_t()
+        _lib.check(lib.pr_mesh_weld_workspace_size(C.byref(count), C.byref(size)), "pr_mesh_weld_workspace_size")
+        workspace = torch.empty(size.value, dtype=torch.uint8, device=dev)
+        _lib.check(lib.pr_mesh_weld(C.byref(count), workspace.data_ptr(), size.value, stream), "pr_mesh_weld")
+        out_vo, out_to = offsets.cpu().tolist()                             # (the host synchronisation)
+        out_v = torch.empty((out_vo[G], 3), dtype=torch.float32, device=dev)
+        out_n = None if normals is None else torch.empty((out_vo[G], 3), dtype=torch.float32, device=dev)
+        out_a = None if attributes is None else torch.empty((out_vo[G], A), dtype=torch.float32, device=dev)
+        out_t = torch.empty((out_to[G], 3), dtype=torch.int32, device=dev)
+        vmap = torch.full((V,), -1, dtype=torch.int32, device=dev) if maps else None
+        tmap = torch.full((T,), -1, dtype=torch.int32, device=dev) if maps else None
+        if out_vo[G] > 0 or (maps and V + T > 0):
+            some = out_vo[G] > 0                                    # (a kept triangle refers to three output vertices)
+            emit = weld_struct(*common, normals=normals, attributes=attributes, out_vertices=out_v if some else None,
+                               out_normals=out_n if some else None, out_attributes=out_a if some else None,
+                               out_triangles=out_t if some else None, vertex_map=vmap if maps and V > 0 else None,
+                               triangle_map=tmap if maps and T > 0 else None, merge=merge)
+            _lib.check(lib.pr_mesh_weld(C.byref(emit), workspace.data_ptr(), size.value, stream), "pr_mesh_weld")
+    meshes = [Mesh(out_v[out_vo[g]:out_vo[g + 1]], out_t[out_to[g]:out_to[g + 1]], None if out_n is None else out_n[out_vo[g]:out_vo[g + 1]],
+                   None if out_a is None else out_a[out_vo[g]:out_vo[g + 1]]) for g in range(G)]
+    if not maps:
+        return meshes, None, None
+    return (meshes, [vmap[vertex_offsets[g]:vertex_offsets[g + 1]] for g in range(G)],
+            [tmap[triangle_offsets[g]:triangle_offsets[g + 1]] for g in range(G)])
+
+
+def weld_meshes(meshes: Sequence[Mesh], *, merge: bool = True, maps: bool = False):
+    """The meshes welded and compacted (``pr_mesh_weld``, include/playrender.h): vertices of a mesh whose three components compare
+    equal become ONE vertex - the one with the lowest index, whose position, normal and feature rows are copied bit for bit; nothing
+    is averaged -, vertices that no kept triangle refers to go, and so do the triangles that ``audit_meshes`` counts as dropped (an
+    index out of range, a vertex that is not finite, ``a == b`` or ``a == c`` as values).  The kept triangles keep their order and
+    orientation.  In the result identity by index IS identity by value: what an OBJ viewer or an adjacency builder needs, while
+    ``RayGrid.contains`` and ``audit_meshes`` answer as on the input.  ``merge=False`` merges nothing and only drops the dead rows.
+
+    The meshes are packed as ``simplify_meshes`` packs them, counted, and - after reading the two offset arrays back, the ONE host
+    synchronisation - emitted into exactly sized tensors.  Returns one mesh per input; they have normals iff every input has them,
+    and ``features`` iff every input has them with one common width - carried as fp32 attribute rows, so the result's features
+    are fp32 whatever the input's dtype.  ``maps=True``: a triple ``(meshes, vertex_maps, triangle_maps)`` of lists, per mesh int32
+    ``(V)`` - the output index of every input vertex's representative, -1 if it is not finite or unreferenced - and int32 ``(T)`` -
+    the output index of every kept triangle, -1 for a dropped one.  There is no CPU fallback."""
+    meshes = list(meshes)
+    if not meshes:
+        raise ValueError("weld_meshes needs at least one mesh")
+    if not all(m.vertices.is_cuda and m.triangles.is_cuda for m in meshes):
+        raise RuntimeError(NO_CPU)
+    dev = meshes[0].vertices.device
+    for m in meshes:
+        if m.vertices.dim() != 2 or m.vertices.size(1) != 3 or m.triangles.dim() != 2 or m.triangles.size(1) != 3:
+            raise ValueError(f"a mesh has vertices (V, 3) and triangles (T, 3), got {list(m.vertices.shape)} / {list(m.triangles.shape)}")
+    with_normals = all(m.normals is not None for m in meshes)
+    with_features = all(m.features is not None and m.features.dim() == 2 for m in meshes) and \
+        len({m.features.size(1) for m in meshes}) == 1
+    if with_features and meshes[0].features.size(1) > _lib.WELD_MAX_ATTRIBUTE_WIDTH:
+        raise ValueError(f"features can be at most {_lib.WELD_MAX_ATTRIBUTE_WIDTH} wide, got {meshes[0].features.size(1)}")
+    pack = lambda parts, dtype, width=3: torch.cat([p.detach().to(device=dev, dtype=dtype).reshape(-1, width) for p in parts]).contiguous()
+    vertices = pack([m.vertices for m in meshes], torch.float32)
+    triangles = pack([m.triangles for m in meshes], torch.int32)
+    normals = pack([m.normals for m in meshes], torch.float32) if with_normals else None
+    if normals is not None and normals.size(0) != vertices.size(0):
+        raise ValueError("normals must have one row per vertex")
+    features = None
+    if with_features:
+        if any(m.features.size(0) != m.vertices.size(0) for m in meshes):
+            raise ValueError("features must have one row per vertex")
+        width = meshes[0].features.size(1)
+        features = pack([m.features for m in meshes], torch.float32, width) if width else None
+    vertex_offsets, triangle_offsets = [0], [0]
+    for m in meshes:
+        vertex_offsets.append(vertex_offsets[-1] + m.vertices.size(0))
+        triangle_offsets.append(triangle_offsets[-1] + m.triangles.size(0))
+    out, vmaps, tmaps = _weld_packed(vertices, normals, features, triangles, vertex_offsets, triangle_offsets, bool(merge), bool(maps))
+    return (out, vmaps, tmaps) if maps else out
+
+
 def bounding_grid(meshes: Sequence[Mesh], cells):
     """A grid of ``cells`` cells (one integer, or three) around the joint bounding box of the meshes' finite vertices, for
     ``RayGrid.build``: per axis ``cell = extent / (cells - 1/4)`` and ``origin = lowest - cell / 8`` - the box is widened by an eighth
@@ -916,7 +1060,8 @@ def bounding_grid(meshes: Sequence[Mesh], cells):
 
 
 def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float, *, normals: bool = True, keep_largest: int = 0,
-                    min_points: int = 0, close_border: bool = False, simplify: int = 0, keep_duplicates: bool = False) -> List[Mesh]:
+                    min_points: int = 0, close_border: bool = False, simplify: int = 0, keep_duplicates: bool = False,
+                    weld: bool = False) -> List[Mesh]:
     """Meshes of the level set ``sigma = level`` of ``sigma (G, nx, ny, nz)`` (device tensor, z fastest - what ``density_grid``
     returns); ``axes``: the coordinates of the lattice points along x, y, z (``nx``, ``ny``, ``nz`` values).  Returns G meshes.
 
@@ -931,7 +1076,10 @@ def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: fl
     ``k`` lattice steps (``lattice_cluster_grid``) - evaluate the field finely, keep a mesh of a coarser lattice's size.  Two more
     read-backs (the ends of the axes, the simplified sizes).  At 0 (the default) nothing changes.  ``keep_duplicates`` is
     ``simplify_meshes``'s: duplicate triangles stay, so that every directed edge keeps its partner - what ``RayGrid.winding`` /
-    ``contains`` need of a simplified mesh."""
+    ``contains`` need of a simplified mesh.
+
+    ``weld=True``: the meshes - after the simplification, if any - go through ``weld_meshes``: one vertex per value, no unreferenced
+    vertex, no dropped triangle.  One more read-back.  At False (the default) nothing changes."""
     if not sigma.is_cuda:
         raise RuntimeError(NO_CPU)
     if sigma.dim() != 4:
@@ -972,7 +1120,10 @@ def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: fl
             _lib.check(lib.pr_extract_surface(C.byref(emit), workspace.data_ptr(), size.value, stream), "pr_extract_surface")
     if simplify:
         grid = _cluster_grid(*lattice_cluster_grid(axes, simplify))
-        return _simplify_packed(vertices, vertex_normals, triangles, vertex_offsets, triangle_offsets, *grid, bool(keep_duplicates))
+        meshes = _simplify_packed(vertices, vertex_normals, triangles, vertex_offsets, triangle_offsets, *grid, bool(keep_duplicates))
+        return weld_meshes(meshes) if weld else meshes
+    if weld:
+        return _weld_packed(vertices, vertex_normals, None, triangles, vertex_offsets, triangle_offsets, True, False)[0]
     meshes = []
     for g in range(G):
         v0, v1, t0, t1 = vertex_offsets[g], vertex_offsets[g + 1], triangle_offsets[g], triangle_offsets[g + 1]
