@@ -1100,6 +1100,95 @@ int pr_mesh_weld_workspace_size(const pr_mesh_weld_t* s, size_t* bytes);
 int pr_mesh_weld(const pr_mesh_weld_t* s, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Smoothing of packed meshes: pr_mesh_smooth builds the vertex-to-triangle incidence lists, runs `steps` Laplacian / Taubin steps on
+ * them and returns the positions, the area-weighted vertex normals of the result, the lists as a CSR, a state word per vertex and the
+ * counts - the adjacency reader that pr_mesh_weld prepares meshes for.
+ *   Input: G meshes packed as pr_mesh_weld leaves them - vertices (V, 3) fp32, triangles (T, 3) int32 LOCAL to their group,
+ *     vertex_offsets (G + 1), triangle_offsets (G + 1), optional pinned (V) uint8, all on the device; total_vertices / total_triangles
+ *     are V and T as host values.  Offsets that leave [0, V] / [0, T] or decrease are clamped as pr_mesh_weld clamps them, never
+ *     followed.  Identity is by INDEX: the call is meant for WELDED meshes.  On an unwelded mesh coinciding vertices are different
+ *     vertices, every triangle fan is open, and the surface tears along the seams as soon as a vertex moves.
+ *   Definitions: a VALID triangle has three indices in [0, V_g), pairwise different as indices, and nine finite input coordinates;
+ *     every other triangle of the group is dropped and counted.  The INCIDENCE LIST of vertex v is the local indices of the valid
+ *     triangles with a corner at v in ascending order, k(v) its length.  The OTHERS of v in an incident triangle (a, b, c), as stored,
+ *     are (b, c) if v is a, (c, a) if v is b, (a, b) if v is c; the sequence q_1 .. q_2k of v lists these pairs triangle after triangle
+ *     in list order (the triangle umbrella: on a closed manifold every neighbour occurs twice, and the mean of q is the uniform
+ *     umbrella's).  A BORDER vertex has 1 <= k(v) <= max_degree and some vertex that occurs exactly once in q.  A vertex is MOVABLE if
+ *     its three input components are finite, 1 <= k(v) <= max_degree, pinned[v] == 0 (or pinned is NULL), and it is not a border vertex
+ *     while PR_SMOOTH_PIN_BORDER is set.
+ *   Step s = 0 .. steps - 1 has the factor f = lambda for even s and mu for odd s (Taubin: mu < -lambda < 0; plain Laplacian:
+ *     mu == lambda).  A movable vertex is updated per component in fp32, without contraction or fused multiply-add:
+ *       acc = q_1, then acc = acc + q_j for j = 2 .. 2k in that order; mean = acc / (float)(2k), correctly rounded;
+ *       p' = p + f * (mean - p).
+ *     All reads are of the positions before the step (Jacobi, two buffers).  Every other vertex keeps its three words bit for bit.
+ *   out_vertices (V, 3): the positions after the last step; a copy with steps == 0; the rows that no clamped group owns are copied too.
+ *   out_normals (V, 3), optional: for a vertex with 1 <= k <= max_degree, from the FINAL positions: per incident triangle in list order
+ *     n = (b - a) x (c - a) of its stored corners, every component one difference of two products (cyclic, as in pr_mesh_audit:
+ *     n0 = e1[1] e2[2] - e1[2] e2[1], ...); N is the first n, the others are added in order; length = sqrt((N0 N0 + N1 N1) + N2 N2),
+ *     correctly rounded; the row is N / length if length is finite and > 0, else three zeros, as the mesher writes them.  Three zeros
+ *     for every other vertex and for the rows that no clamped group owns.  A normal points from matter to empty space whenever the
+ *     triangles do.
+ *   incidence_offsets (V + 1) and incidence (3 T), optional, both or neither: the lists as a CSR.  The offsets are entries into
+ *     `incidence` over ALL groups, those of a group's vertices are consecutive, and a row that no clamped group owns repeats the running
+ *     total (0 in front of the first group, the total behind the last); incidence_offsets[V] is the total.  3 T entries are always room
+ *     enough, so there is no counting call; the entries at and behind the total are not written.
+ *   vertex_state (V) int32, optional: the sum of  1: k >= 1   2: border   4: pinned by the mask   8: k > max_degree   16: not finite
+ *     32: movable.  -1 in the rows that no clamped group owns.
+ *   counts (G, 8) int32, always and fully written:
+ *       [0] valid triangles        [1] dropped triangles        [2] movable vertices        [3] finite vertices with k = 0
+ *       [4] border vertices        [5] vertices with k > max_degree        [6] vertices that are not finite        [7] the largest k
+ *   Order: the positions in the lists are handed out by integer atomics, so the order of arrival is arbitrary; every list with
+ *     k <= max_degree is then sorted, no output depends on the arrival, and a second call gives equal bits everywhere - WITH ONE EXCEPTION: a list with k > max_degree
+ *     is not sorted.  Its segment of `incidence` holds the right SET of triangles in an unspecified order; its vertex is immovable, has
+ *     a zero normal and no border bit, and is counted in [5].
+ *   Bounded work: a lane sorts at most max_degree entries by insertion, at most 3 T max_degree comparisons in all, and the border
+ *     test reads at most max_degree^2 pairs of triangles; no lane waits for another.
+ *   Memory safety: every index read from the mesh or from the workspace is range-checked where it is read; rows that no clamped group
+ *     owns are only copied.  Hostile input may cost the correctness of the hostile group, never memory safety, and never another
+ *     group's rows.
+ * Workspace bytes = the sum of these regions, each rounded up to 256 bytes, with BV = ceil(V / 256) + G and BT = ceil(T / 256) + G
+ *   (upper bounds of the blocks of 256 vertices / triangles, none across two groups): 4 x 4 (G + 1) (per group: first vertex, first
+ *   triangle, first vertex block, first triangle block) + 4 V (counts k) + 4 (V + 1) (list offsets) + 4 V (cursors) + 12 T (list
+ *   entries) + 4 T (kept flags, with the list positions of the three corners) + 12 V (second position buffer) + 4 V (state) + 4 BV (list entries per vertex block) + 4 (BV + 1)
+ *   (their scan and the total) + 4 BT (valid triangles per triangle block) + 24 BV (per vertex block: movable, k = 0, border,
+ *   k > max_degree, not finite, largest k): 28 bytes per vertex, 16 per triangle.
+ * Nine kernel launches on `stream` with steps == 0, plus ONE per step, whatever the optional outputs; no memset, no memcpy, no
+ * allocation, no synchronisation: capturable into a HIP graph.  Integer atomics only, in the count and in the fill.
+ * Additive entry points: PR_ABI_VERSION is unchanged.  sizeof(pr_mesh_smooth_t) = 120.
+ * Refused (PR_ERR_INVALID, before any device work; by pr_mesh_smooth_workspace_size too, except the workspace itself): NULL vertices,
+ * triangles, offsets, out_vertices or counts, groups < 1, a negative total, unknown flag bits, steps outside 0 .. 4096, max_degree
+ * outside 1 .. 256, lambda or mu not finite, exactly one of incidence_offsets / incidence, out_vertices == vertices, 3 T + 256 G or
+ * V + 256 G at or above 2^31 (the list entries and the block counts are int32); by the call only, and last: a NULL, misaligned or too
+ * small workspace.
+ */
+#define PR_SMOOTH_PIN_BORDER 1u
+typedef struct pr_mesh_smooth_t {
+    int32_t groups;                       /* G >= 1 */
+    int32_t total_vertices;               /* V, as a host value, >= 0 */
+    int32_t total_triangles;              /* T, as a host value, >= 0 */
+    uint32_t flags;                       /* PR_SMOOTH_PIN_BORDER or 0 */
+    int32_t steps;                        /* 0 .. 4096 */
+    int32_t max_degree;                   /* 1 .. 256 */
+    float lambda;                         /* factor of the even steps, finite */
+    float mu;                             /* factor of the odd steps, finite */
+    const float* vertices;                /* (V, 3) */
+    const int32_t* triangles;             /* (T, 3), indices local to the group */
+    const int32_t* vertex_offsets;        /* (G + 1) */
+    const int32_t* triangle_offsets;      /* (G + 1) */
+    const uint8_t* pinned;                /* (V) or NULL; != 0: the vertex does not move */
+    float* out_vertices;                  /* (V, 3), always written; not `vertices` */
+    float* out_normals;                   /* (V, 3) or NULL */
+    int32_t* incidence_offsets;           /* (V + 1) or NULL; with incidence */
+    int32_t* incidence;                   /* (3 T) or NULL; with incidence_offsets */
+    int32_t* vertex_state;                /* (V) or NULL */
+    int32_t* counts;                      /* (G, 8), always written */
+} pr_mesh_smooth_t;
+/* Host computation, no device work; refuses everything above that does not concern the workspace. */
+int pr_mesh_smooth_workspace_size(const pr_mesh_smooth_t* s, size_t* bytes);
+/* `workspace`: 256-byte aligned, pr_mesh_smooth_workspace_size bytes. */
+int pr_mesh_smooth(const pr_mesh_smooth_t* s, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Backward pass of pr_render_forward (what torch.autograd does for the reference's op graph when
  * training/trainer_backpropagated_autoencoder.py:349 calls total_loss.backward()).  The forward call must
  * have run with PR_FLAG_SAVE_FOR_BACKWARD (with or without PR_FLAG_TRAIN_BN) on the same `call`, `objects` and

@@ -296,6 +296,21 @@ WELD_COUNTS = 8                  # columns of pr_mesh_weld_t.counts
 WELD_MAX_ATTRIBUTE_WIDTH = 4096
 
 
+class MeshSmooth(C.Structure):
+    """pr_mesh_smooth_t (include/playrender.h)."""
+    _fields_ = [("groups", C.c_int32), ("total_vertices", C.c_int32), ("total_triangles", C.c_int32), ("flags", C.c_uint32),
+                ("steps", C.c_int32), ("max_degree", C.c_int32), ("lambda_", C.c_float), ("mu", C.c_float),
+                ("vertices", C.c_void_p), ("triangles", C.c_void_p), ("vertex_offsets", C.c_void_p), ("triangle_offsets", C.c_void_p),
+                ("pinned", C.c_void_p), ("out_vertices", C.c_void_p), ("out_normals", C.c_void_p), ("incidence_offsets", C.c_void_p),
+                ("incidence", C.c_void_p), ("vertex_state", C.c_void_p), ("counts", C.c_void_p)]
+
+
+SMOOTH_PIN_BORDER = 1            # PR_SMOOTH_PIN_BORDER
+SMOOTH_COUNTS = 8                # columns of pr_mesh_smooth_t.counts
+SMOOTH_MAX_STEPS = 4096
+SMOOTH_MAX_DEGREE = 256
+
+
 # every exported symbol of include/playrender.h : (restype, argtypes)
 class SceneSetup(C.Structure):
     """pr_scene_setup_t (include/playrender.h)."""
@@ -348,6 +363,8 @@ SYMBOLS = {
     "pr_mesh_audit": (C.c_int, [C.POINTER(MeshAudit), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_mesh_weld_workspace_size": (C.c_int, [C.POINTER(MeshWeld), C.POINTER(C.c_size_t)]),
     "pr_mesh_weld": (C.c_int, [C.POINTER(MeshWeld), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pr_mesh_smooth_workspace_size": (C.c_int, [C.POINTER(MeshSmooth), C.POINTER(C.c_size_t)]),
+    "pr_mesh_smooth": (C.c_int, [C.POINTER(MeshSmooth), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_backward_workspace_size": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(C.c_size_t)]),
     "pr_render_backward": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(OutputGrads), C.POINTER(OutputGrads),
                                      C.POINTER(InputGrads), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),

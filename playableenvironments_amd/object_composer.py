@@ -950,7 +950,7 @@ class ObjectComposer(Tracked, nn.Module):
     def extract_mesh(self, object_idx: int, resolution, style: torch.Tensor, deformation: torch.Tensor, *, level: float,
                      fine: bool = False, canonical_pose: bool = False, normals: bool = True, features: bool = False,
                      keep_largest: int = 0, min_points: int = 0, close_border: bool = False, stride: int = 0, guard: int = 1,
-                     simplify: int = 0, keep_duplicates: bool = False, weld: bool = False):
+                     simplify: int = 0, keep_duplicates: bool = False, weld: bool = False, smooth: int = 0):
         """Triangle meshes of the density field of object ``object_idx`` in its OBJECT frame: ``density_grid`` at the composer's
         ``precision``, then ``surface.extract_surface`` (marching tetrahedra on the device) on the lattice of voxel centres.  One
         ``surface.Mesh`` per row of ``style (G, S)`` / ``deformation (G, D)``.
@@ -975,7 +975,13 @@ class ObjectComposer(Tracked, nn.Module):
 
         ``weld=True``: ``surface.extract_surface``'s - the meshes are welded (``surface.weld_meshes``: one vertex per value, no
         unreferenced vertex, no dropped triangle) after the simplification and BEFORE the feature query, so ``features`` are
-        queried at the welded vertices.  At False (the default) nothing changes."""
+        queried at the welded vertices.  At False (the default) nothing changes.
+
+        ``smooth = n >= 1``: ``surface.extract_surface``'s - implies ``weld=True``; the welded meshes get ``n`` Taubin iterations
+        (``surface.smooth_meshes``) and normals recomputed from the smoothed triangles, after the simplification and the weld and
+        BEFORE the feature query, so ``features`` are queried at the smoothed vertices (a smoothing step moves a vertex to a convex
+        combination of its neighbours and back by less, so they stay inside the box for the default factors).  At 0 (the default)
+        nothing changes."""
         if stride:
             sigma = self.density_band(object_idx, resolution, style, deformation, level=level, stride=stride, guard=guard, fine=fine,
                                       canonical_pose=canonical_pose)[0]
@@ -984,7 +990,7 @@ class ObjectComposer(Tracked, nn.Module):
         axes = self._grid_axes(object_idx, list(sigma.shape[1:]), fine, sigma.device)
         meshes = _surface.extract_surface(sigma, axes, level, normals=normals, keep_largest=keep_largest, min_points=min_points,
                                           close_border=close_border, simplify=simplify, keep_duplicates=keep_duplicates,
-                                          weld=weld)
+                                          weld=weld, smooth=smooth)
         if features:
             # one query: the groups padded to the largest one (at least one row) with a lattice point, which is inside the box
             G, most = len(meshes), max(1, max(m.vertices.size(0) for m in meshes))

@@ -30,6 +30,10 @@ and ``Mesh.keep_shells`` drops the fragments that a simplification detached.
 
 ``weld_meshes`` / ``Mesh.welded`` / ``Mesh.compacted`` (``pr_mesh_weld``) merge the vertices with equal values into the lowest one and
 drop unreferenced vertices and dropped triangles: the mesh for readers that trust indices (``extract_surface(weld=True)``).
+
+``smooth_meshes`` / ``Mesh.smoothed`` / ``Mesh.vertex_normals`` / ``Mesh.incidence`` (``pr_mesh_smooth``) are that reader: vertex-to-
+triangle incidence lists, Laplacian / Taubin smoothing on them and area-weighted vertex normals of the result, deterministic bit for
+bit (``extract_surface(smooth=n)``).
 """
 from __future__ import annotations
 
@@ -112,6 +116,35 @@ class Mesh:
         """This one mesh without its unreferenced vertices and its dropped triangles; no vertices are merged:
         ``weld_meshes([self], merge=False)[0]``."""
         return weld_meshes([self], merge=False)[0]
+
+    def smoothed(self, **kw):
+        """This one mesh after Taubin smoothing: ``smooth_meshes([self], **kw)``, the mesh itself - or, with ``report=True``, the
+        triple ``(mesh, counts, state)``.  Welds first unless ``weld=False``."""
+        if kw.get("report"):
+            meshes, counts, states = smooth_meshes([self], **kw)
+            return meshes[0], counts[0], states[0]
+        return smooth_meshes([self], **kw)[0]
+
+    def vertex_normals(self, **kw) -> "Mesh":
+        """The same vertices, triangles and features with the normals recomputed from the triangles - area-weighted, pointing where the
+        triangles point: ``smooth_meshes`` with no step and no weld.  What a mesh wants after ``simplified``, whose normals are still
+        the lattice gradients at the representatives' old positions.  Identity is by index: a vertex of an unwelded mesh gets the
+        normal of its own triangles only.  ``max_degree`` is ``smooth_meshes``'s."""
+        return smooth_meshes([self], iterations=0, weld=False, normals=True, **kw)[0]
+
+    def incidence(self, max_degree: int = 64):
+        """The vertex-to-triangle incidence lists of this mesh as a CSR: ``(offsets (V + 1), triangles)`` int32 - the valid triangles
+        (three different indices in range, nine finite coordinates) with a corner at vertex ``v`` are
+        ``triangles[offsets[v]:offsets[v + 1]]``, ascending (a list longer than ``max_degree`` holds the right set in an unspecified
+        order).  ``triangles`` has room for ``3 T`` entries, of which ``offsets[V]`` are written; nothing is read back."""
+        if not (self.vertices.is_cuda and self.triangles.is_cuda):
+            raise RuntimeError(NO_CPU)
+        _, _, _, max_degree = _smooth_arguments(0, 0.0, None, max_degree)
+        V, T = self.vertices.size(0), self.triangles.size(0)
+        out = _smooth_packed(self.vertices.detach().to(torch.float32).reshape(-1, 3).contiguous(),
+                             self.triangles.detach().to(torch.int32).reshape(-1, 3).contiguous(), [0, V], [0, T], steps=0, lam=0.0,
+                             mu=0.0, max_degree=max_degree, pin_border=True, normals=False, incidence=True)
+        return out["incidence_offsets"], out["incidence"][:3 * T]
 
     def keep_shells(self, n: int, compact: bool = False) -> "Mesh":
         """The mesh restricted to its ``n`` largest shells by triangle count (ties: the lower label first; ``MeshAudit.labels``):
@@ -1029,6 +1062,150 @@ def weld_meshes(meshes: Sequence[Mesh], *, merge: bool = True, maps: bool = Fals
     return (out, vmaps, tmaps) if maps else out
 
 
+def smooth_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offsets: torch.Tensor, triangle_offsets: torch.Tensor,
+                  total_vertices: int, total_triangles: int, out_vertices: torch.Tensor, counts: torch.Tensor, *, steps: int = 0,
+                  lam: float = 0.5, mu: float = -0.53, max_degree: int = 64, pin_border: bool = True,
+                  pinned: Optional[torch.Tensor] = None, out_normals: Optional[torch.Tensor] = None,
+                  incidence_offsets: Optional[torch.Tensor] = None, incidence: Optional[torch.Tensor] = None,
+                  vertex_state: Optional[torch.Tensor] = None) -> _lib.MeshSmooth:
+    """``pr_mesh_smooth_t`` over prepared tensors (fp32 / int32 / uint8, contiguous, one device)."""
+    s = _lib.MeshSmooth()
+    s.groups = vertex_offsets.numel() - 1
+    s.total_vertices = int(total_vertices)
+    s.total_triangles = int(total_triangles)
+    s.flags = _lib.SMOOTH_PIN_BORDER if pin_border else 0
+    s.steps = int(steps)
+    s.max_degree = int(max_degree)
+    s.lambda_ = float(lam)
+    s.mu = float(mu)
+    for name, t in (("vertices", vertices), ("triangles", triangles), ("vertex_offsets", vertex_offsets),
+                    ("triangle_offsets", triangle_offsets), ("pinned", pinned), ("out_vertices", out_vertices),
+                    ("out_normals", out_normals), ("incidence_offsets", incidence_offsets), ("incidence", incidence),
+                    ("vertex_state", vertex_state), ("counts", counts)):
+        setattr(s, name, None if t is None else t.data_ptr())
+    return s
+
+
+def _smooth_packed(vertices, triangles, vertex_offsets, triangle_offsets, *, steps, lam, mu, max_degree, pin_border, pinned=None,
+                   normals=True, incidence=False, state=False):
+    """``pr_mesh_smooth`` on packed meshes (device tensors; the two offset arrays are host lists): ONE call into exactly sized
+    tensors - the sizes do not change - and no host synchronisation.  Returns a dict of the packed outputs."""
+    lib = _lib.load()
+    dev = vertices.device
+    G, V, T = len(vertex_offsets) - 1, vertex_offsets[-1], triangle_offsets[-1]
+    row = lambda n: max(n, 1)                                       # (an empty tensor has no address: the library refuses NULL)
+    if vertices.size(0) == 0:
+        vertices = torch.empty((1, 3), dtype=torch.float32, device=dev)
+    if triangles.size(0) == 0:
+        triangles = torch.empty((1, 3), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        offsets = torch.tensor([vertex_offsets, triangle_offsets], dtype=torch.int32).to(dev)
+        out = {"vertices": torch.empty((row(V), 3), dtype=torch.float32, device=dev),
+               "counts": torch.empty((G, _lib.SMOOTH_COUNTS), dtype=torch.int32, device=dev)}
+        if normals:
+            out["normals"] = torch.empty((row(V), 3), dtype=torch.float32, device=dev)
+        if incidence:
+            out["incidence_offsets"] = torch.empty(V + 1, dtype=torch.int32, device=dev)
+            out["incidence"] = torch.empty(row(3 * T), dtype=torch.int32, device=dev)
+        if state:
+            out["state"] = torch.empty(row(V), dtype=torch.int32, device=dev)
+        if pinned is not None and pinned.numel() == 0:
+            pinned = None
+        s = smooth_struct(vertices, triangles, offsets[0], offsets[1], V, T, out["vertices"], out["counts"], steps=steps, lam=lam, mu=mu,
+                          max_degree=max_degree, pin_border=pin_border, pinned=pinned, out_normals=out.get("normals"),
+                          incidence_offsets=out.get("incidence_offsets"), incidence=out.get("incidence"), vertex_state=out.get("state"))
+        size = C.c_size_t()
+        _lib.check(lib.pr_mesh_smooth_workspace_size(C.byref(s), C.byref(size)), "pr_mesh_smooth_workspace_size")
+        workspace = torch.empty(size.value, dtype=torch.uint8, device=dev)
+        _lib.check(lib.pr_mesh_smooth(C.byref(s), workspace.data_ptr(), size.value, stream), "pr_mesh_smooth")
+    for key in ("vertices", "normals", "state"):
+        if key in out:
+            out[key] = out[key][:V]
+    return out
+
+
+def _smooth_arguments(iterations, lam, mu, max_degree):
+    """``(steps, lam, mu, max_degree)`` checked as ``pr_mesh_smooth`` checks them, with the argument's own name in the message."""
+    try:
+        iterations, max_degree = operator.index(iterations), operator.index(max_degree)
+    except TypeError:
+        raise ValueError(f"iterations and max_degree must be integers, got {iterations!r} / {max_degree!r}") from None
+    steps = iterations if mu is None else 2 * iterations
+    if iterations < 0 or steps > _lib.SMOOTH_MAX_STEPS:
+        raise ValueError(f"iterations must give 0 .. {_lib.SMOOTH_MAX_STEPS} steps (two per iteration with mu), got {iterations}")
+    if not 1 <= max_degree <= _lib.SMOOTH_MAX_DEGREE:
+        raise ValueError(f"max_degree must be 1 .. {_lib.SMOOTH_MAX_DEGREE}, got {max_degree}")
+    lam = float(lam)
+    mu = lam if mu is None else float(mu)
+    if not (math.isfinite(lam) and math.isfinite(mu)):
+        raise ValueError(f"lam and mu must be finite, got {lam} / {mu}")
+    return steps, lam, mu, max_degree
+
+
+def smooth_meshes(meshes: Sequence[Mesh], *, iterations: int = 10, lam: float = 0.5, mu: Optional[float] = -0.53,
+                  pin_border: bool = True, pinned=None, weld: bool = True, normals: bool = True, max_degree: int = 64,
+                  report: bool = False):
+    """The meshes smoothed (``pr_mesh_smooth``, include/playrender.h): ``iterations`` Taubin iterations - a step with the factor
+    ``lam``, then one with ``mu`` (``mu < -lam < 0`` keeps the volume), ``steps = 2 * iterations`` - of the triangle umbrella on the
+    vertex-to-triangle incidence lists, deterministic bit for bit.  ``mu=None``: plain Laplacian smoothing, ``steps = iterations`` with
+    ``lam`` alone (the mesh shrinks).  Triangles are untouched, so the topology - and with it ``audit_meshes``' counts - stays.
+
+    Identity is by INDEX: with ``weld=True`` (the default) the meshes go through ``weld_meshes`` first - its read-back is the ONE host
+    synchronisation; ``weld=False`` is for meshes that are welded already and synchronises nothing (an unwelded mesh tears at its
+    coinciding vertices).  ``pin_border``: vertices on an open border stay.  ``pinned``: per mesh a ``(V)`` mask (or None) of vertices
+    that stay - rows of the mesh as smoothed, so with ``weld=True`` of the WELDED mesh.  Vertices with more than ``max_degree``
+    (1 .. 256) incident triangles stay and get a zero normal.  ``normals=True`` replaces the normals by the area-weighted normals of
+    the smoothed triangles (zero rows where a vertex has no valid triangle); at False the input's normals are carried.  Features
+    are carried row for row (vertex counts do not change after the weld).  Returns one mesh per input; ``report=True``: a triple
+    ``(meshes, counts, states)`` of lists with the ``(8)`` counts and the ``(V)`` state words of every mesh (header), still on the
+    device.  There is no CPU fallback."""
+    meshes = list(meshes)
+    if not meshes:
+        raise ValueError("smooth_meshes needs at least one mesh")
+    if not all(m.vertices.is_cuda and m.triangles.is_cuda for m in meshes):
+        raise RuntimeError(NO_CPU)
+    steps, lam, mu, max_degree = _smooth_arguments(iterations, lam, mu, max_degree)
+    for m in meshes:
+        if m.vertices.dim() != 2 or m.vertices.size(1) != 3 or m.triangles.dim() != 2 or m.triangles.size(1) != 3:
+            raise ValueError(f"a mesh has vertices (V, 3) and triangles (T, 3), got {list(m.vertices.shape)} / {list(m.triangles.shape)}")
+    if weld:
+        meshes = weld_meshes(meshes)
+    dev = meshes[0].vertices.device
+    pack = lambda parts, dtype: torch.cat([p.detach().to(device=dev, dtype=dtype).reshape(-1, 3) for p in parts]).contiguous()
+    vertices = pack([m.vertices for m in meshes], torch.float32)
+    triangles = pack([m.triangles for m in meshes], torch.int32)
+    vertex_offsets, triangle_offsets = [0], [0]
+    for m in meshes:
+        vertex_offsets.append(vertex_offsets[-1] + m.vertices.size(0))
+        triangle_offsets.append(triangle_offsets[-1] + m.triangles.size(0))
+    mask = None
+    if pinned is not None:
+        pinned = list(pinned)
+        if len(pinned) != len(meshes):
+            raise ValueError(f"pinned must hold one mask (or None) per mesh, got {len(pinned)} for {len(meshes)} meshes")
+        parts = []
+        for m, p in zip(meshes, pinned):
+            if p is None:
+                parts.append(torch.zeros(m.vertices.size(0), dtype=torch.uint8, device=dev))
+                continue
+            if p.numel() != m.vertices.size(0):
+                raise ValueError(f"a pinned mask must have one entry per vertex of the mesh as it is smoothed ({m.vertices.size(0)}), "
+                                 f"got {p.numel()}")
+            parts.append((p.detach().to(dev).reshape(-1) != 0).to(torch.uint8))
+        mask = torch.cat(parts).contiguous()
+    out = _smooth_packed(vertices, triangles, vertex_offsets, triangle_offsets, steps=steps, lam=lam, mu=mu, max_degree=max_degree,
+                         pin_border=bool(pin_border), pinned=mask, normals=bool(normals), state=bool(report))
+    result = []
+    for g, m in enumerate(meshes):
+        v0, v1 = vertex_offsets[g], vertex_offsets[g + 1]
+        result.append(Mesh(out["vertices"][v0:v1], m.triangles, out["normals"][v0:v1] if normals else m.normals, m.features))
+    if not report:
+        return result
+    return (result, [out["counts"][g] for g in range(len(meshes))],
+            [out["state"][vertex_offsets[g]:vertex_offsets[g + 1]] for g in range(len(meshes))])
+
+
 def bounding_grid(meshes: Sequence[Mesh], cells):
     """A grid of ``cells`` cells (one integer, or three) around the joint bounding box of the meshes' finite vertices, for
     ``RayGrid.build``: per axis ``cell = extent / (cells - 1/4)`` and ``origin = lowest - cell / 8`` - the box is widened by an eighth
@@ -1061,7 +1238,7 @@ def bounding_grid(meshes: Sequence[Mesh], cells):
 
 def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float, *, normals: bool = True, keep_largest: int = 0,
                     min_points: int = 0, close_border: bool = False, simplify: int = 0, keep_duplicates: bool = False,
-                    weld: bool = False) -> List[Mesh]:
+                    weld: bool = False, smooth: int = 0) -> List[Mesh]:
     """Meshes of the level set ``sigma = level`` of ``sigma (G, nx, ny, nz)`` (device tensor, z fastest - what ``density_grid``
     returns); ``axes``: the coordinates of the lattice points along x, y, z (``nx``, ``ny``, ``nz`` values).  Returns G meshes.
 
@@ -1079,7 +1256,11 @@ def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: fl
     ``contains`` need of a simplified mesh.
 
     ``weld=True``: the meshes - after the simplification, if any - go through ``weld_meshes``: one vertex per value, no unreferenced
-    vertex, no dropped triangle.  One more read-back.  At False (the default) nothing changes."""
+    vertex, no dropped triangle.  One more read-back.  At False (the default) nothing changes.
+
+    ``smooth = n >= 1``: implies ``weld=True``; the welded meshes then go through ``smooth_meshes(iterations=n, weld=False)`` - ``n``
+    Taubin iterations at the default factors, borders pinned, normals recomputed from the smoothed triangles when ``normals`` is set.
+    No further read-back.  At 0 (the default) nothing changes."""
     if not sigma.is_cuda:
         raise RuntimeError(NO_CPU)
     if sigma.dim() != 4:
@@ -1092,6 +1273,16 @@ def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: fl
         raise ValueError(f"simplify must be an integer >= 0, got {simplify!r}") from None
     if simplify < 0:
         raise ValueError(f"simplify must be an integer >= 0, got {simplify}")
+    try:
+        smooth = operator.index(smooth)
+    except TypeError:
+        raise ValueError(f"smooth must be an integer >= 0, got {smooth!r}") from None
+    if smooth < 0 or 2 * smooth > _lib.SMOOTH_MAX_STEPS:
+        raise ValueError(f"smooth must be an integer in 0 .. {_lib.SMOOTH_MAX_STEPS // 2}, got {smooth}")
+    if smooth:
+        meshes = extract_surface(sigma, axes, level, normals=normals, keep_largest=keep_largest, min_points=min_points,
+                                 close_border=close_border, simplify=simplify, keep_duplicates=keep_duplicates, weld=True)
+        return smooth_meshes(meshes, iterations=smooth, weld=False, normals=bool(normals))
     dev = sigma.device
     sigma = sigma.detach().to(torch.float32).contiguous()
     if keep_largest or min_points or close_border:
