@@ -1189,6 +1189,92 @@ int pr_mesh_smooth_workspace_size(const pr_mesh_smooth_t* s, size_t* bytes);
 int pr_mesh_smooth(const pr_mesh_smooth_t* s, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Area-weighted point samples of packed meshes: pr_mesh_sample draws `samples` points per group with probability proportional to
+ * triangle area and carries the per-vertex rows (normals, attribute columns) to them - what a surface integral such as the deviation
+ * of one mesh from another, or a point cloud with features, is made from.  Everything below is chosen so that NO output depends on
+ * the execution order; a restatement in numpy and Python integers reproduces every bit (tests/sample_reference.py).
+ *   Input: G meshes packed as pr_mesh_weld leaves them - vertices (V, 3) fp32, triangles (T, 3) int32 LOCAL to their group,
+ *     vertex_offsets (G + 1), triangle_offsets (G + 1), optional normals (V, 3) fp32, optional attributes (V, C) fp32 with
+ *     C = attribute_width, 1 <= C <= 4096 (ignored when attributes is NULL), all on the device; total_vertices / total_triangles are V
+ *     and T as host values.  Offsets that leave [0, V] / [0, T] or decrease are clamped as pr_mesh_weld and pr_mesh_smooth clamp them,
+ *     never followed.  Host values: samples = n per group, n >= 0, G n < 2^31; seed; first_sample; flags.
+ *   Definitions: a VALID triangle has three indices in [0, V_g), pairwise different as indices, and nine finite coordinates
+ *     (pr_mesh_smooth's definition); every other triangle of the group is dropped and counted.  The AREA of a valid triangle is
+ *     pr_mesh_audit's, in fp64 without contraction: the corners converted to double, e1 = b - a, e2 = c - a, every component of the
+ *     cross product one difference of two products (n0 = e1[1] e2[2] - e1[2] e2[1], cyclic), area = 0.5 sqrt((n0 n0 + n1 n1) + n2 n2),
+ *     correctly rounded.  A_max(g) is the largest area of the group (a maximum is exact).  The WEIGHT of a valid triangle is
+ *     w_t = (uint64) floor((area_t / A_max) * 2^32) with the correctly rounded fp64 quotient (the scaling is exact); a dropped triangle
+ *     has w = 0.  A valid triangle smaller than A_max * 2^-32 therefore has weight 0 too and is NEVER DRAWN; counts[2] says how many
+ *     there are.  W_t is the inclusive prefix sum of w within the group in uint64 and W(g) its last value (T < 2^31 and w <= 2^32:
+ *     nothing overflows; integer sums are the same in any order).  A group with no valid triangle or with A_max == 0 is EMPTY.
+ *   Sample i of group g has the stream index j = first_sample + i modulo 2^64 and the draw
+ *       x[0..3] = philox4x32_10(counter = (low32(j), high32(j), g, 0), key = (low32(k), high32(k))),  k = splitmix64 finaliser of seed
+ *     (the generator and the key mix of the renderer's noise streams, pr_noise_fill).  So samples [a, b) of one call are samples
+ *     [0, b - a) of a call with first_sample advanced by a, and calls with disjoint index ranges draw disjoint streams.
+ *     Triangle: r = x[0] | (uint64) x[1] << 32, pick = floor(r W(g) / 2^64), t = the first triangle with W_t > pick: probability
+ *     w_t / W(g) to within 2^-63 absolute.  Barycentrics: U = x[2] >> 8, V = x[3] >> 8; if U + V > 2^24 (as integers) then
+ *     U = 2^24 - U and V = 2^24 - V; b1 = U 2^-24, b2 = V 2^-24, b0 = (2^24 - U - V) 2^-24, all exact in fp32.
+ *     Point formula, per component in fp32 without contraction or fused multiply-add, a, b, c being the rows of the stored corners in
+ *     stored order:  p = ((b0 * a) + (b1 * b)) + (b2 * c).
+ *   Outputs; the samples of an empty group get triangle -1 and zeros everywhere else:
+ *     points (G, n, 3), always written: the point formula on the corner positions.
+ *     triangle (G, n) int32, optional: t, local to the group.
+ *     barycentric (G, n, 2), optional: (b1, b2) - pr_closest_query's (v, w): the point is a + v (b - a) + w (c - a).
+ *     out_normals (G, n, 3), optional.  Without PR_SAMPLE_FACE_NORMALS it needs `normals`: N = the point formula on the three corner
+ *       rows, length = sqrt((N0 N0 + N1 N1) + N2 N2) correctly rounded, the row is N / length if length is finite and > 0, else three
+ *       zeros.  With PR_SAMPLE_FACE_NORMALS: N = (b - a) x (c - a) of the stored corner positions in fp32 with pr_mesh_smooth's
+ *       component formula, normalised the same way; `normals` is ignored.
+ *     out_attributes (G, n, C), optional, needs `attributes`: every column through the point formula.
+ *     counts (G, 4) int32, always and fully written:
+ *       [0] valid triangles    [1] dropped triangles    [2] valid triangles with weight 0    [3] samples drawn: n, 0 for an empty group
+ *     measures (G, 2) fp64, always written: [0] A_max, [1] ((double) W(g) * A_max) * 2^-32 - the area the sampler distributes over, a
+ *       repeatable stand-in for pr_mesh_audit's area, below it by less than 2^-32 A_max per valid triangle; both 0 for an empty group.
+ *   Memory safety: every index read from the mesh or from the workspace is range-checked where it is read; rows that no clamped group
+ *     owns are never touched.  Hostile input may cost the correctness of the hostile group, never memory safety, and never another
+ *     group's outputs.
+ * Workspace bytes = the sum of these regions, each rounded up to 256 bytes, with BT = ceil(T / 256) + G (an upper bound of the blocks of
+ *   256 triangles, none across two groups): 3 x 4 (G + 1) (per group: first vertex, first triangle, first triangle block) + 8 T (the
+ *   area, then W_t) + 8 BT (block maxima) + 4 BT + 4 BT (valid / weight-0 triangles per block) + 8 BT + 8 BT (block weight sums and
+ *   their scan) + 8 G + 8 G (A_max, W) + 16 G n (per sample: triangle, U, V).
+ * Seven kernel launches on `stream`, EIGHT with out_attributes, whatever else is asked for and also with n == 0; no memset, no memcpy,
+ * no allocation, no synchronisation: capturable into a HIP graph.  No atomics; no lane waits for another.
+ * Additive entry points: PR_ABI_VERSION is unchanged.  sizeof(pr_mesh_sample_t) = 144.
+ * Refused (PR_ERR_INVALID, before any device work; by pr_mesh_sample_workspace_size too, except the workspace itself): NULL vertices,
+ * triangles, offsets, points, counts or measures, groups < 1, a negative total, unknown flag bits, samples < 0, G * samples at or above
+ * 2^31, out_attributes without attributes, attribute_width outside 1 .. 4096 when attributes is given, out_normals with neither
+ * normals nor PR_SAMPLE_FACE_NORMALS, T + 256 G at or above 2^31 (the block counts are int32), an output pointer equal to an input
+ * pointer; by the call only, and last: a NULL, misaligned or too small workspace.
+ */
+#define PR_SAMPLE_FACE_NORMALS 1u
+typedef struct pr_mesh_sample_t {
+    int32_t groups;                       /* G >= 1 */
+    int32_t total_vertices;               /* V, as a host value, >= 0 */
+    int32_t total_triangles;              /* T, as a host value, >= 0 */
+    uint32_t flags;                       /* PR_SAMPLE_FACE_NORMALS or 0 */
+    int32_t samples;                      /* n per group, >= 0, G n < 2^31 */
+    int32_t attribute_width;              /* C, 1 .. 4096 with attributes */
+    uint64_t seed;                        /* the stream's seed */
+    uint64_t first_sample;                /* stream index of sample 0 of every group */
+    const float* vertices;                /* (V, 3) */
+    const int32_t* triangles;             /* (T, 3), indices local to the group */
+    const int32_t* vertex_offsets;        /* (G + 1) */
+    const int32_t* triangle_offsets;      /* (G + 1) */
+    const float* normals;                 /* (V, 3) or NULL */
+    const float* attributes;              /* (V, C) or NULL */
+    float* points;                        /* (G, n, 3), always written */
+    int32_t* triangle;                    /* (G, n) or NULL */
+    float* barycentric;                   /* (G, n, 2) or NULL */
+    float* out_normals;                   /* (G, n, 3) or NULL */
+    float* out_attributes;                /* (G, n, C) or NULL; needs attributes */
+    int32_t* counts;                      /* (G, 4), always written */
+    double* measures;                     /* (G, 2), always written */
+} pr_mesh_sample_t;
+/* Host computation, no device work; refuses everything above that does not concern the workspace. */
+int pr_mesh_sample_workspace_size(const pr_mesh_sample_t* s, size_t* bytes);
+/* `workspace`: 256-byte aligned, pr_mesh_sample_workspace_size bytes. */
+int pr_mesh_sample(const pr_mesh_sample_t* s, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Backward pass of pr_render_forward (what torch.autograd does for the reference's op graph when
  * training/trainer_backpropagated_autoencoder.py:349 calls total_loss.backward()).  The forward call must
  * have run with PR_FLAG_SAVE_FOR_BACKWARD (with or without PR_FLAG_TRAIN_BN) on the same `call`, `objects` and

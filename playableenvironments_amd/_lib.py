@@ -311,6 +311,22 @@ SMOOTH_MAX_STEPS = 4096
 SMOOTH_MAX_DEGREE = 256
 
 
+class MeshSample(C.Structure):
+    """pr_mesh_sample_t (include/playrender.h)."""
+    _fields_ = [("groups", C.c_int32), ("total_vertices", C.c_int32), ("total_triangles", C.c_int32), ("flags", C.c_uint32),
+                ("samples", C.c_int32), ("attribute_width", C.c_int32), ("seed", C.c_uint64), ("first_sample", C.c_uint64),
+                ("vertices", C.c_void_p), ("triangles", C.c_void_p), ("vertex_offsets", C.c_void_p), ("triangle_offsets", C.c_void_p),
+                ("normals", C.c_void_p), ("attributes", C.c_void_p), ("points", C.c_void_p), ("triangle", C.c_void_p),
+                ("barycentric", C.c_void_p), ("out_normals", C.c_void_p), ("out_attributes", C.c_void_p), ("counts", C.c_void_p),
+                ("measures", C.c_void_p)]
+
+
+SAMPLE_FACE_NORMALS = 1          # PR_SAMPLE_FACE_NORMALS
+SAMPLE_COUNTS = 4                # columns of pr_mesh_sample_t.counts
+SAMPLE_MEASURES = 2              # columns of pr_mesh_sample_t.measures
+SAMPLE_MAX_ATTRIBUTE_WIDTH = 4096
+
+
 # every exported symbol of include/playrender.h : (restype, argtypes)
 class SceneSetup(C.Structure):
     """pr_scene_setup_t (include/playrender.h)."""
@@ -365,6 +381,8 @@ SYMBOLS = {
     "pr_mesh_weld": (C.c_int, [C.POINTER(MeshWeld), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_mesh_smooth_workspace_size": (C.c_int, [C.POINTER(MeshSmooth), C.POINTER(C.c_size_t)]),
     "pr_mesh_smooth": (C.c_int, [C.POINTER(MeshSmooth), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pr_mesh_sample_workspace_size": (C.c_int, [C.POINTER(MeshSample), C.POINTER(C.c_size_t)]),
+    "pr_mesh_sample": (C.c_int, [C.POINTER(MeshSample), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_backward_workspace_size": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(C.c_size_t)]),
     "pr_render_backward": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(OutputGrads), C.POINTER(OutputGrads),
                                      C.POINTER(InputGrads), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),

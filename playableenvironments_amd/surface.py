@@ -34,6 +34,11 @@ drop unreferenced vertices and dropped triangles: the mesh for readers that trus
 ``smooth_meshes`` / ``Mesh.smoothed`` / ``Mesh.vertex_normals`` / ``Mesh.incidence`` (``pr_mesh_smooth``) are that reader: vertex-to-
 triangle incidence lists, Laplacian / Taubin smoothing on them and area-weighted vertex normals of the result, deterministic bit for
 bit (``extract_surface(smooth=n)``).
+
+``sample_meshes`` / ``Mesh.sample`` / ``RayGrid.sample`` (``pr_mesh_sample``) draw points on the surfaces with probability proportional
+to area - repeatable bit for bit from a seed, with normals and feature rows carried to the points - and ``compare_meshes`` measures
+with them how far one mesh lies from another as a surface integral (mean, rms, max, Chamfer distance, F-score), where
+``Mesh.distance_to`` looks from the vertices only.
 """
 from __future__ import annotations
 
@@ -131,6 +136,10 @@ class Mesh:
         the lattice gradients at the representatives' old positions.  Identity is by index: a vertex of an unwelded mesh gets the
         normal of its own triangles only.  ``max_degree`` is ``smooth_meshes``'s."""
         return smooth_meshes([self], iterations=0, weld=False, normals=True, **kw)[0]
+
+    def sample(self, n: int, *, seed: int, **kw) -> "SurfaceSamples":
+        """``n`` points on this one mesh, drawn with probability proportional to area: ``sample_meshes([self], n, seed=seed, **kw)[0]``."""
+        return sample_meshes([self], n, seed=seed, **kw)[0]
 
     def incidence(self, max_degree: int = 64):
         """The vertex-to-triangle incidence lists of this mesh as a CSR: ``(offsets (V + 1), triangles)`` int32 - the valid triangles
@@ -637,6 +646,20 @@ class RayGrid:
         if labels:
             to = getattr(self, "host_triangle_offsets", None) or self.triangle_offsets.cpu().tolist()
         return [MeshAudit(counts[g], measures[g], shell[to[g]:to[g + 1]] if labels else None) for g in range(self.groups)]
+
+    def sample(self, n: int, *, seed: int, first: int = 0, normals: Optional[str] = "face") -> List["SurfaceSamples"]:
+        """``n`` points on each of the meshes this grid holds, drawn with probability proportional to area (``pr_mesh_sample`` on the
+        packed arrays, one ``SurfaceSamples`` per group; ``sample_meshes`` states the rule) - e.g. points to ``cast`` from or to test
+        with ``contains``.  The grid holds positions only: ``normals`` is ``"face"`` or None.  One call on the current stream, no host
+        synchronisation."""
+        if normals not in ("face", None):
+            raise ValueError(f"a RayGrid holds no vertex normals: normals must be 'face' or None, got {normals!r}")
+        n, seed, first = _sample_arguments(n, seed, first, self.groups)
+        if not self.vertices.is_cuda:
+            raise RuntimeError(NO_CPU)
+        out = _sample_packed(self.vertices, self.triangles, self.vertex_offsets, self.triangle_offsets, self.total_vertices,
+                             self.total_triangles, n, seed, first, face=normals == "face")
+        return _surface_samples(out, self.groups)
 
     def cast(self, origins: torch.Tensor, directions: torch.Tensor, *, t_min: float = 0.0, t_max: float = math.inf,
              cull_back: bool = False, barycentric: bool = False, nearest: bool = False) -> RayHits:
@@ -1204,6 +1227,279 @@ def smooth_meshes(meshes: Sequence[Mesh], *, iterations: int = 10, lam: float = 
         return result
     return (result, [out["counts"][g] for g in range(len(meshes))],
             [out["state"][vertex_offsets[g]:vertex_offsets[g + 1]] for g in range(len(meshes))])
+
+
+def sample_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offsets: torch.Tensor, triangle_offsets: torch.Tensor,
+                  total_vertices: int, total_triangles: int, samples: int, seed: int, points: torch.Tensor, counts: torch.Tensor,
+                  measures: torch.Tensor, *, first: int = 0, face_normals: bool = False, normals: Optional[torch.Tensor] = None,
+                  attributes: Optional[torch.Tensor] = None, triangle: Optional[torch.Tensor] = None,
+                  barycentric: Optional[torch.Tensor] = None, out_normals: Optional[torch.Tensor] = None,
+                  out_attributes: Optional[torch.Tensor] = None) -> _lib.MeshSample:
+    """``pr_mesh_sample_t`` over prepared tensors (fp32 / int32 / fp64, contiguous, one device); the attribute width is the second
+    dimension of ``attributes``."""
+    s = _lib.MeshSample()
+    s.groups = vertex_offsets.numel() - 1
+    s.total_vertices = int(total_vertices)
+    s.total_triangles = int(total_triangles)
+    s.flags = _lib.SAMPLE_FACE_NORMALS if face_normals else 0
+    s.samples = int(samples)
+    s.attribute_width = 0 if attributes is None else attributes.size(1)
+    s.seed = int(seed)
+    s.first_sample = int(first)
+    for name, t in (("vertices", vertices), ("triangles", triangles), ("vertex_offsets", vertex_offsets),
+                    ("triangle_offsets", triangle_offsets), ("normals", normals), ("attributes", attributes), ("points", points),
+                    ("triangle", triangle), ("barycentric", barycentric), ("out_normals", out_normals),
+                    ("out_attributes", out_attributes), ("counts", counts), ("measures", measures)):
+        setattr(s, name, None if t is None else t.data_ptr())
+    return s
+
+
+@dataclass
+class SurfaceSamples:
+    """What ``sample_meshes`` returns per mesh, on the device: ``points (n, 3)``, ``triangle (n)`` int32 - the triangle every point lies
+    on, -1 throughout for a mesh without area -, ``barycentric (n, 2)`` = ``(v, w)`` of the point in it (``RayGrid.closest``'s
+    convention: the point is ``a + v (b - a) + w (c - a)``), ``normals (n, 3)`` unit vectors (zero rows where there is none) or None,
+    ``features (n, F)`` fp32 or None, ``counts (4)`` int32 - valid triangles, dropped triangles, valid triangles too small to be drawn,
+    points drawn - and ``measures (2)`` fp64: the largest triangle area and the area the points are spread over."""
+    points: torch.Tensor
+    triangle: torch.Tensor
+    barycentric: torch.Tensor
+    normals: Optional[torch.Tensor]
+    features: Optional[torch.Tensor]
+    counts: torch.Tensor
+    measures: torch.Tensor
+
+
+def _sample_arguments(n, seed, first, groups):
+    """``(n, seed, first)`` checked as ``pr_mesh_sample`` checks them, with the argument's own name in the message."""
+    try:
+        n, seed, first = operator.index(n), operator.index(seed), operator.index(first)
+    except TypeError:
+        raise ValueError(f"n, seed and first must be integers, got {n!r} / {seed!r} / {first!r}") from None
+    if n < 0 or groups * n >= 2 ** 31:
+        raise ValueError(f"n must be >= 0 with meshes * n below 2^31, got {n} for {groups} meshes")
+    if not (0 <= seed < 2 ** 64 and 0 <= first < 2 ** 64):
+        raise ValueError(f"seed and first must be in [0, 2^64), got {seed} / {first}")
+    return n, seed, first
+
+
+def _sample_packed(vertices, triangles, vertex_offsets, triangle_offsets, V: int, T: int, n: int, seed: int, first: int, *,
+                   face: bool = False, normals=None, attributes=None):
+    """One ``pr_mesh_sample`` call on packed device tensors (the offsets too), on the current stream, into exactly sized tensors:
+    a dict of the ``(G, n, ...)`` outputs.  The workspace is sized on the host; nothing is read back."""
+    lib = _lib.load()
+    dev = vertices.device
+    G = vertex_offsets.numel() - 1
+    rows = max(G * n, 1)                                            # (an empty tensor has no address: the library refuses NULL)
+    with torch.cuda.device(dev):
+        new = lambda width, dtype=torch.float32: torch.empty((rows, width), dtype=dtype, device=dev)
+        out = {"points": new(3), "triangle": new(1, torch.int32), "barycentric": new(2),
+               "counts": torch.empty((G, _lib.SAMPLE_COUNTS), dtype=torch.int32, device=dev),
+               "measures": torch.empty((G, _lib.SAMPLE_MEASURES), dtype=torch.float64, device=dev)}
+        if face or normals is not None:
+            out["normals"] = new(3)
+        if attributes is not None:
+            out["features"] = new(attributes.size(1))
+        s = sample_struct(vertices, triangles, vertex_offsets, triangle_offsets, V, T, n, seed, out["points"], out["counts"],
+                          out["measures"], first=first, face_normals=face, normals=None if face else normals, attributes=attributes,
+                          triangle=out["triangle"], barycentric=out["barycentric"], out_normals=out.get("normals"),
+                          out_attributes=out.get("features"))
+        size = C.c_size_t()
+        _lib.check(lib.pr_mesh_sample_workspace_size(C.byref(s), C.byref(size)), "pr_mesh_sample_workspace_size")
+        workspace = torch.empty(size.value, dtype=torch.uint8, device=dev)
+        _lib.check(lib.pr_mesh_sample(C.byref(s), workspace.data_ptr(), size.value, torch.cuda.current_stream(dev).cuda_stream),
+                   "pr_mesh_sample")
+    for key in ("points", "triangle", "barycentric", "normals", "features"):
+        if key in out:
+            out[key] = out[key][:G * n].reshape((G, n) + ((out[key].size(1),) if key != "triangle" else ()))
+    return out
+
+
+def _surface_samples(out, groups: int) -> List[SurfaceSamples]:
+    pick = lambda key, g: out[key][g] if key in out else None
+    return [SurfaceSamples(out["points"][g], out["triangle"][g], out["barycentric"][g], pick("normals", g), pick("features", g),
+                           out["counts"][g], out["measures"][g]) for g in range(groups)]
+
+
+def sample_meshes(meshes: Sequence[Mesh], n: int, *, seed: int, first: int = 0, normals: Optional[str] = "face",
+                  features: bool = True) -> List[SurfaceSamples]:
+    """``n`` points on every mesh, drawn with probability proportional to triangle area (``pr_mesh_sample``, include/playrender.h),
+    one ``SurfaceSamples`` per mesh: the point cloud of an object, and what a surface integral over a mesh is made from
+    (``compare_meshes``).  Point ``i`` of mesh ``g`` is a function of ``(seed, first + i, g)`` and of the mesh alone - Philox draws,
+    integer weights and integer prefix sums -, so the result is equal bit for bit from run to run, points ``[k, n)`` are points
+    ``[0, n - k)`` of the call with ``first + k``, and two calls whose ranges ``[first, first + n)`` do not meet draw independent
+    points.  ``seed`` has no default: the caller owns repeatability.  Triangles with an index out of range, a repeated index or a
+    coordinate that is not finite are not drawn from, nor are triangles below ``2^-32`` of the mesh's largest (``counts`` reports
+    both); a mesh without area gets ``triangle == -1`` and zeros.
+
+    ``normals``: ``"face"`` (the default) - the unit normal of the triangle the point lies on, pointing where the triangle points;
+    ``"vertex"`` - the meshes' vertex normals interpolated to the point and normalised, which raises for a mesh without normals; None.
+    ``features=True`` carries ``Mesh.features`` to the points where every mesh has them with one common width - as fp32 rows,
+    whatever their dtype, as ``weld_meshes`` carries them.
+
+    The meshes are packed as ``simplify_meshes`` packs them; the workspace is sized on the host; one call on the current stream and
+    NO host synchronisation.  There is no CPU fallback."""
+    meshes = list(meshes)
+    if not meshes:
+        raise ValueError("sample_meshes needs at least one mesh")
+    if normals not in ("vertex", "face", None):
+        raise ValueError(f"normals must be 'vertex', 'face' or None, got {normals!r}")
+    n, seed, first = _sample_arguments(n, seed, first, len(meshes))
+    if not all(m.vertices.is_cuda and m.triangles.is_cuda for m in meshes):
+        raise RuntimeError(NO_CPU)
+    dev = meshes[0].vertices.device
+    for m in meshes:
+        if m.vertices.dim() != 2 or m.vertices.size(1) != 3 or m.triangles.dim() != 2 or m.triangles.size(1) != 3:
+            raise ValueError(f"a mesh has vertices (V, 3) and triangles (T, 3), got {list(m.vertices.shape)} / {list(m.triangles.shape)}")
+    if normals == "vertex" and not all(m.normals is not None for m in meshes):
+        raise ValueError("normals='vertex' needs meshes with normals (Mesh.vertex_normals() computes them); 'face' needs none")
+    with_features = bool(features) and all(m.features is not None and m.features.dim() == 2 for m in meshes) and \
+        len({m.features.size(1) for m in meshes}) == 1 and meshes[0].features.size(1) > 0
+    if with_features and meshes[0].features.size(1) > _lib.SAMPLE_MAX_ATTRIBUTE_WIDTH:
+        raise ValueError(f"features can be at most {_lib.SAMPLE_MAX_ATTRIBUTE_WIDTH} wide, got {meshes[0].features.size(1)}")
+    pack = lambda parts, dtype, width=3: torch.cat([p.detach().to(device=dev, dtype=dtype).reshape(-1, width) for p in parts]).contiguous()
+    vertices = pack([m.vertices for m in meshes], torch.float32)
+    triangles = pack([m.triangles for m in meshes], torch.int32)
+    rows = None
+    if normals == "vertex":
+        rows = pack([m.normals for m in meshes], torch.float32)
+        if rows.size(0) != vertices.size(0):
+            raise ValueError("normals must have one row per vertex")
+    attributes = None
+    if with_features:
+        if any(m.features.size(0) != m.vertices.size(0) for m in meshes):
+            raise ValueError("features must have one row per vertex")
+        attributes = pack([m.features for m in meshes], torch.float32, meshes[0].features.size(1))
+    vo, to = [0], [0]
+    for m in meshes:
+        vo.append(vo[-1] + m.vertices.size(0))
+        to.append(to[-1] + m.triangles.size(0))
+    if vertices.size(0) == 0:                                      # (an empty tensor has no address: the library refuses NULL)
+        vertices = torch.empty((1, 3), dtype=torch.float32, device=dev)
+        rows = None if rows is None else torch.empty((1, 3), dtype=torch.float32, device=dev)
+        attributes = None if attributes is None else torch.empty((1, attributes.size(1)), dtype=torch.float32, device=dev)
+    if triangles.size(0) == 0:
+        triangles = torch.empty((1, 3), dtype=torch.int32, device=dev)
+    offsets = torch.tensor([vo, to], dtype=torch.int32).to(dev)
+    out = _sample_packed(vertices, triangles, offsets[0], offsets[1], vo[-1], to[-1], n, seed, first, face=normals == "face",
+                         normals=rows, attributes=attributes)
+    return _surface_samples(out, len(meshes))
+
+
+DEVIATION_FIELDS = ("samples", "misses", "mean", "rms", "max", "p99", "normal_consistency")
+
+
+@dataclass
+class MeshDeviation:
+    """What ``compare_meshes`` returns, on the device: per direction a fp64 vector of ``DEVIATION_FIELDS`` followed by one share per
+    threshold, the ``(samples)`` fp32 distances they were reduced from (``+inf``: a miss) and the thresholds.  ``report()`` reads
+    them back."""
+    a_to_b: torch.Tensor
+    b_to_a: torch.Tensor
+    distance_a_to_b: torch.Tensor
+    distance_b_to_a: torch.Tensor
+    thresholds: tuple = ()
+
+    def report(self) -> dict:
+        """The deviation as a plain dict - ONE read-back.  ``a_to_b`` / ``b_to_a``: ``samples``, ``misses`` - samples with nothing of
+        the other mesh within ``max_distance``; they are left out of the means and always reported -, ``mean``, ``rms``, ``max``
+        and ``p99`` (nearest rank) of the found distances (NaN if none was found), ``normal_consistency`` - the mean ``|n . n'|`` of
+        the sample's face normal and the closest triangle's over the found samples where neither is zero - and ``within``: per
+        threshold the share of ALL samples, misses included, within it.  ``chamfer = a_to_b.mean + b_to_a.mean``.  ``thresholds``:
+        per threshold ``precision`` (the share of a within it of b), ``recall`` (of b within it of a) and ``fscore``, their harmonic
+        mean (0 where both are 0)."""
+        host = torch.stack([self.a_to_b, self.b_to_a]).cpu().tolist()
+        k = len(DEVIATION_FIELDS)
+        out = {}
+        for name, row in zip(("a_to_b", "b_to_a"), host):
+            side = dict(zip(DEVIATION_FIELDS, row))
+            side["samples"], side["misses"] = int(side["samples"]), int(side["misses"])
+            side["within"] = list(row[k:])
+            out[name] = side
+        out["chamfer"] = out["a_to_b"]["mean"] + out["b_to_a"]["mean"]
+        out["thresholds"] = []
+        for i, threshold in enumerate(self.thresholds):
+            precision, recall = host[0][k + i], host[1][k + i]
+            fscore = 2 * precision * recall / (precision + recall) if precision + recall > 0 else 0.0
+            out["thresholds"].append({"threshold": threshold, "precision": precision, "recall": recall, "fscore": fscore})
+        return out
+
+
+def _unit_rows(n: torch.Tensor) -> torch.Tensor:
+    length = n.norm(dim=1, keepdim=True)
+    return torch.where((length > 0) & torch.isfinite(length), n / length, torch.zeros_like(n))
+
+
+def _one_sided_deviation(samples: SurfaceSamples, other: Mesh, grid: "RayGrid", max_distance: float, thresholds):
+    """``(statistics, distances)`` of one direction: plain torch expressions in fp64, nothing is read back."""
+    found = grid.closest(samples.points, max_distance=max_distance)
+    distance, triangle = found.distance[0], found.triangle[0]
+    d = distance.to(torch.float64)
+    hit = torch.isfinite(d) & (triangle >= 0)
+    total = torch.tensor(float(d.numel()), dtype=torch.float64, device=d.device)
+    m = hit.sum()
+    count = m.to(torch.float64)                                      # (0 found: 0 / 0 = NaN in the means)
+    nan = torch.full_like(count, math.nan)
+    zero = torch.zeros_like(d)
+    mean = torch.where(hit, d, zero).sum() / count
+    rms = torch.sqrt(torch.where(hit, d * d, zero).sum() / count)
+    largest = torch.where(m > 0, torch.where(hit, d, torch.full_like(d, -math.inf)).max(), nan)
+    # nearest rank: the smallest found distance that at least 99 % of the found distances do not exceed
+    ordered = torch.sort(torch.where(hit, d, torch.full_like(d, math.inf))).values
+    rank = ((99 * m + 99) // 100 - 1).clamp(min=0)
+    p99 = torch.where(m > 0, ordered[rank], nan)
+    # the closest triangle's face normal, in fp64, against the sample's
+    face = torch.zeros((d.numel(), 3), dtype=torch.float64, device=d.device)
+    if other.triangles.size(0) > 0:
+        rows = triangle.clamp(min=0, max=other.triangles.size(0) - 1).to(torch.int64)
+        corners = other.vertices.detach().to(torch.float64)[other.triangles.detach().to(torch.int64)[rows]]
+        face = _unit_rows(torch.cross(corners[:, 1] - corners[:, 0], corners[:, 2] - corners[:, 0], dim=1))
+    own = _unit_rows(samples.normals.to(torch.float64))
+    both = hit & (face != 0).any(dim=1) & (own != 0).any(dim=1)
+    dots = (face * own).sum(dim=1).abs()
+    consistency = torch.where(both, dots, zero).sum() / both.sum().to(torch.float64)
+    shares = [(d <= t).sum().to(torch.float64) / total for t in thresholds]            # (a miss is +inf: within nothing)
+    return torch.stack([total, total - count, mean, rms, largest, p99, consistency] + shares), distance
+
+
+def compare_meshes(a: Mesh, b: Mesh, *, samples: int, seed: int, max_distance: float, thresholds=(), cells=32) -> MeshDeviation:
+    """How far two meshes lie from each other, as surface integrals: ``samples`` area-weighted points of ``a``
+    (``sample_meshes``, face normals, stream indices ``[0, samples)``) measured against ``b`` with ``RayGrid.closest`` on
+    ``bounding_grid([b], cells)``, and as many of ``b`` (indices ``[samples, 2 samples)``: the two draws are disjoint) against ``a``.
+    Unlike ``Mesh.distance_to``, which looks from the VERTICES of one mesh - few and at the cluster representatives after a
+    simplification, exactly the points that moved after a smoothing, dense where the triangles are small -, every part of either
+    surface counts by its area here; ``distance_to`` stays the cheap one-sided check.
+
+    ``max_distance`` bounds the search as in ``closest`` and has no default; a sample with nothing within it is a MISS, left out of
+    the means and counted.  ``thresholds``: distances for which the share of samples within them - precision, recall, F-score - is
+    reported; one above ``max_distance`` raises, because misses could not be told from samples beyond it.  The reductions are torch
+    expressions in fp64 on the device; two grid builds (one read-back each, plus ``bounding_grid``'s) are the host synchronisations,
+    and ``MeshDeviation.report()`` is the read-back of the result.  There is no CPU fallback."""
+    if not isinstance(a, Mesh) or not isinstance(b, Mesh):
+        raise ValueError("compare_meshes compares two Mesh objects")
+    try:
+        samples = operator.index(samples)
+    except TypeError:
+        raise ValueError(f"samples must be an integer >= 1, got {samples!r}") from None
+    if samples < 1:
+        raise ValueError(f"samples must be an integer >= 1, got {samples}")
+    max_distance = float(max_distance)
+    if math.isnan(max_distance) or max_distance < 0:
+        raise ValueError(f"max_distance must be >= 0 and not NaN, got {max_distance}")
+    thresholds = tuple(float(t) for t in thresholds)
+    for t in thresholds:
+        if math.isnan(t) or t < 0 or t > max_distance:
+            raise ValueError(f"a threshold must lie in [0, max_distance = {max_distance}] - beyond it a miss cannot be told from a "
+                             f"sample that is merely farther -, got {t}")
+    if not all(m.vertices.is_cuda and m.triangles.is_cuda for m in (a, b)):
+        raise RuntimeError(NO_CPU)
+    from_a = sample_meshes([a], samples, seed=seed, first=0, normals="face", features=False)[0]
+    from_b = sample_meshes([b], samples, seed=seed, first=samples, normals="face", features=False)[0]
+    grid_a = RayGrid.build([a], *bounding_grid([a], cells))
+    grid_b = RayGrid.build([b], *bounding_grid([b], cells))
+    a_to_b, distance_a = _one_sided_deviation(from_a, b, grid_b, max_distance, thresholds)
+    b_to_a, distance_b = _one_sided_deviation(from_b, a, grid_a, max_distance, thresholds)
+    return MeshDeviation(a_to_b, b_to_a, distance_a, distance_b, thresholds)
 
 
 def bounding_grid(meshes: Sequence[Mesh], cells):
