@@ -1275,6 +1275,110 @@ int pr_mesh_sample_workspace_size(const pr_mesh_sample_t* s, size_t* bytes);
 int pr_mesh_sample(const pr_mesh_sample_t* s, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Intersection of packed meshes on the grid of pr_raycast_build: pr_mesh_intersect finds, for every triangle of a QUERY mesh set, the
+ * triangles of the TARGET mesh set of the same group that it cuts, and optionally the pairs and one contact segment per pair - does
+ * object A, at its current pose, cut object B, and where; with PR_INTERSECT_SELF: does a mesh cut itself.  It reads what
+ * pr_closest_query reads and builds nothing.  The result is DEFINED as that of the exhaustive rule below over all (query, target)
+ * pairs of a group, in fixed fp32 arithmetic; the grid may change the time and never the bits - without any domain restriction,
+ * because BOX is part of the rule (argument: DESIGN.md 28.2).
+ *   Targets: the packed meshes of a finished EMITTING pr_raycast_build, read exactly as pr_closest_t reads them (same fields, same
+ *     clamping of offsets, same grid coordinates and lists; references outside [0, max_references) or [0, T_g) are skipped where
+ *     they are read: a stale or foreign grid costs correctness, never memory safety).
+ *   Queries: a second packed mesh set of the same G - q_vertices (QV, 3) fp32, q_triangles (QT, 3) int32 LOCAL to their group,
+ *     q_vertex_offsets (G + 1), q_triangle_offsets (G + 1), all on the device, q_total_vertices / q_total_triangles = QV and QT as host
+ *     values, offsets clamped in the same way - and optionally transform (G, 3, 4) fp32, row-major, rows m_k = (m_k0, m_k1, m_k2, m_k3):
+ *     query vertex x of group g is used as  x'_k = ((m_k0 x_0 + m_k1 x_1) + m_k2 x_2) + m_k3,  in fp32 without contraction; a NULL
+ *     transform uses x itself.  (A static object's grid is built once and the moving object is posed per call.)
+ *   Candidates, on both sides: three indices in [0, V_g) / [0, QV_g) and nine finite coordinates - on the query side after the
+ *     transform.  A target that pr_raycast_build classifies as dead (a == b or a == c as values) is no candidate.
+ *   Pair rule: query triangle Q = (a, b, c) and target triangle T of the same group, both candidates, are a PAIR iff BOX and
+ *     (EDGE(Q -> T) or EDGE(T -> Q)) hold.
+ *       BOX: on all three axes min(Q) <= max(T) and min(T) <= max(Q), min and max over the three corners, compared as fp32 values.
+ *       EDGE(X -> Y): at least one of X's edges is accepted by Y.  X's edges are taken in the order (a, b), (b, c), (c, a), each as
+ *         the ray o = start, d = end - start, and the test is pr_raycast_t's test of one ray against one triangle exactly as stated
+ *         there (fp32, no contraction, the same dot and cross products, e1, e2, p, det, s, u, q, v, t), with no culling (det < 0 or
+ *         det > 0), t_min = 0, t_max = 1, and one more clause, the CONDITIONING clause, with that header's dot-product order:
+ *             det * det > 2^-20 * (((e1 . e1) (e2 . e2)) (d . d))        (four fp32 products, left to right as bracketed).
+ *       Every comparison is false on a NaN.
+ *     The clause is no decoration: neighbouring triangles of a marching-tetrahedra mesh are often coplanar, det is then rounding
+ *     noise instead of 0, and without the clause a clean lattice sphere "cuts itself".  Consequences: COPLANAR OVERLAP IS NEVER A
+ *     PAIR; the rule is SYMMETRIC - with the roles of the two mesh sets swapped (and the transform applied to the vertices beforehand)
+ *     the pair set is transposed -; like pr_raycast_query it is NOT WATERTIGHT along shared edges and vertices: an edge through
+ *     another triangle's edge or vertex can be accepted by both neighbours or by neither.
+ *   PR_INTERSECT_SELF: the query set IS the target set.  The four query pointers must each be NULL or equal to the target's, the
+ *     query totals must equal the target's, transform must be NULL.  A pair is left out if q == t, and if any corner of Q equals any
+ *     corner of T as VALUES in the sense of pr_mesh_audit ("Vertex identity is by VALUE": the three fp32 components compare equal
+ *     with ==, so -0 equals +0) - neighbours always touch.  Every unordered pair that remains shows up from both sides.
+ *   Outputs, all optional except count, rows in the PACKED order of the query triangles:
+ *     count (QT) int32: the pairs of the query triangle.   first (QT) int32: the lowest target index among them, or -1.
+ *     pair_offsets (QT + 1) int32: the exclusive sums of count; the last element is P, the number of pairs.
+ *     pairs (max_pairs, 2) int32: (query, target), both LOCAL to their group; the pairs of packed query row r are the rows
+ *       [pair_offsets[r], pair_offsets[r + 1]).  The order inside such a segment of rows is unspecified.
+ *     segments (max_pairs, 2, 3) fp32, needs pairs: the accepted edge tests of the pair are taken in the fixed order Q's three edges
+ *       against T, then T's three against Q; each gives the point o + t d, per component o_k + t * d_k in fp32 without contraction.
+ *       Endpoint 0 is the first such point; endpoint 1 is the point with the largest squared distance from endpoint 0 (r = point -
+ *       endpoint 0, r . r in fp32 with the dot-product order above), the earliest on ties: with one accepted test it equals endpoint 0.
+ *     Rows of queries that are no candidates, and rows that no clamped group owns, get count 0 and first -1.  Nothing at or beyond
+ *     max_pairs is written; count, first and pair_offsets do not depend on max_pairs.
+ *   Calling pattern (the build's): P is only known on the device.  A counting call with pairs == NULL writes count, first and
+ *     pair_offsets; one read-back of pair_offsets[QT] follows; an exactly sized emitting call ends the sequence (and writes count,
+ *     first and pair_offsets again, with the same values).
+ *   Query: one lane per query triangle, 256-lane blocks that never span two groups.  The lane tests the group's loose list.  With
+ *     g(x) = (x - origin_k) / cell_k in fp32 (the build's two roundings): if on some axis not g(max Q) >= 0 or not g(min Q) < cells_k,
+ *     no tight target is tested.  Otherwise the lane visits the cells (int)max(g(min Q), 0) .. min((int)min(g(max Q), cells_k),
+ *     cells_k - 1) on every axis, and a triangle found in the list of a cell is tested there iff BOX holds and the cell is
+ *     (int)max(g(min T), g(min Q)) on every axis: a target listed in several cells is counted once.
+ * Workspace bytes = the sum of these regions, each rounded up to 256 bytes, with NB = floor(QT / 256) + 1: 5 x 4 (G + 1) (per group:
+ *   first vertex and first triangle of both sets, first query block) + 4 (QT + 1) (the exclusive sums) + 2 x 4 NB (block sums of the
+ *   counts and their scan) + 4 (the total).
+ * Five kernel launches on `stream` for a counting call, six for an emitting one (also with QT == 0), no memset, no memcpy, no
+ * allocation, no synchronisation: capturable into a HIP graph.  No atomics.
+ * Additive entry points: PR_ABI_VERSION is unchanged.  sizeof(pr_mesh_intersect_t) = 200.
+ * Refused (PR_ERR_INVALID, before any device work; by pr_mesh_intersect_workspace_size too, except the workspace itself):
+ * everything pr_closest_query refuses about mesh, grid and capacities (NULL vertices, triangles, offsets or cell_offsets, groups < 1,
+ * a cells entry outside 1 .. 1024 or a product above 2^21, a cell size that is not finite or not > 0, a non-finite origin, a negative
+ * total or capacity, NULL references with max_references > 0, T + 256 G or G (C + 1) + 256 at or above 2^31), a NULL count, segments
+ * without pairs, a negative q_total_vertices, q_total_triangles or max_pairs, QT + 256 G at or above 2^31, unknown flag bits; without
+ * PR_INTERSECT_SELF NULL q_vertices, q_triangles or query offsets; with it a transform, a foreign query pointer or other query
+ * totals; by the call only, and last: a NULL, misaligned or too small workspace.  QT == 0, T == 0 and an empty group are valid.
+ */
+#define PR_INTERSECT_SELF 1u
+typedef struct pr_mesh_intersect_t {
+    int32_t groups;                       /* G >= 1 */
+    int32_t total_vertices;               /* V = vertex_offsets[G], as a host value, >= 0 */
+    int32_t total_triangles;              /* T = triangle_offsets[G], as a host value, >= 0 */
+    uint32_t flags;                       /* PR_INTERSECT_SELF or 0 */
+    float origin[3];                      /* the grid of the build: finite */
+    float cell[3];                        /* finite, > 0 */
+    int32_t cells[3];                     /* each 1 .. PR_RAYCAST_MAX_AXIS_CELLS, product <= PR_RAYCAST_MAX_CELLS */
+    int32_t max_references;               /* rows of references, >= 0 */
+    int32_t q_total_vertices;             /* QV, as a host value, >= 0 (self: V) */
+    int32_t q_total_triangles;            /* QT, as a host value, >= 0 (self: T) */
+    int32_t max_pairs;                    /* rows of pairs and segments, >= 0 */
+    uint32_t reserved_;
+    const float* vertices;                /* (V, 3) */
+    const int32_t* triangles;             /* (T, 3), indices local to the group */
+    const int32_t* vertex_offsets;        /* (G + 1) */
+    const int32_t* triangle_offsets;      /* (G + 1) */
+    const int32_t* cell_offsets;          /* (G (C + 1) + 1), as pr_raycast_build wrote them */
+    const int32_t* references;            /* (max_references), as an emitting pr_raycast_build wrote them (NULL: max_references 0) */
+    const float* q_vertices;              /* (QV, 3); self: NULL or vertices */
+    const int32_t* q_triangles;           /* (QT, 3), indices local to the group; self: NULL or triangles */
+    const int32_t* q_vertex_offsets;      /* (G + 1); self: NULL or vertex_offsets */
+    const int32_t* q_triangle_offsets;    /* (G + 1); self: NULL or triangle_offsets */
+    const float* transform;               /* (G, 3, 4) or NULL; self: NULL */
+    int32_t* count;                       /* (QT), always written */
+    int32_t* first;                       /* (QT) or NULL */
+    int32_t* pair_offsets;                /* (QT + 1) or NULL */
+    int32_t* pairs;                       /* (max_pairs, 2) or NULL: count only */
+    float* segments;                      /* (max_pairs, 2, 3) or NULL; needs pairs */
+} pr_mesh_intersect_t;
+/* Host computation, no device work; refuses everything above that does not concern the workspace. */
+int pr_mesh_intersect_workspace_size(const pr_mesh_intersect_t* s, size_t* bytes);
+/* `workspace`: 256-byte aligned, pr_mesh_intersect_workspace_size bytes. */
+int pr_mesh_intersect(const pr_mesh_intersect_t* s, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Backward pass of pr_render_forward (what torch.autograd does for the reference's op graph when
  * training/trainer_backpropagated_autoencoder.py:349 calls total_loss.backward()).  The forward call must
  * have run with PR_FLAG_SAVE_FOR_BACKWARD (with or without PR_FLAG_TRAIN_BN) on the same `call`, `objects` and

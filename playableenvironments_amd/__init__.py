@@ -17,7 +17,9 @@ Public surface (mirrors the reference's modules for the renderer hot path only):
                             extracted meshes by vertex clustering (extract_mesh(simplify=k)); surface.RayGrid casts rays
                             against them (closest hits on a cell grid) and finds the closest point of a mesh to a point
                             (RayGrid.closest, Mesh.distance_to) and whether a point lies inside one (RayGrid.winding /
-                            contains / signed_distance: watertight, exact where the topology depends on it)
+                            contains / signed_distance: watertight, exact where the topology depends on it); RayGrid.intersect /
+                            Mesh.intersections / Mesh.self_intersections / surface.collide find the triangle pairs in which
+                            two meshes - or one mesh and itself - cut each other, with contact segments
   ray_sampling, wire_format pixel / ray samplers and the renderer <-> decoder tensor glue of the reference
   parallel                  frame shards, overlapped feature all-gather, gradient all-reduce (torch.distributed / RCCL)
   configs / synthetic       shipped renderer configurations and seeded synthetic scenes
@@ -26,8 +28,8 @@ from . import batching, configs, encoders, geometry, parallel, ray_sampling, sur
 from .environment_model import EnvironmentModel  # noqa: F401
 from .frame_graph import FrameGraph  # noqa: F401
 from .object_composer import ObjectComposer, ObjectIDsHelper  # noqa: F401
-from .surface import Mesh, RayGrid, clean_lattice, label_components, simplify_meshes  # noqa: F401
+from .surface import Mesh, MeshContacts, RayGrid, clean_lattice, collide, label_components, simplify_meshes  # noqa: F401
 
 __all__ = ["ObjectComposer", "ObjectIDsHelper", "EnvironmentModel", "FrameGraph", "configs", "synthetic", "parallel",
            "ray_sampling", "wire_format", "encoders", "batching", "geometry", "surface", "Mesh", "label_components",
-           "clean_lattice", "simplify_meshes", "RayGrid"]
+           "clean_lattice", "simplify_meshes", "RayGrid", "MeshContacts", "collide"]

@@ -327,6 +327,20 @@ SAMPLE_MEASURES = 2              # columns of pr_mesh_sample_t.measures
 SAMPLE_MAX_ATTRIBUTE_WIDTH = 4096
 
 
+class MeshIntersect(C.Structure):
+    """pr_mesh_intersect_t (include/playrender.h)."""
+    _fields_ = [("groups", C.c_int32), ("total_vertices", C.c_int32), ("total_triangles", C.c_int32), ("flags", C.c_uint32),
+                ("origin", C.c_float * 3), ("cell", C.c_float * 3), ("cells", C.c_int32 * 3), ("max_references", C.c_int32),
+                ("q_total_vertices", C.c_int32), ("q_total_triangles", C.c_int32), ("max_pairs", C.c_int32), ("reserved_", C.c_uint32),
+                ("vertices", C.c_void_p), ("triangles", C.c_void_p), ("vertex_offsets", C.c_void_p), ("triangle_offsets", C.c_void_p),
+                ("cell_offsets", C.c_void_p), ("references", C.c_void_p), ("q_vertices", C.c_void_p), ("q_triangles", C.c_void_p),
+                ("q_vertex_offsets", C.c_void_p), ("q_triangle_offsets", C.c_void_p), ("transform", C.c_void_p), ("count", C.c_void_p),
+                ("first", C.c_void_p), ("pair_offsets", C.c_void_p), ("pairs", C.c_void_p), ("segments", C.c_void_p)]
+
+
+INTERSECT_SELF = 1               # PR_INTERSECT_SELF
+
+
 # every exported symbol of include/playrender.h : (restype, argtypes)
 class SceneSetup(C.Structure):
     """pr_scene_setup_t (include/playrender.h)."""
@@ -383,6 +397,8 @@ SYMBOLS = {
     "pr_mesh_smooth": (C.c_int, [C.POINTER(MeshSmooth), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_mesh_sample_workspace_size": (C.c_int, [C.POINTER(MeshSample), C.POINTER(C.c_size_t)]),
     "pr_mesh_sample": (C.c_int, [C.POINTER(MeshSample), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pr_mesh_intersect_workspace_size": (C.c_int, [C.POINTER(MeshIntersect), C.POINTER(C.c_size_t)]),
+    "pr_mesh_intersect": (C.c_int, [C.POINTER(MeshIntersect), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_backward_workspace_size": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(C.c_size_t)]),
     "pr_render_backward": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(OutputGrads), C.POINTER(OutputGrads),
                                      C.POINTER(InputGrads), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),

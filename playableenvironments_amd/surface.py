@@ -39,6 +39,10 @@ bit (``extract_surface(smooth=n)``).
 to area - repeatable bit for bit from a seed, with normals and feature rows carried to the points - and ``compare_meshes`` measures
 with them how far one mesh lies from another as a surface integral (mean, rms, max, Chamfer distance, F-score), where
 ``Mesh.distance_to`` looks from the vertices only.
+
+``RayGrid.intersect`` / ``Mesh.intersections`` / ``Mesh.self_intersections`` / ``collide`` (``pr_mesh_intersect``) find on the same
+grid the triangle pairs in which a second mesh, posed by a transform, cuts the grid's mesh - or a mesh cuts itself -, with one contact
+segment per pair: the results of the exhaustive rule over all pairs, bit for bit, whatever the grid.
 """
 from __future__ import annotations
 
@@ -103,6 +107,28 @@ class Mesh:
         if other.groups != 1:
             raise ValueError(f"distance_to needs a grid of one group, got {other.groups}")
         return other.closest(self.vertices, max_distance=max_distance).distance[0]
+
+    def intersections(self, other, *, transform=None, cells=32, **kw) -> "MeshContacts":
+        """The triangles of this mesh, posed by ``transform`` (into the other's frame; None: as it is), that cut ``other`` - a
+        ``RayGrid`` of one group, or a ``Mesh``, which is sorted into ``bounding_grid([other], cells)`` first:
+        ``RayGrid.intersect([self], transform=transform, **kw)[0]`` (``pairs=True`` / ``segments=True`` for the pairs and the contact
+        segments)."""
+        if isinstance(other, Mesh):
+            if not (self.vertices.is_cuda and other.vertices.is_cuda):
+                raise RuntimeError(NO_CPU)
+            other = RayGrid.build([other], *bounding_grid([other], cells))
+        if other.groups != 1:
+            raise ValueError(f"intersections needs a grid of one group, got {other.groups}")
+        return other.intersect([self], transform=transform, **kw)[0]
+
+    def self_intersections(self, *, cells=32, pairs: bool = False) -> "MeshContacts":
+        """Where this mesh cuts itself - what ``simplified`` (two sheets can meet in a cell) and many ``smoothed`` iterations can
+        cause, and what ``audit()`` does not see: the mesh on ``bounding_grid([self], cells)`` against itself
+        (``RayGrid.intersect(self_=True)``).  Triangles that share a corner value are no pair; ``report()["pairs"]`` counts every
+        unordered pair once.  ``contains``, ``signed_volume`` and ``compare_meshes`` mean what they say only where this is 0."""
+        if not (self.vertices.is_cuda and self.triangles.is_cuda):
+            raise RuntimeError(NO_CPU)
+        return RayGrid.build([self], *bounding_grid([self], cells)).intersect(self_=True, pairs=pairs)[0]
 
     def audit(self, labels: bool = False) -> "MeshAudit":
         """How this one mesh is made up: ``audit_meshes([self], labels=labels)[0]``.  A welded mesh (``welded``) answers
@@ -790,6 +816,90 @@ class RayGrid:
         distance = self.closest(points, max_distance=max_distance).distance
         signed = torch.where(self.contains(points, axis=axis), -distance, distance)
         return signed.amin(dim=0) if nearest else signed
+
+    def intersect(self, meshes: Optional[Sequence[Mesh]] = None, *, transform=None, pairs: bool = False, segments: bool = False,
+                  self_: bool = False) -> List["MeshContacts"]:
+        """The triangles of ``meshes`` - one per group, posed by ``transform`` (``v' = R v + t``: one ``(3, 4)`` / ``(4, 4)`` matrix for
+        all groups, or ``(G, 3, 4)`` / ``(G, 4, 4)``; None: as they are) - that cut the triangles of this grid's meshes
+        (``pr_mesh_intersect``): one ``MeshContacts`` per group.  Two triangles are a pair iff their boxes overlap and an edge of one
+        passes through the other, decided in fixed fp32 arithmetic with a conditioning clause - coplanar overlap is never a pair, and the
+        result is that of the exhaustive rule over all pairs, bit for bit, whatever the grid.  ``self_=True``: the grid's meshes
+        against themselves (``meshes`` and ``transform`` must be None) - pairs of one triangle with itself and of triangles that share
+        a corner value are left out, and every unordered pair shows up twice.  Without ``pairs`` / ``segments`` one counting call and no
+        host synchronisation; with them the number of pairs is read back - the ONE synchronisation -, an exactly sized emitting call
+        follows, and one sort puts the pairs into (query, target) order.  A static object's grid is built once and the moving object
+        posed per call: cheaper than ``Mesh.transformed`` and a rebuild."""
+        G, dev = self.groups, self.vertices.device
+        if not self.vertices.is_cuda:
+            raise RuntimeError(NO_CPU)
+        if self_:
+            if meshes is not None or transform is not None:
+                raise ValueError("self_=True queries the grid's own meshes: meshes and transform must be None")
+            to = getattr(self, "host_triangle_offsets", None) or self.triangle_offsets.cpu().tolist()
+            query = {}
+            QT = self.total_triangles
+        else:
+            meshes = list(meshes) if meshes is not None else []
+            if len(meshes) != G:
+                raise ValueError(f"the grid holds {G} groups, got {len(meshes)} meshes")
+            if not all(m.vertices.is_cuda and m.triangles.is_cuda for m in meshes):
+                raise RuntimeError(NO_CPU)
+            for m in meshes:
+                if m.vertices.dim() != 2 or m.vertices.size(1) != 3 or m.triangles.dim() != 2 or m.triangles.size(1) != 3:
+                    raise ValueError(f"a mesh has vertices (V, 3) and triangles (T, 3), got {list(m.vertices.shape)} / {list(m.triangles.shape)}")
+            pack = lambda parts, dtype: torch.cat([p.detach().to(device=dev, dtype=dtype).reshape(-1, 3) for p in parts]).contiguous()
+            q_vertices, q_triangles = pack([m.vertices for m in meshes], torch.float32), pack([m.triangles for m in meshes], torch.int32)
+            vo, to = [0], [0]
+            for m in meshes:
+                vo.append(vo[-1] + m.vertices.size(0))
+                to.append(to[-1] + m.triangles.size(0))
+            QT = to[-1]
+            if q_vertices.size(0) == 0:                                # (an empty tensor has no address: the library refuses NULL)
+                q_vertices = torch.empty((1, 3), dtype=torch.float32, device=dev)
+            if q_triangles.size(0) == 0:
+                q_triangles = torch.empty((1, 3), dtype=torch.int32, device=dev)
+            q_offsets = torch.tensor([vo, to], dtype=torch.int32).to(dev)
+            query = dict(q_vertices=q_vertices, q_triangles=q_triangles, q_vertex_offsets=q_offsets[0], q_triangle_offsets=q_offsets[1],
+                         q_total_vertices=vo[-1], q_total_triangles=QT, transform=_pose_rows(transform, G, dev))
+        lib = _lib.load()
+        count = torch.empty(max(QT, 1), dtype=torch.int32, device=dev)
+        first = torch.empty(max(QT, 1), dtype=torch.int32, device=dev)
+        offsets = torch.empty(QT + 1, dtype=torch.int32, device=dev)
+        pair_rows = segment_rows = None
+        bounds = [0] * (G + 1)
+        with torch.cuda.device(dev):
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            common = (self.vertices, self.triangles, self.vertex_offsets, self.triangle_offsets, self.total_vertices,
+                      self.total_triangles, self.origin, self.cell, self.cells, self.cell_offsets)
+            outputs = dict(references=self.references if self.references.numel() else None, count=count, first=first,
+                           pair_offsets=offsets, self_=self_, **query)
+            s = intersect_struct(*common, **outputs)
+            size = C.c_size_t()
+            _lib.check(lib.pr_mesh_intersect_workspace_size(C.byref(s), C.byref(size)), "pr_mesh_intersect_workspace_size")
+            workspace = torch.empty(size.value, dtype=torch.uint8, device=dev)
+            _lib.check(lib.pr_mesh_intersect(C.byref(s), workspace.data_ptr(), size.value, stream), "pr_mesh_intersect")
+            if pairs or segments:
+                bounds = offsets[torch.tensor(to, dtype=torch.int64, device=dev)].cpu().tolist()          # (the host synchronisation)
+                P = bounds[-1]
+                if P < 0:
+                    raise RuntimeError("2^31 or more pairs")
+                pair_rows = torch.empty((P, 2), dtype=torch.int32, device=dev)
+                segment_rows = torch.empty((P, 2, 3), dtype=torch.float32, device=dev) if segments else None
+                if P > 0:
+                    s = intersect_struct(*common, pairs=pair_rows, segments=segment_rows, **outputs)
+                    _lib.check(lib.pr_mesh_intersect(C.byref(s), workspace.data_ptr(), size.value, stream), "pr_mesh_intersect")
+                    # (packed query row, target) as one key: the rows of a query are already adjacent, the sort orders them inside
+                    row = torch.repeat_interleave(torch.arange(QT, dtype=torch.int64, device=dev), count[:QT].to(torch.int64), output_size=P)
+                    order = torch.sort(row * (self.total_triangles + 1) + pair_rows[:, 1].to(torch.int64)).indices
+                    pair_rows = pair_rows[order]
+                    segment_rows = segment_rows[order] if segments else None
+        out = []
+        for g in range(G):
+            own = offsets[to[g]:to[g + 1] + 1]
+            out.append(MeshContacts(count[to[g]:to[g + 1]], first[to[g]:to[g + 1]], own - own[:1],
+                                    pair_rows[bounds[g]:bounds[g + 1]] if pair_rows is not None else None,
+                                    segment_rows[bounds[g]:bounds[g + 1]] if segment_rows is not None else None, symmetric=bool(self_)))
+        return out
 
 
 @dataclass
@@ -1500,6 +1610,140 @@ def compare_meshes(a: Mesh, b: Mesh, *, samples: int, seed: int, max_distance: f
     a_to_b, distance_a = _one_sided_deviation(from_a, b, grid_b, max_distance, thresholds)
     b_to_a, distance_b = _one_sided_deviation(from_b, a, grid_a, max_distance, thresholds)
     return MeshDeviation(a_to_b, b_to_a, distance_a, distance_b, thresholds)
+
+
+def intersect_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offsets: torch.Tensor, triangle_offsets: torch.Tensor,
+                     total_vertices: int, total_triangles: int, origin, cell, cells, cell_offsets: torch.Tensor, *,
+                     references: Optional[torch.Tensor] = None, q_vertices: Optional[torch.Tensor] = None,
+                     q_triangles: Optional[torch.Tensor] = None, q_vertex_offsets: Optional[torch.Tensor] = None,
+                     q_triangle_offsets: Optional[torch.Tensor] = None, q_total_vertices: Optional[int] = None,
+                     q_total_triangles: Optional[int] = None, transform: Optional[torch.Tensor] = None,
+                     count: Optional[torch.Tensor] = None, first: Optional[torch.Tensor] = None,
+                     pair_offsets: Optional[torch.Tensor] = None, pairs: Optional[torch.Tensor] = None,
+                     segments: Optional[torch.Tensor] = None, self_: bool = False) -> _lib.MeshIntersect:
+    """``pr_mesh_intersect_t`` over prepared tensors (fp32 / int32, contiguous, one device); ``max_references`` is the rows of
+    ``references``, ``max_pairs`` the rows of ``pairs``.  The query totals default to the targets' with ``self_`` and to the rows of the
+    query tensors otherwise."""
+    s = _lib.MeshIntersect()
+    s.groups = vertex_offsets.numel() - 1
+    s.total_vertices = int(total_vertices)
+    s.total_triangles = int(total_triangles)
+    s.flags = _lib.INTERSECT_SELF if self_ else 0
+    for a in range(3):
+        s.origin[a] = float(origin[a])
+        s.cell[a] = float(cell[a])
+        s.cells[a] = int(cells[a])
+    s.max_references = 0 if references is None else references.size(0)
+    if q_total_vertices is None:
+        q_total_vertices = total_vertices if self_ else (0 if q_vertices is None else q_vertices.size(0))
+    if q_total_triangles is None:
+        q_total_triangles = total_triangles if self_ else (0 if q_triangles is None else q_triangles.size(0))
+    s.q_total_vertices = int(q_total_vertices)
+    s.q_total_triangles = int(q_total_triangles)
+    s.max_pairs = 0 if pairs is None else pairs.size(0)
+    for name, x in (("vertices", vertices), ("triangles", triangles), ("vertex_offsets", vertex_offsets),
+                    ("triangle_offsets", triangle_offsets), ("cell_offsets", cell_offsets), ("references", references),
+                    ("q_vertices", q_vertices), ("q_triangles", q_triangles), ("q_vertex_offsets", q_vertex_offsets),
+                    ("q_triangle_offsets", q_triangle_offsets), ("transform", transform), ("count", count), ("first", first),
+                    ("pair_offsets", pair_offsets), ("pairs", pairs), ("segments", segments)):
+        setattr(s, name, None if x is None else x.data_ptr())
+    return s
+
+
+@dataclass
+class MeshContacts:
+    """What ``RayGrid.intersect`` returns per group, on the device (``pr_mesh_intersect``, include/playrender.h): ``count (QT)`` int32 -
+    the target triangles every query triangle cuts -, ``first (QT)`` int32 - the lowest of them, or -1 -, ``offsets (QT + 1)`` int32 -
+    the exclusive sums of ``count`` -, ``pairs (P, 2)`` int32 = (query, target) sorted by (query, target), or None, and ``segments
+    (P, 2, 3)`` - one contact segment per pair, in the targets' frame - or None.  ``symmetric``: the result of a self-intersection
+    query, in which every unordered pair shows up twice.  ``report()`` reads the summary back."""
+    count: torch.Tensor
+    first: torch.Tensor
+    offsets: torch.Tensor
+    pairs: Optional[torch.Tensor] = None
+    segments: Optional[torch.Tensor] = None
+    symmetric: bool = False
+
+    def report(self) -> dict:
+        """``pairs`` (unordered pairs for a self-intersection query), ``query_triangles`` - query triangles that cut something -,
+        ``target_triangles`` - target triangles that are cut (None without ``pairs``) -, ``contact_length`` - the fp64 sum of the
+        segment lengths (None without ``segments``; halved for a self-intersection query) - and ``intersecting``.  ONE read-back."""
+        count = self.count.to(torch.int64)
+        values = [count.sum().to(torch.float64), (count > 0).sum().to(torch.float64)]
+        if self.pairs is not None:
+            targets = torch.sort(self.pairs[:, 1]).values                    # (distinct values counted on the device: no shape to read back)
+            values.append(((targets[1:] != targets[:-1]).sum() + min(targets.numel(), 1)).to(torch.float64))
+        if self.segments is not None:
+            d = self.segments.to(torch.float64)
+            values.append((d[:, 1] - d[:, 0]).square().sum(dim=1).sqrt().sum())
+        values = torch.stack(values).cpu().tolist()                          # (the host synchronisation)
+        share = 2 if self.symmetric else 1
+        pairs = int(values[0]) // share
+        out = {"pairs": pairs, "query_triangles": int(values[1]), "target_triangles": None, "contact_length": None,
+               "intersecting": pairs > 0}
+        at = 2
+        if self.pairs is not None:
+            out["target_triangles"] = int(values[at])
+            at += 1
+        if self.segments is not None:
+            out["contact_length"] = values[at] / share
+        return out
+
+
+def _pose_rows(transform, groups: int, dev) -> Optional[torch.Tensor]:
+    """``transform`` as ``(G, 3, 4)`` fp32 rows: one ``(3, 4)`` / ``(4, 4)`` matrix for every group, or ``(G, 3, 4)`` / ``(G, 4, 4)``."""
+    if transform is None:
+        return None
+    m = torch.as_tensor(transform, dtype=torch.float32, device=dev)
+    if m.dim() == 2:
+        m = m.unsqueeze(0).expand(groups, -1, -1)
+    if m.dim() != 3 or m.size(0) != groups or m.size(1) not in (3, 4) or m.size(2) != 4:
+        raise ValueError(f"transform must be (3, 4), (4, 4), (G, 3, 4) or (G, 4, 4) with G = {groups}, got {list(m.shape)}")
+    return m[:, :3, :].contiguous()
+
+
+@dataclass
+class Collision:
+    """What ``collide`` returns: ``intersecting`` - the surfaces cut each other -, ``pairs`` - in how many triangle pairs -, and
+    ``b_in_a`` - b's first finite vertex lies inside a (None unless asked for)."""
+    intersecting: bool
+    pairs: int
+    b_in_a: Optional[bool] = None
+
+
+def collide(a, b: Mesh, *, transform=None, cells=32, inside: bool = False) -> Collision:
+    """Whether the mesh ``b``, posed by ``transform`` (``v' = R v + t``, a ``(3, 4)`` or ``(4, 4)`` matrix into a's frame, or None),
+    cuts ``a`` - a ``Mesh``, sorted into ``bounding_grid([a], cells)`` here, or a ``RayGrid`` of one group that was built once for a
+    static object.  ``intersecting`` comes from ``RayGrid.intersect`` and sees every contact of the two SURFACES, including those in
+    which no vertex of either mesh lies inside the other; a mesh swallowed whole touches nothing, so ``inside=True`` also reports
+    ``b_in_a``: ``contains`` of b's first finite posed vertex on a's grid.  That needs what ``contains`` needs of ``a`` - a capped mesh
+    (``close_border=True``) that kept its duplicates when simplified; ``a.audit().report()["balanced"]`` checks it.  A composition:
+    one counting call, one ``pr_inside_query`` with ``inside`` (``contains`` does not synchronise), and ONE read-back of both answers;
+    a ``Mesh`` given as ``a`` costs the read-backs of ``bounding_grid`` and ``RayGrid.build`` in front of that."""
+    if not isinstance(b, Mesh):
+        raise ValueError("collide needs a Mesh as its second argument")
+    if isinstance(a, Mesh):
+        if not (a.vertices.is_cuda and b.vertices.is_cuda):
+            raise RuntimeError(NO_CPU)
+        a = RayGrid.build([a], *bounding_grid([a], cells))
+    if a.groups != 1:
+        raise ValueError(f"collide needs a grid of one group, got {a.groups}")
+    contacts = a.intersect([b], transform=transform)[0]
+    values = [contacts.count.to(torch.int64).sum()]
+    if inside:
+        m = _pose_rows(transform, 1, a.vertices.device)
+        v = b.vertices.detach().to(device=a.vertices.device, dtype=torch.float32).reshape(-1, 3)
+        if m is not None:
+            v = v @ m[0, :, :3].T + m[0, :, 3]
+        if v.size(0) == 0:
+            values.append(torch.zeros((), dtype=torch.int64, device=a.vertices.device))
+        else:
+            finite = torch.isfinite(v).all(dim=1)
+            at = torch.argmax(finite.to(torch.uint8))                      # (the first finite vertex)
+            point = torch.where(finite[at], v[at], torch.full_like(v[at], math.inf))
+            values.append(a.contains(point.reshape(1, 1, 3))[0, 0].to(torch.int64))
+    values = torch.stack(values).cpu().tolist()                            # (the host synchronisation)
+    return Collision(values[0] > 0, int(values[0]), bool(values[1]) if inside else None)
 
 
 def bounding_grid(meshes: Sequence[Mesh], cells):
