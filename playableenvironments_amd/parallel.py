@@ -368,9 +368,18 @@ class ArenaAdam(torch.optim.Optimizer):
     checkpoints move between the two.  ``capturable=True`` keeps the step count on the device (a training step recorded into a
     HIP graph: ``frame_graph.GraphedStep``); ``decoupled_weight_decay=True`` is AdamW.
 
+    ``torch.amp.GradScaler.step(optimizer)`` hands the optimiser the scale and its overflow flag as the device tensors
+    ``optimizer.grad_scale`` (``None`` after an explicit ``scaler.unscale_``) and ``optimizer.found_inf``
+    (``_step_supports_amp_scaling``, the contract of torch's fused optimisers): the kernel divides the gradients by the scale and
+    skips the update on overflow.  With ``capturable=True`` both go to the kernel as pointers (no host synchronisation; the device
+    step count is not moved by a skipped step); with a host-side step count ``found_inf`` is read back once - the synchronisation
+    torch's unfused path makes - and a skipped step is not counted.
+
     >>> arena = flatten_parameters(model.object_composer)
     >>> optimizer = ArenaAdam([arena], lr=1e-4)
     >>> loss.backward(); flat_gradient(arena, model.object_composer); optimizer.step()"""
+
+    _step_supports_amp_scaling = True      # GradScaler.step leaves unscaling and the overflow check to step()
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  amsgrad: bool = False, *, maximize: bool = False, capturable: bool = False, decoupled_weight_decay: bool = False):
@@ -383,13 +392,16 @@ class ArenaAdam(torch.optim.Optimizer):
         super().__init__(params, defaults)
 
     @torch.no_grad()
-    def step(self, closure=None, *, grad_scaler=None):
+    def step(self, closure=None):
         loss = None
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
         from . import _lib
         lib = _lib.load()
+        # (set by torch.amp.GradScaler.step for the duration of this call)
+        grad_scale, found_inf = getattr(self, "grad_scale", None), getattr(self, "found_inf", None)
+        overflow = None          # found_inf read back, once, for the parameters whose step count lives on the host
         for group in self.param_groups:
             beta1, beta2 = group["betas"]
             lr = group["lr"]
@@ -406,6 +418,10 @@ class ArenaAdam(torch.optim.Optimizer):
                     raise RuntimeError("ArenaAdam: the gradient must be a dense fp32 tensor on the parameter's device")
                 if not g.is_contiguous():
                     g = g.contiguous()
+                for name, t in (("grad_scale", grad_scale), ("found_inf", found_inf)):
+                    if t is not None and not (torch.is_tensor(t) and t.dtype == torch.float32 and t.numel() == 1 and t.device == p.device):
+                        raise RuntimeError(f"ArenaAdam: {name} must be one fp32 value in a tensor on the parameter's device "
+                                           "(torch.amp.GradScaler.step sets it)")
                 state = self.state[p]
                 if len(state) == 0:
                     state["step"] = torch.zeros((), dtype=torch.float32, device=p.device if group["capturable"] else "cpu")
@@ -414,12 +430,19 @@ class ArenaAdam(torch.optim.Optimizer):
                 step = state["step"]
                 on_device = step.is_cuda
                 if not on_device:
+                    if found_inf is not None:
+                        if overflow is None:
+                            overflow = bool(found_inf.item() != 0)       # (a NaN counts as an overflow, as in the kernel)
+                        if overflow:
+                            continue
                     step += 1
                 with torch.cuda.device(p.device):
                     _lib.check(lib.pr_adam_step(p.data_ptr(), g.data_ptr(), state["exp_avg"].data_ptr(), state["exp_avg_sq"].data_ptr(),
                                                 p.numel(), lr, beta1, beta2, group["eps"], group["weight_decay"],
                                                 1 if group["decoupled_weight_decay"] else 0, 1 if group["maximize"] else 0,
-                                                0.0 if on_device else float(step), step.data_ptr() if on_device else None, None, None,
+                                                0.0 if on_device else float(step), step.data_ptr() if on_device else None,
+                                                None if grad_scale is None else grad_scale.data_ptr(),
+                                                found_inf.data_ptr() if on_device and found_inf is not None else None,
                                                 torch.cuda.current_stream(p.device).cuda_stream), "pr_adam_step")
                 # (the kernel wrote through a raw pointer: tell autograd's version counter, which the renderer's packed-weight
                 # cache and the saved-tensor checks key on)

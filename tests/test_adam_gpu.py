@@ -1,0 +1,328 @@
+"""``pr_adam_step`` on the GPU (python -m pytest tests -m gpu), straight through the C ABI, against the float64 Adam of
+tests/adam_reference.py within the tolerances derived there.  Each of the four arrays (and every device scalar) lives inside a larger
+allocation filled with a NaN bit pattern, at least 8 guard floats on both sides; after EVERY call the guards and ``grad`` must be
+untouched bit for bit and ``p, m, v`` within the tolerances of the float64 step taken from the device's own input state (multi-step
+tests restart the reference from the device's state, so errors do not compound).  Covered: the ``float4`` path and the scalar path the
+kernel takes when any pointer is not 16-byte aligned (each pointer alone - a lone misaligned ``grad`` is what ``parallel.flat_gradient``
+produces -, all four by 1, 2 and 3 floats) at the seams of a ``float4``, a wave and a workgroup; a size above the cap of 2048 workgroups;
+the modes, betas of 0 and a tiny eps on three families of state; the step count by value and on the device; the GradScaler arms
+(``grad_scale``, ``found_inf``); non-finite gradients; equal bits from call to call and between the two paths; and
+``torch.amp.GradScaler.step(ArenaAdam)`` against ``GradScaler.step(torch.optim.Adam(fused=True))``.
+
+Measured on an MI355X over the 553 kernel calls of this module (``_report`` prints both with ``pytest -s``): the largest
+error / tolerance is 0.466 for ``p``, 0.495 for ``m`` and 0.328 for ``v`` (``adam_step_fp32`` on the CPU: 0.47, 0.54, 0.61 on the same
+inputs), and 0 of 53 844 945 values differ in bits from ``adam_step_fp32`` - NaNs compared as equal: 180 NaNs of the non-finite-gradient
+test differ from the host's in sign or payload, which is the processor's choice.  The second number is a diagnostic and is never asserted."""
+import functools
+import inspect
+
+import numpy as np
+import pytest
+import torch
+
+from playableenvironments_amd import _lib
+from tests import adam_reference as ar
+
+pytestmark = pytest.mark.gpu
+
+F = np.float32
+POISON = 0x7FC0DEAD                # a NaN as fp32
+GUARD = 8                          # floats in front of and behind every array that must stay poisoned (plus up to 4 of padding)
+# The largest error / tolerance observed over every call of this module, and the number of elements (of p, m and v together) whose bits
+# differ from adam_step_fp32 - a diagnostic that is never asserted: the device's double pow may differ from the host's in the last place.
+WORST = {"p": 0.0, "m": 0.0, "v": 0.0, "bit_differences": 0, "elements": 0, "calls": 0}
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _need_gpu(built_library):
+    if not torch.cuda.is_available():
+        pytest.fail("the gpu-marked tests need a GPU: the optimiser kernel has no CPU fallback")
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _report():
+    yield
+    print(f"\npr_adam_step, {WORST['calls']} calls: worst error / tolerance p {WORST['p']:.3f} m {WORST['m']:.3f} v {WORST['v']:.3f}; "
+          f"{WORST['bit_differences']} of {WORST['elements']} values differ in bits from adam_step_fp32")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# poisoned allocations
+class Placed:
+    """``values`` (fp32) inside a poisoned allocation, ``shift`` floats past a 16-byte boundary."""
+
+    def __init__(self, values, shift=0):
+        values = np.ascontiguousarray(values, dtype=F).reshape(-1)
+        self.n, self.first = values.size, GUARD + shift
+        self.buffer = torch.full((self.n + 2 * GUARD + 4,), POISON, dtype=torch.int32, device="cuda")
+        assert self.buffer.data_ptr() % 16 == 0
+        self.view = self.buffer.view(torch.float32)[self.first:self.first + self.n]
+        self.view.copy_(torch.from_numpy(values))
+        self.sent = values.copy()
+        # the claim of the case, checked where the pointer is made
+        assert self.view.data_ptr() % 16 == 4 * shift and self.view.data_ptr() == self.buffer.data_ptr() + 4 * self.first
+        self.pointer = self.view.data_ptr()
+
+    def read(self, what):
+        """The values after a call; the guards must be what they were."""
+        words = self.buffer.cpu().numpy()
+        outside = np.concatenate([words[:self.first], words[self.first + self.n:]])
+        assert outside.size >= 2 * GUARD and (outside == POISON).all(), \
+            f"{what}: guard words written at {np.flatnonzero(outside != POISON)[:8]} (of {self.first} in front, {outside.size - self.first} behind)"
+        return words[self.first:self.first + self.n].view(F).copy()
+
+    def unchanged(self, what):
+        assert np.array_equal(self.read(what).view(np.uint32), self.sent.view(np.uint32)), f"{what} was written"
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=F).view(np.uint32)
+
+
+def device_step(p, g, m, v, shifts=(0, 0, 0, 0), *, step=None, step_device=None, grad_scale=None, found_inf=None, **hyper):
+    """One ``pr_adam_step`` on poisoned allocations; returns what the device holds afterwards.  Checked here: the status, every guard,
+    ``grad``, the scale and the flag untouched."""
+    lib = _lib.load()
+    P, G, M, V = (Placed(a, s) for a, s in zip((p, g, m, v), shifts))
+    count = None if step_device is None else Placed([step_device], 1)
+    scale = None if grad_scale is None else Placed([grad_scale], 3)
+    flag = None if found_inf is None else Placed([found_inf], 2)
+    pointer = lambda x: None if x is None else x.pointer
+    status = lib.pr_adam_step(P.pointer, G.pointer, M.pointer, V.pointer, P.n, hyper["lr"], hyper["beta1"], hyper["beta2"], hyper["eps"],
+                              hyper.get("weight_decay", 0.0), int(hyper.get("decoupled", False)), int(hyper.get("maximize", False)),
+                              0.0 if step is None else float(step), pointer(count), pointer(scale), pointer(flag),
+                              torch.cuda.current_stream().cuda_stream)
+    _lib.check(status, "pr_adam_step")
+    torch.cuda.synchronize()
+    G.unchanged("grad")
+    for name, scalar in (("grad_scale", scale), ("found_inf", flag)):
+        if scalar is not None:
+            scalar.unchanged(name)
+    return ar.AdamStep(P.read("param"), M.read("exp_avg"), V.read("exp_avg_sq"), None if count is None else count.read("step")[0])
+
+
+def checked_step(p, g, m, v, shifts=(0, 0, 0, 0), want=None, fp32=None, **kw):
+    """``device_step`` held to the float64 step from the same inputs: within the tolerances where the reference is finite, non-finite
+    exactly where the reference is, the device count as the reference counts."""
+    got = device_step(p, g, m, v, shifts, **kw)
+    want = ar.adam_step_float64(p, g, m, v, **kw) if want is None else want
+    fp32 = ar.adam_step_fp32(p, g, m, v, **kw) if fp32 is None else fp32
+    # (two NaNs count as equal: the sign and payload of a NaN that an operation makes are the processor's choice)
+    differ = sum(int(((bits(getattr(got, k)) != bits(getattr(fp32, k))) & ~(np.isnan(getattr(got, k)) & np.isnan(getattr(fp32, k)))).sum())
+                 for k in ("p", "m", "v"))
+    r = ar.ratios(got, want)
+    for key, ratio in zip(("p", "m", "v"), r):
+        WORST[key] = max(WORST[key], ratio)
+    WORST["bit_differences"] += differ
+    WORST["elements"] += 3 * got.p.size
+    WORST["calls"] += 1
+    what = f"shifts {shifts} n {got.p.size} {kw}: error / tolerance (p, m, v) = {r}; {differ} of {3 * got.p.size} values differ in bits from adam_step_fp32"
+    for key in ("p", "m", "v"):
+        assert np.array_equal(np.isfinite(getattr(got, key)), np.isfinite(getattr(want, key))), f"{key}: non-finite elements; {what}"
+    assert max(r) <= 1.0, what
+    if want.step_device is None:
+        assert got.step_device is None
+    else:
+        assert bits(got.step_device) == bits(want.step_device), (got.step_device, want.step_device)
+    return got
+
+
+def same_bits(a, b, what):
+    for key in ("p", "m", "v"):
+        x, y = bits(getattr(a, key)), bits(getattr(b, key))
+        assert np.array_equal(x, y), f"{what}: {key} differs in {int((x != y).sum())} of {x.size} elements, first at {int(np.flatnonzero(x != y)[0])}"
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+ALIGNMENTS = {"aligned": (0, 0, 0, 0), "param+1": (1, 0, 0, 0), "grad+1": (0, 1, 0, 0), "exp_avg+1": (0, 0, 1, 0), "exp_avg_sq+1": (0, 0, 0, 1),
+              "all+1": (1, 1, 1, 1), "all+2": (2, 2, 2, 2), "all+3": (3, 3, 3, 3)}
+
+
+@pytest.mark.parametrize("case", list(ALIGNMENTS))
+def test_alignment(case):
+    """The ``float4`` path (all four pointers 16-byte aligned) and the scalar path (any one is not) at the seams of a ``float4``, of a wave
+    and of a workgroup's 1024 elements; both paths give the same bits."""
+    shifts = ALIGNMENTS[case]
+    kw = dict(ar.MODES["l2"], step=3)
+    for n in ar.SIZES:
+        p, g, m, v = ar.inputs("wide", n, 0)
+        want, fp32 = ar.adam_step_float64(p, g, m, v, **kw), ar.adam_step_fp32(p, g, m, v, **kw)
+        got = checked_step(p, g, m, v, shifts, want=want, fp32=fp32, **kw)
+        other = checked_step(p, g, m, v, ALIGNMENTS["all+2" if case == "aligned" else "aligned"], want=want, fp32=fp32, **kw)
+        same_bits(got, other, f"{case} against the other path, n {n}")
+        if case == "aligned":
+            same_bits(got, checked_step(p, g, m, v, shifts, want=want, fp32=fp32, **kw), f"call to call, n {n}")
+
+
+LARGE = 8388608 + 4099             # 2048 workgroups x 256 threads x 4 float4 x 4, and a tail: the grid-stride loop makes a second round
+
+
+@functools.lru_cache(maxsize=None)
+def _large_case():
+    p, g, m, v = ar.inputs("wide", LARGE, 2)
+    kw = dict(ar.MODES["l2"], lr=1e-2, step=3)
+    return (p, g, m, v), kw, ar.adam_step_float64(p, g, m, v, **kw), ar.adam_step_fp32(p, g, m, v, **kw)
+
+
+@pytest.mark.parametrize("case", ["aligned", "grad+1"])
+def test_above_the_block_cap(case):
+    """More elements than 2048 workgroups cover in one round: every element is updated exactly once.  A missing update is outside the
+    tolerance at every element and a hundred times outside it at all but a few in a million (one update moves a parameter by about
+    lr = 1e-2 against a tolerance of a few 1e-7 of it, and moves ``m`` and ``v`` by far more than their roundings); a second update
+    moves the state by as much again."""
+    (p, g, m, v), kw, want, fp32 = _large_case()
+    moved = lambda times: np.logical_or.reduce([np.abs(getattr(want, k) - old.astype(np.float64)) > times * getattr(want, "tol_" + k)
+                                                for k, old in (("p", p), ("m", m), ("v", v))])
+    assert moved(1).all() and (~moved(100)).mean() < 1e-5           # (what makes the sentences above true for these inputs)
+    checked_step(p, g, m, v, ALIGNMENTS[case], want=want, fp32=fp32, **kw)
+
+
+@pytest.mark.parametrize("family", ar.FAMILIES)
+@pytest.mark.parametrize("mode", list(ar.MODES))
+def test_modes(mode, family):
+    """Plain, L2, decoupled, maximize, betas of 0, eps from 1e-15 to 1e-3 on gradients from 1e-12 to 1e6, over zero state, wide state and
+    ``m`` within ulps of ``g``; three steps, each held to the float64 step from the device's own state, on both paths."""
+    p, g, m, v = ar.inputs(family, 4099, 1)
+    for shifts in (ALIGNMENTS["aligned"], ALIGNMENTS["grad+1"]):
+        state = ar.AdamStep(p, m, v, None)
+        for t in (1, 2, 3):
+            gt = g if t == 1 else ar.inputs(family, 4099, 1 + t)[1]
+            state = checked_step(state.p, gt, state.m, state.v, shifts, step=t, **ar.MODES[mode])
+
+
+@pytest.mark.parametrize("t", ar.STEPS)
+def test_step_count_by_value(t):
+    """The bias corrections from the first step to 2^24 (where ``beta^t`` has long been 0): ``1 - beta^t`` needs the power in double."""
+    p, g, m, v = ar.inputs("wide", 1025, 1)
+    for mode in ("plain", "lr_one", "beta2_near_one", "eps_tiny"):
+        for shifts in (ALIGNMENTS["aligned"], ALIGNMENTS["all+1"]):
+            checked_step(p, g, m, v, shifts, step=t, **ar.MODES[mode])
+
+
+@pytest.mark.parametrize("before", [0.0, 999.0])
+def test_step_count_on_the_device(before):
+    """A device count is incremented first and holds the new count afterwards; the update is the by-value call's with that count, bit for
+    bit (the same kernel, the same corrections)."""
+    p, g, m, v = ar.inputs("wide", 1025, 1)
+    for shifts in (ALIGNMENTS["aligned"], ALIGNMENTS["grad+1"]):
+        on_device = checked_step(p, g, m, v, shifts, step_device=F(before), **ar.MODES["l2"])
+        assert on_device.step_device == F(before + 1)
+        by_value = checked_step(p, g, m, v, shifts, step=before + 1, **ar.MODES["l2"])
+        same_bits(on_device, by_value, f"device count {before} + 1 against step = {before + 1}")
+
+
+@pytest.mark.parametrize("scale", ar.SCALES)
+def test_grad_scale(scale):
+    """The gradients are divided by ``*grad_scale`` (a power of two, 3 and 1e-3) on both paths, with and without a clear ``found_inf``,
+    with the count by value and on the device."""
+    p, g, m, v = ar.inputs("wide", 1025, 1)
+    for mode in ("plain", "l2", "maximize_l2", "decoupled"):
+        for shifts in (ALIGNMENTS["aligned"], ALIGNMENTS["grad+1"]):
+            a = checked_step(p, g, m, v, shifts, step=3, grad_scale=scale, **ar.MODES[mode])
+            b = checked_step(p, g, m, v, shifts, step=3, grad_scale=scale, found_inf=0.0, **ar.MODES[mode])
+            c = checked_step(p, g, m, v, shifts, step_device=F(2.0), grad_scale=scale, found_inf=0.0, **ar.MODES[mode])
+            same_bits(a, b, "found_inf = 0")
+            same_bits(a, c, "found_inf = 0, device count")
+            assert c.step_device == F(3.0)
+    # a power of two only moves the exponent: scaled gradients give the bits of the unscaled ones
+    if scale == 65536.0:
+        same_bits(checked_step(p, g * F(scale), m, v, step=3, grad_scale=scale, **ar.MODES["plain"]),
+                  checked_step(p, g, m, v, step=3, **ar.MODES["plain"]), "grad x 65536 / 65536")
+
+
+@pytest.mark.parametrize("flag", [1.0, float("nan")])
+def test_found_inf_skips_the_update(flag):
+    """A set ``found_inf`` (a NaN included) leaves ``p, m, v`` bit for bit and does not move a device count - with a scale and without."""
+    p, g, m, v = ar.inputs("wide", 1025, 1)
+    g[::7] = np.inf
+    for scale in (65536.0, None):
+        for shifts in (ALIGNMENTS["aligned"], ALIGNMENTS["grad+1"]):
+            for count in (dict(step=3), dict(step_device=F(2.0))):
+                got = checked_step(p, g, m, v, shifts, grad_scale=scale, found_inf=flag, **count, **ar.MODES["l2"])
+                same_bits(got, ar.AdamStep(p, m, v, None), f"found_inf = {flag}, scale {scale}, {count}")
+                assert got.step_device is None or bits(got.step_device) == bits(F(2.0))
+
+
+@pytest.mark.parametrize("bad", [float("nan"), float("inf"), float("-inf")])
+def test_non_finite_gradients_stay_in_their_element(bad):
+    """Without ``found_inf`` a NaN or infinite gradient makes exactly its own element's ``p, m, v`` non-finite, at each position of a
+    ``float4`` and in the tail; every neighbour is within tolerance."""
+    n = 4 * 9 + 3
+    for mode in ("plain", "l2", "decoupled", "maximize", "beta1_zero", "beta2_zero"):
+        for shifts in (ALIGNMENTS["aligned"], ALIGNMENTS["grad+1"]):
+            p, g, m, v = ar.inputs("wide", n, 5)
+            where = np.array([0, 4 + 1, 8 + 2, 12 + 3, n - 1])
+            g[where] = bad
+            got = checked_step(p, g, m, v, shifts, step=2, **ar.MODES[mode])          # (non-finite exactly where the reference is)
+            hit = np.zeros(n, bool)
+            hit[where] = True
+            for key in ("p", "m", "v"):
+                assert np.array_equal(~np.isfinite(getattr(got, key)), hit), (mode, shifts, key)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("route", ["host_count", "capturable", "unscale_first"])
+def test_grad_scaler_drives_arena_adam(route):
+    """``torch.amp.GradScaler.step(ArenaAdam)`` against ``GradScaler.step(torch.optim.Adam(fused=True))`` on equal parameters and scaled
+    gradients over 5 steps, one of them with an infinite gradient: each step's parameters within the float64 bound (the reference gets
+    the unscaled gradient and this optimiser's own state), equal step counts with the skipped step not counted, equal scales after
+    ``update()``."""
+    from playableenvironments_amd import parallel
+    assert "grad_scaler" not in inspect.signature(parallel.ArenaAdam.step).parameters
+    hyper = dict(ar.MODES["l2"])
+    kw = dict(lr=hyper["lr"], betas=(hyper["beta1"], hyper["beta2"]), eps=hyper["eps"], weight_decay=hyper["weight_decay"])
+    capturable = route == "capturable"
+    n = 4099
+    start, _, _, _ = ar.inputs("wide", n, 6)
+    mine_p, theirs_p = (torch.nn.Parameter(torch.from_numpy(start).cuda()) for _ in range(2))
+    mine = parallel.ArenaAdam([mine_p], capturable=capturable, **kw)
+    theirs = torch.optim.Adam([theirs_p], fused=True, capturable=capturable, **kw)
+    scalers = [torch.amp.GradScaler("cuda", init_scale=1024.0, growth_interval=2) for _ in range(2)]
+    for scaler in scalers:
+        scaler.scale(torch.zeros((), device="cuda"))       # (the scale tensor is made by the first loss that is scaled)
+    counted = 0
+    for step in range(5):
+        unscaled = (np.random.default_rng(step).normal(size=n) * 10.0 ** (step - 3)).astype(F)
+        scale = float(scalers[0].get_scale())
+        assert scale == float(scalers[1].get_scale())
+        scaled = unscaled * F(scale)                    # (a power of two: exact)
+        if step == 2:
+            scaled[n // 2] = np.inf
+        before = {k: t.detach().cpu().numpy().copy() for k, t in
+                  (("p", mine_p), ("m", mine.state[mine_p].get("exp_avg", torch.zeros(n))), ("v", mine.state[mine_p].get("exp_avg_sq", torch.zeros(n))))}
+        for p, opt, scaler in ((mine_p, mine, scalers[0]), (theirs_p, theirs, scalers[1])):
+            p.grad = torch.from_numpy(scaled).cuda()
+            if route == "unscale_first":
+                scaler.unscale_(opt)
+            scaler.step(opt)
+            scaler.update()
+        assert not hasattr(mine, "grad_scale") and not hasattr(mine, "found_inf")
+        counted += step != 2
+        assert float(mine.state[mine_p]["step"]) == float(theirs.state[theirs_p]["step"]) == counted
+        assert mine.state[mine_p]["step"].is_cuda == capturable
+        assert float(scalers[0].get_scale()) == float(scalers[1].get_scale())
+        got = ar.AdamStep(mine_p.detach().cpu().numpy(), mine.state[mine_p]["exp_avg"].cpu().numpy(), mine.state[mine_p]["exp_avg_sq"].cpu().numpy(), None)
+        if step == 2:
+            same_bits(got, ar.AdamStep(before["p"], before["m"], before["v"], None), "the skipped step")
+            assert float(scalers[0].get_scale()) == scale / 2
+            continue
+        want = ar.adam_step_float64(before["p"], unscaled, before["m"], before["v"], step=counted, **hyper)
+        r = ar.ratios(got, want)
+        assert max(r) <= 1.0, (route, step, r)
+        # torch's fused kernel on its own state: the same optimiser to fp32 round-off
+        assert torch.allclose(mine_p.detach(), theirs_p.detach(), rtol=1e-5, atol=1e-6), (route, step)
+    assert float(scalers[0].get_scale()) != 1024.0
+
+    with pytest.raises(RuntimeError, match="grad_scale must be one fp32 value"):
+        mine_p.grad = torch.zeros(n, device="cuda")
+        mine.grad_scale, mine.found_inf = torch.ones((), dtype=torch.float64, device="cuda"), None
+        try:
+            mine.step()
+        finally:
+            del mine.grad_scale, mine.found_inf
+    with pytest.raises(RuntimeError, match="found_inf must be one fp32 value"):
+        mine.grad_scale, mine.found_inf = None, torch.zeros(())
+        try:
+            mine.step()
+        finally:
+            del mine.grad_scale, mine.found_inf

@@ -2638,7 +2638,12 @@ def test_arena_adam_matches_torch_adam(mode):
     for n in sizes:
         base.append(storage[at:at + n])
         at += n
-    mine_p = [torch.nn.Parameter(b.clone()) for b in base]
+    def odd(t):         # a copy as a view one float into a storage of its own (a clone would be a fresh, aligned allocation)
+        own = torch.empty(t.numel() + 1, device=t.device)
+        own[1:] = t
+        return own[1:]
+    mine_p = [torch.nn.Parameter(odd(b)) for b in base]
+    assert all(p.data_ptr() % 16 == 4 and p.storage_offset() == 1 for p in mine_p)      # pr_adam_step's scalar path
     theirs_p = [torch.nn.Parameter(b.clone()) for b in base]
     mine_kw = dict(kw, decoupled_weight_decay=(mode == "adamw"), capturable=(mode == "capturable"))
     mine = parallel.ArenaAdam(mine_p, **mine_kw)
@@ -2646,7 +2651,8 @@ def test_arena_adam_matches_torch_adam(mode):
     for step in range(6):
         for a, b in zip(mine_p, theirs_p):
             g = torch.randn_like(a) * (10.0 ** (step - 3))
-            a.grad, b.grad = g.clone(), g.clone()
+            a.grad, b.grad = odd(g), g.clone()
+            assert a.grad.data_ptr() % 16 == 4
         versions = [p._version for p in mine_p]
         mine.step()
         theirs.step()
