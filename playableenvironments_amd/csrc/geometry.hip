@@ -830,15 +830,16 @@ __device__ __forceinline__ void project_object(int lane, int k, int objects, int
         const float py = -__fmul_rn(__fdiv_rn(-cam[1], cam[2]), focal);
         if (boxes) {
             const bool behind = cam[2] > 0.f;
-            lo_x = fminf(lo_x, behind ? 1e20f : px);
-            lo_y = fminf(lo_y, behind ? 1e20f : py);
-            hi_x = fmaxf(hi_x, behind ? -1e20f : px);
-            hi_y = fmaxf(hi_y, behind ? -1e20f : py);
+            // (torch.min / max and torch.clamp keep a NaN - a point with cam.z == 0 projects to 0 / 0 -, fminf / fmaxf would drop it)
+            lo_x = nan_min(behind ? 1e20f : px, lo_x);
+            lo_y = nan_min(behind ? 1e20f : py, lo_y);
+            hi_x = nan_max(behind ? -1e20f : px, hi_x);
+            hi_y = nan_max(behind ? -1e20f : py, hi_y);
         }
         float nx = __fdiv_rn(__fadd_rn(px, width / 2.0f), width), ny = __fdiv_rn(__fadd_rn(py, height / 2.0f), height);
         if (boxes) {
-            nx = fminf(fmaxf(nx, 0.f), 1.f);
-            ny = fminf(fmaxf(ny, 0.f), 1.f);
+            nx = nan_clamp(nx, 0.f, 1.f);
+            ny = nan_clamp(ny, 0.f, 1.f);
         }
         // (points, 2, objects)
         float* dst = out_points + ((size_t)i * 2) * objects + k;
@@ -848,10 +849,10 @@ __device__ __forceinline__ void project_object(int lane, int k, int objects, int
     if (boxes) {
 #pragma unroll
         for (int d = 32; d > 0; d >>= 1) {
-            lo_x = fminf(lo_x, __shfl_down(lo_x, d, 64));
-            lo_y = fminf(lo_y, __shfl_down(lo_y, d, 64));
-            hi_x = fmaxf(hi_x, __shfl_down(hi_x, d, 64));
-            hi_y = fmaxf(hi_y, __shfl_down(hi_y, d, 64));
+            lo_x = nan_min(lo_x, __shfl_down(lo_x, d, 64));
+            lo_y = nan_min(lo_y, __shfl_down(lo_y, d, 64));
+            hi_x = nan_max(hi_x, __shfl_down(hi_x, d, 64));
+            hi_y = nan_max(hi_y, __shfl_down(hi_y, d, 64));
         }
         if (lane == 0) {
             const float v[4] = {lo_x, lo_y, hi_x, hi_y};
@@ -859,7 +860,7 @@ __device__ __forceinline__ void project_object(int lane, int k, int objects, int
             float* dst = boxes + k;      // (4, objects)
             for (int a = 0; a < 4; ++a) {
                 const float n = __fdiv_rn(__fadd_rn(v[a], size[a] / 2.0f), size[a]);
-                dst[(size_t)a * objects] = fminf(fmaxf(n, 0.f), 1.f);
+                dst[(size_t)a * objects] = nan_clamp(n, 0.f, 1.f);
             }
         }
     }
