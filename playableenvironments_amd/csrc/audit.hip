@@ -4,7 +4,7 @@
 //
 // Nine launches on the caller's stream (eight without measures), all kernels:
 //   k_audit_init      empties both tables, zeroes the flags and the shell sizes, fills labels with -1; one lane of block 0
-//                     clamps the offsets and builds the block tables (what k_simplify_init and k_simplify_groups do)
+//                     clamps the offsets and builds the block tables (the rule: mesh_dev.h)
 //   k_audit_weld      per vertex: inserts its index into the group's open-addressing table of 2 V_g slots, keyed by the three values;
 //                     a slot only ever moves to a lower index with the SAME values, so a 32-bit word stands for the 96-bit key
 //   k_audit_lookup    per vertex: its representative = the final content of its key's slot (the lowest index with its values)
@@ -17,17 +17,16 @@
 //                     of one grid): one row of integer partial sums per block, no atomic on a shared word
 //   k_audit_measure   per triangle: the three fp64 terms, reduced per block in a fixed tree, one row of partials per block
 //   k_audit_finish    one block per group: the integer partials -> counts, the fp64 partials in a fixed order -> measures
-// Lanes: one per element, wave64, 256-lane blocks that never span two groups (block tables and bisection as in simplify.hip).  Integer
-// atomics only; the floating-point sums are trees of fixed shape.  No lane ever waits for another: a probe sequence ends after at most
-// the region's size (2 V_g slots hold at most V_g keys, 6 T_g slots at most 3 T_g), and the union-find is that of components.hip,
-// whose TERMINATION argument carries over word for word (a parent only ever decreases and stays <= its own index).
-#include "pr_common.h"
+// Lanes: one per element, wave64, 256-lane blocks that never span two groups (mesh_lane, mesh_dev.h).  Integer atomics only; the
+// floating-point sums are trees of fixed shape.  No lane ever waits for another: a probe sequence ends after at most the region's size
+// (2 V_g slots hold at most V_g keys, 6 T_g slots at most 3 T_g), and the union-find is mesh_uf_find / mesh_uf_unite, shared with
+// components.hip; mesh_dev.h holds the vertex table's rule and the union-find's TERMINATION argument.
+#include "mesh_dev.h"
 
 #include <math.h>
 
 namespace pr {
 
-constexpr int AUDIT_EMPTY_VERTEX = 0x7FFFFFFF;             // above every vertex index: an atomic minimum can only lower a slot
 constexpr unsigned long long AUDIT_EMPTY_EDGE = ~0ull;     // (a key has 62 bits)
 constexpr int AUDIT_NO_TRIANGLE = 0x7FFFFFFF;
 constexpr int AUDIT_COUNTS = 12, AUDIT_MEASURES = 8, AUDIT_TERMS = 5;
@@ -58,41 +57,10 @@ struct AuditParams {
     int32_t* vpart;               // (BV) per vertex block: referenced representatives
 };
 
-struct AuditLane {
-    int group;                    // -1: the block lies behind the last group
-    int first, size;              // the group's first row and its rows
-    int local;                    // row inside the group
-    bool live;
-};
-
-// the lane of block `b` of a vertex or triangle grid: `blk` / `first` are the block table and the clamped offsets of that kind
-__device__ __forceinline__ AuditLane audit_lane(int groups, const int32_t* blk, const int32_t* first, int b) {
-    AuditLane l;
-    const PR_GLOBAL_AS int32_t* table = as_global(blk);
-    l.group = -1;
-    l.first = l.size = l.local = 0;
-    l.live = false;
-    if (b >= table[groups]) return l;
-    int lo = 0, hi = groups;                  // table[lo] <= b < table[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (table[mid] <= b) lo = mid;
-        else hi = mid;
-    }
-    l.group = lo;
-    l.first = as_global(first)[lo];
-    l.size = as_global(first)[lo + 1] - l.first;
-    l.local = (b - table[lo]) * 256 + (int)threadIdx.x;
-    l.live = l.local < l.size;
-    return l;
-}
-
-__device__ __forceinline__ bool audit_finite(float x) { return __fsub_rn(x, x) == 0.f; }
-
 __global__ __launch_bounds__(256) void k_audit_init(AuditParams s) {
     const size_t stride = (size_t)gridDim.x * 256, at = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t V = (size_t)s.V, T = (size_t)s.T;
-    for (size_t i = at; i < 2 * V; i += stride) as_global(s.vslot)[i] = AUDIT_EMPTY_VERTEX;
+    for (size_t i = at; i < 2 * V; i += stride) as_global(s.vslot)[i] = MESH_EMPTY_VERTEX;
     for (size_t i = at; i < V; i += stride) as_global(s.vref)[i] = 0;
     for (size_t i = at; i < 6 * T; i += stride) {
         as_global(s.ekey)[i] = AUDIT_EMPTY_EDGE;
@@ -123,48 +91,19 @@ __global__ __launch_bounds__(256) void k_audit_init(AuditParams s) {
     }
 }
 
-struct AuditVertex {
-    float x[3];
-    bool finite;
-    unsigned int at;              // first slot of the probe sequence (local to the group's region)
-};
-
-// the values of vertex `row` and the start of its probe sequence in a region of `size` slots; -0 hashes as +0 (they compare equal)
-__device__ __forceinline__ AuditVertex audit_vertex(const AuditParams& s, size_t row, unsigned int size) {
-    AuditVertex v;
-    unsigned int bits[3];
-    v.finite = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        v.x[a] = as_global(s.vertices)[row * 3 + a];
-        v.finite = v.finite && audit_finite(v.x[a]);
-        bits[a] = v.x[a] == 0.f ? 0u : __float_as_uint(v.x[a]);
-    }
-    const unsigned long long h = noise_mix(noise_mix((unsigned long long)bits[0] | (unsigned long long)bits[1] << 32) ^ bits[2]);
-    v.at = size ? (unsigned int)(h % size) : 0u;
-    return v;
-}
-
-// whether vertex `index` (local, read from a slot: checked here) of the group that starts at row `first` has the values of `v`
-__device__ __forceinline__ bool audit_same_values(const AuditParams& s, int first, int size, int index, const AuditVertex& v) {
-    if ((unsigned)index >= (unsigned)size) return false;
-    const PR_GLOBAL_AS float* o = as_global(s.vertices) + ((size_t)first + index) * 3;
-    return o[0] == v.x[0] && o[1] == v.x[1] && o[2] == v.x[2];
-}
-
 __global__ __launch_bounds__(256) void k_audit_weld(AuditParams s) {
-    const AuditLane l = audit_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
+    const MeshLane l = mesh_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
     if (!l.live) return;
     const unsigned int size = 2u * (unsigned int)l.size;
-    const AuditVertex v = audit_vertex(s, (size_t)l.first + l.local, size);
+    const MeshVertex v = mesh_vertex(s.vertices, (size_t)l.first + l.local, size);
     if (!v.finite) return;                    // (not inserted: it has no class)
     PR_GLOBAL_AS int32_t* region = as_global(s.vslot) + 2 * (size_t)l.first;
     unsigned int at = v.at;
     for (unsigned int probe = 0; probe < size; ++probe) {      // (ends at an empty slot or at the class: at most V_g classes in 2 V_g slots)
-        int seen = AUDIT_EMPTY_VERTEX;
+        int seen = MESH_EMPTY_VERTEX;
         if (__hip_atomic_compare_exchange_strong(region + at, &seen, l.local, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
             return;
-        if (audit_same_values(s, l.first, l.size, seen, v)) {
+        if (mesh_same_values(s.vertices, l.first, l.size, seen, v)) {
             __hip_atomic_fetch_min(region + at, l.local, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             return;
         }
@@ -173,19 +112,19 @@ __global__ __launch_bounds__(256) void k_audit_weld(AuditParams s) {
 }
 
 __global__ __launch_bounds__(256) void k_audit_lookup(AuditParams s) {
-    const AuditLane l = audit_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
+    const MeshLane l = mesh_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
     if (!l.live) return;
     const unsigned int size = 2u * (unsigned int)l.size;
     const size_t row = (size_t)l.first + l.local;
-    const AuditVertex v = audit_vertex(s, row, size);
+    const MeshVertex v = mesh_vertex(s.vertices, row, size);
     int rep = -1;
     if (v.finite) {
         const PR_GLOBAL_AS int32_t* region = as_global(s.vslot) + 2 * (size_t)l.first;
         unsigned int at = v.at;
         for (unsigned int probe = 0; probe < size; ++probe) {  // (the weld kernel has finished: the slots hold the minima)
             const int seen = region[at];
-            if (seen == AUDIT_EMPTY_VERTEX) break;
-            if (audit_same_values(s, l.first, l.size, seen, v)) {
+            if (seen == MESH_EMPTY_VERTEX) break;
+            if (mesh_same_values(s.vertices, l.first, l.size, seen, v)) {
                 rep = seen;
                 break;
             }
@@ -197,7 +136,7 @@ __global__ __launch_bounds__(256) void k_audit_lookup(AuditParams s) {
 
 __global__ __launch_bounds__(256) void k_audit_edges(AuditParams s) {
     __shared__ int lds[4];
-    const AuditLane l = audit_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
+    const MeshLane l = mesh_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
     if (l.group < 0) return;                  // (the whole block)
     bool candidate = false;
     if (l.live) {
@@ -254,35 +193,8 @@ __global__ __launch_bounds__(256) void k_audit_edges(AuditParams s) {
     }
 }
 
-// (reads that race with the unite kernel's atomics go to the coherent level; a stale value is an ancestor in an earlier forest)
-__device__ __forceinline__ int audit_parent(const PR_GLOBAL_AS int32_t* slot) {
-    return __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ int audit_find(const PR_GLOBAL_AS int32_t* parent, int x) {
-    // x strictly falls; the unsigned comparison also ends the walk on a negative value, which no candidate's chain holds
-    for (int up = audit_parent(parent + x); (unsigned)up < (unsigned)x; up = audit_parent(parent + x)) x = up;
-    return x;
-}
-
-__device__ __forceinline__ void audit_unite(PR_GLOBAL_AS int32_t* parent, int a, int b) {
-    a = audit_find(parent, a);
-    b = audit_find(parent, b);
-    while (a != b) {                               // a + b strictly falls
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int was = __hip_atomic_fetch_min(parent + a, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (was == a) return;                      // a was a root and now hangs under b
-        a = audit_find(parent, was);               // was < a: somebody re-parented a first - that parent must meet b too
-        b = audit_find(parent, b);
-    }
-}
-
 __global__ __launch_bounds__(256) void k_audit_unite(AuditParams s) {
-    const AuditLane l = audit_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
+    const MeshLane l = mesh_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
     if (!l.live) return;
     const size_t row = (size_t)l.first + l.local;
     PR_GLOBAL_AS int32_t* parent = as_global(s.parent) + l.first;
@@ -294,19 +206,19 @@ __global__ __launch_bounds__(256) void k_audit_unite(AuditParams s) {
         if (slot < lowest || slot >= highest) continue;
         const int owner = as_global(s.eown)[slot];
         // the owner is a candidate of this group with a side on the same edge, and no higher than this triangle
-        if (owner >= 0 && owner < l.local && parent[owner] >= 0) audit_unite(parent, l.local, owner);
+        if (owner >= 0 && owner < l.local && parent[owner] >= 0) mesh_uf_unite(parent, l.local, owner);
     }
 }
 
 __global__ __launch_bounds__(256) void k_audit_flatten(AuditParams s) {
     __shared__ int block_root, block_sum;
-    const AuditLane l = audit_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
+    const MeshLane l = mesh_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
     if (l.group < 0) return;                  // (the whole block)
     PR_GLOBAL_AS int32_t* parent = as_global(s.parent) + l.first;
     PR_GLOBAL_AS int32_t* size = as_global(s.tsize) + l.first;
     int root = -1;
     if (l.live && parent[l.local] >= 0) {
-        root = audit_find(parent, l.local);   // (no unions in this kernel: the roots are final)
+        root = mesh_uf_find(parent, l.local);   // (no unions in this kernel: the roots are final)
         parent[l.local] = root;
     }
     if (l.live && s.labels) as_global(s.labels)[(size_t)l.first + l.local] = root;
@@ -345,7 +257,7 @@ __global__ __launch_bounds__(256) void k_audit_count(AuditParams s) {
     __shared__ int block_largest;
     const int b = (int)blockIdx.x;
     if (b >= s.BT) {
-        const AuditLane l = audit_lane(s.groups, s.vblk, s.vfirst, b - s.BT);
+        const MeshLane l = mesh_lane(s.groups, s.vblk, s.vfirst, b - s.BT);
         if (l.group < 0) return;              // (the whole block)
         int referenced = 0, total;
         if (l.live) {
@@ -356,7 +268,7 @@ __global__ __launch_bounds__(256) void k_audit_count(AuditParams s) {
         if (threadIdx.x == 0) as_global(s.vpart)[b - s.BT] = total;
         return;
     }
-    const AuditLane l = audit_lane(s.groups, s.tblk, s.tfirst, b);
+    const MeshLane l = mesh_lane(s.groups, s.tblk, s.tfirst, b);
     if (l.group < 0) return;                  // (the whole block)
     int sum[5] = {0, 0, 0, 0, 0};
     const long long slots = 6 * (long long)l.size, begin = 6 * (long long)(l.local - (int)threadIdx.x);
@@ -404,7 +316,7 @@ __device__ __forceinline__ double audit_block_sum(double x, double* lds) {
 
 __global__ __launch_bounds__(256) void k_audit_measure(AuditParams s) {
     __shared__ double lds[4];
-    const AuditLane l = audit_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
+    const MeshLane l = mesh_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
     if (l.group < 0) return;                  // (the whole block)
     double term[AUDIT_TERMS] = {0.0, 0.0, 0.0, 0.0, 0.0};
     if (l.live && as_global(s.parent)[(size_t)l.first + l.local] >= 0) {       // a candidate: its indices are in range
@@ -504,12 +416,6 @@ struct AuditPlan {
     int BV, BT;
 };
 
-static size_t audit_region(size_t* at, size_t bytes) {
-    const size_t begin = *at;
-    *at += (bytes + 255) / 256 * 256;
-    return begin;
-}
-
 // Host checks of both entry points: no device work.
 static int plan_audit(const pr_mesh_audit_t* s, const char* who, AuditPlan* plan) {
     PR_REQUIRE(s != nullptr, "%s: NULL description", who);
@@ -530,22 +436,22 @@ static int plan_audit(const pr_mesh_audit_t* s, const char* who, AuditPlan* plan
     const size_t V = (size_t)s->total_vertices, T = (size_t)s->total_triangles;
     const size_t table = ((size_t)s->groups + 1) * sizeof(int32_t);
     size_t at = 0;
-    plan->vfirst = audit_region(&at, table);
-    plan->tfirst = audit_region(&at, table);
-    plan->vblk = audit_region(&at, table);
-    plan->tblk = audit_region(&at, table);
-    plan->vslot = audit_region(&at, 8 * V);
-    plan->vrep = audit_region(&at, 4 * V);
-    plan->vref = audit_region(&at, 4 * V);
-    plan->ekey = audit_region(&at, 48 * T);
-    plan->ecnt = audit_region(&at, 48 * T);
-    plan->eown = audit_region(&at, 24 * T);
-    plan->tslot = audit_region(&at, 12 * T);
-    plan->parent = audit_region(&at, 4 * T);
-    plan->tsize = audit_region(&at, 4 * T);
-    plan->partial = audit_region(&at, (size_t)AUDIT_TERMS * sizeof(double) * (size_t)plan->BT);
-    plan->tpart = audit_region(&at, (size_t)AUDIT_PARTIALS * sizeof(int32_t) * (size_t)plan->BT);
-    plan->vpart = audit_region(&at, sizeof(int32_t) * (size_t)plan->BV);
+    plan->vfirst = workspace_region(&at, table);
+    plan->tfirst = workspace_region(&at, table);
+    plan->vblk = workspace_region(&at, table);
+    plan->tblk = workspace_region(&at, table);
+    plan->vslot = workspace_region(&at, 8 * V);
+    plan->vrep = workspace_region(&at, 4 * V);
+    plan->vref = workspace_region(&at, 4 * V);
+    plan->ekey = workspace_region(&at, 48 * T);
+    plan->ecnt = workspace_region(&at, 48 * T);
+    plan->eown = workspace_region(&at, 24 * T);
+    plan->tslot = workspace_region(&at, 12 * T);
+    plan->parent = workspace_region(&at, 4 * T);
+    plan->tsize = workspace_region(&at, 4 * T);
+    plan->partial = workspace_region(&at, (size_t)AUDIT_TERMS * sizeof(double) * (size_t)plan->BT);
+    plan->tpart = workspace_region(&at, (size_t)AUDIT_PARTIALS * sizeof(int32_t) * (size_t)plan->BT);
+    plan->vpart = workspace_region(&at, sizeof(int32_t) * (size_t)plan->BV);
     plan->bytes = at;
     return PR_OK;
 }
@@ -565,12 +471,7 @@ extern "C" int pr_mesh_audit(const pr_mesh_audit_t* s, void* workspace, size_t w
     static_assert(sizeof(pr_mesh_audit_t) == 72, "the header states this size");
     AuditPlan plan;
     PR_TRY(plan_audit(s, "pr_mesh_audit", &plan));
-    PR_REQUIRE(workspace != nullptr, "pr_mesh_audit: NULL workspace");
-    PR_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-    if (workspace_bytes < plan.bytes) {
-        set_error("workspace too small: %zu bytes given, %zu needed", workspace_bytes, plan.bytes);
-        return PR_ERR_INVALID;
-    }
+    PR_TRY(check_workspace("pr_mesh_audit", workspace, workspace_bytes, plan.bytes));
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     AuditParams p;

@@ -9,7 +9,7 @@
 // (k_scan_blocks_group), k_band_offsets (a block per group: offsets and counts) and - unless the call only counts - k_band_emit (a
 // lane per point: index and position rows).  pr_band_fill: k_band_fill (a lane per point).  256-lane blocks that never span two groups.
 // A point's class is recomputed from the active bytes where it is needed (at most 8 byte reads): no per-point array is kept.
-#include "pr_common.h"
+#include "mesh_dev.h"
 
 namespace pr {
 
@@ -212,12 +212,6 @@ struct BandPlan {
     int points, blocks, cells[3], cell_count, cell_blocks;
 };
 
-static size_t band_region(size_t* at, size_t bytes) {
-    const size_t begin = *at;
-    *at += (bytes + 255) / 256 * 256;
-    return begin;
-}
-
 // Host checks of the three entry points: no device work.
 static int plan_band(const pr_band_t* s, const char* who, BandPlan* plan) {
     PR_REQUIRE(s != nullptr, "%s: NULL description", who);
@@ -250,13 +244,13 @@ static int plan_band(const pr_band_t* s, const char* who, BandPlan* plan) {
     plan->cell_blocks = (int)((cells + 255) / 256);
     const size_t G = (size_t)s->groups;
     size_t at = 0;
-    plan->mixed = band_region(&at, G * (size_t)cells);
-    plan->active = band_region(&at, G * (size_t)cells);
-    plan->msum = band_region(&at, G * plan->cell_blocks * sizeof(int32_t));
-    plan->asum = band_region(&at, G * plan->cell_blocks * sizeof(int32_t));
-    plan->psum = band_region(&at, G * plan->blocks * sizeof(int32_t));
-    plan->poff = band_region(&at, G * plan->blocks * sizeof(int32_t));
-    plan->total = band_region(&at, sizeof(int32_t));
+    plan->mixed = workspace_region(&at, G * (size_t)cells);
+    plan->active = workspace_region(&at, G * (size_t)cells);
+    plan->msum = workspace_region(&at, G * plan->cell_blocks * sizeof(int32_t));
+    plan->asum = workspace_region(&at, G * plan->cell_blocks * sizeof(int32_t));
+    plan->psum = workspace_region(&at, G * plan->blocks * sizeof(int32_t));
+    plan->poff = workspace_region(&at, G * plan->blocks * sizeof(int32_t));
+    plan->total = workspace_region(&at, sizeof(int32_t));
     plan->bytes = at;
     return PR_OK;
 }

@@ -6,7 +6,7 @@
 // at Chebyshev index distance exactly r from the start cell - testing each cell's list, until the best squared distance so far is at
 // most (r cmin)^2, or (r cmin)^2 exceeds the squared radius, or no shell is left.  A triangle listed in several cells is tested
 // several times: a minimum is idempotent.  No lane waits for another, no LDS, no atomics.
-#include "pr_common.h"
+#include "mesh_dev.h"
 
 #include <math.h>
 
@@ -27,11 +27,6 @@ struct ClosestParams {
     const float* points;
     float* distance; int32_t* triangle; float* point; float* barycentric;
 };
-
-__device__ __forceinline__ float cl_dot(const float* x, const float* y) {
-    return __fadd_rn(__fadd_rn(__fmul_rn(x[0], y[0]), __fmul_rn(x[1], y[1])), __fmul_rn(x[2], y[2]));
-}
-__device__ __forceinline__ bool cl_finite(float x) { return __fsub_rn(x, x) == 0.f; }
 
 struct ClosestBest { float d2, v, w, q[3]; int index; };
 
@@ -60,7 +55,7 @@ __device__ __forceinline__ void closest_test(const PR_GLOBAL_AS float* vertices,
         bp[k] = __fsub_rn(p[k], b[k]);
         cp[k] = __fsub_rn(p[k], c[k]);
     }
-    const float d1 = cl_dot(ab, ap), d2 = cl_dot(ac, ap), d3 = cl_dot(ab, bp), d4 = cl_dot(ac, bp), d5 = cl_dot(ab, cp), d6 = cl_dot(ac, cp);
+    const float d1 = mesh_dot(ab, ap), d2 = mesh_dot(ac, ap), d3 = mesh_dot(ab, bp), d4 = mesh_dot(ac, bp), d5 = mesh_dot(ab, cp), d6 = mesh_dot(ac, cp);
     const float vc = __fsub_rn(__fmul_rn(d1, d4), __fmul_rn(d3, d2));
     const float vb = __fsub_rn(__fmul_rn(d5, d2), __fmul_rn(d1, d6));
     const float va = __fsub_rn(__fmul_rn(d3, d6), __fmul_rn(d5, d4));
@@ -101,7 +96,7 @@ __device__ __forceinline__ void closest_test(const PR_GLOBAL_AS float* vertices,
     float r[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) r[k] = __fsub_rn(p[k], q[k]);
-    const float dist2 = cl_dot(r, r);
+    const float dist2 = mesh_dot(r, r);
     if (!(dist2 <= radius2 && dist2 < INFINITY)) return;
     if (dist2 < best.d2 || (dist2 == best.d2 && index < best.index) || best.index < 0) {
         best.d2 = dist2;
@@ -134,7 +129,7 @@ __global__ __launch_bounds__(256) void k_closest_query(ClosestParams s) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         p[a] = as_global(s.points)[row * 3 + a];
-        finite = finite && cl_finite(p[a]);
+        finite = finite && mesh_finite(p[a]);
     }
     ClosestBest best = {INFINITY, 0.f, 0.f, {0.f, 0.f, 0.f}, -1};
     auto test_list = [&](int list) {
@@ -193,7 +188,6 @@ __global__ __launch_bounds__(256) void k_closest_query(ClosestParams s) {
     }
 }
 
-static bool closest_finite(float x) { return x - x == 0.f; }
 
 }  // namespace pr
 
@@ -207,8 +201,8 @@ extern "C" int pr_closest_query(const pr_closest_t* s, void* stream) {
         PR_REQUIRE(s->cells[a] >= 1 && s->cells[a] <= PR_RAYCAST_MAX_AXIS_CELLS, "%s: cells[%d] = %d (1 .. %d)", who, a, s->cells[a],
                    PR_RAYCAST_MAX_AXIS_CELLS);
         cells *= (double)s->cells[a];
-        PR_REQUIRE(closest_finite(s->cell[a]) && s->cell[a] > 0.f, "%s: cell[%d] = %g (finite, > 0)", who, a, (double)s->cell[a]);
-        PR_REQUIRE(closest_finite(s->origin[a]), "%s: origin[%d] = %g (finite)", who, a, (double)s->origin[a]);
+        PR_REQUIRE(host_finite(s->cell[a]) && s->cell[a] > 0.f, "%s: cell[%d] = %g (finite, > 0)", who, a, (double)s->cell[a]);
+        PR_REQUIRE(host_finite(s->origin[a]), "%s: origin[%d] = %g (finite)", who, a, (double)s->origin[a]);
     }
     PR_REQUIRE(cells <= (double)PR_RAYCAST_MAX_CELLS, "%s: %d x %d x %d cells (at most 2^21 = %d)", who, s->cells[0], s->cells[1],
                s->cells[2], PR_RAYCAST_MAX_CELLS);

@@ -11,16 +11,12 @@
 //   k_components_write    labels, sizes, sigma_out, counts[2..3]
 // Lanes: one per lattice point, 256-lane blocks that never span two groups.  Integer atomics only: every output is deterministic.
 //
-// TERMINATION.  No lane ever waits for another lane's progress: there is no spin, no lock and no flag in this file.  The only
-// writes to `label` are the init kernel's, atomic minima (merge) and the store of a root found by a walk (flatten), so a slot only
-// ever decreases, stays <= its own index, and a value read from it - however stale - is an ancestor of the point in some earlier
-// forest: never a wrong set, at worst a longer walk.  Every loop strictly decreases a non-negative integer:
-//   components_find   x -> label[x] < x until label[x] == x: at most x steps.
-//   components_unite  each round ends or replaces the larger of (a, b) by a strictly smaller index (the parent somebody else gave
-//                     it first) and walks down from there: a + b falls every round, so at most a + b rounds.  Going on with the
-//                     returned parent - not giving up - is what keeps the link that parent stood for.
-//   the wave sum of k_components_flatten retires at least one pending lane per pass and is bounded by 64 passes as written.
-#include "pr_common.h"
+// TERMINATION.  No lane ever waits for another lane's progress: there is no spin, no lock and no flag in this file.  The union-find
+// is mesh_uf_find / mesh_uf_unite (mesh_dev.h, which holds their termination argument); its premise holds here: the only writes to
+// `label` are the init kernel's (the head of a run: <= the point's own index), atomic minima (merge) and the store of a root found by
+// a walk (flatten).  The wave sum of k_components_flatten retires at least one pending lane per pass and is bounded by 64 passes as
+// written.
+#include "mesh_dev.h"
 
 namespace pr {
 
@@ -71,33 +67,6 @@ __device__ __forceinline__ bool components_kept(const ComponentsParams& c, int g
     return components_key(size, label) >= as_global(c.winners)[(size_t)group * COMPONENTS_MAX_RANKS + c.keep_largest - 1];
 }
 
-// (reads that race with the merge kernel's atomics go to the coherent level; see TERMINATION for why a stale value is harmless)
-__device__ __forceinline__ int components_parent(const PR_GLOBAL_AS int32_t* slot) {
-    return __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ int components_find(const PR_GLOBAL_AS int32_t* label, int x) {
-    // x strictly falls; the unsigned comparison also ends the walk on a negative value, which no inside point's chain holds
-    for (int up = components_parent(label + x); (unsigned)up < (unsigned)x; up = components_parent(label + x)) x = up;
-    return x;
-}
-
-__device__ __forceinline__ void components_unite(PR_GLOBAL_AS int32_t* label, int a, int b) {
-    a = components_find(label, a);
-    b = components_find(label, b);
-    while (a != b) {                               // a + b strictly falls
-        if (a < b) {
-            const int t = a;
-            a = b;
-            b = t;
-        }
-        const int was = __hip_atomic_fetch_min(label + a, b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (was == a) return;                      // a was a root and now hangs under b
-        a = components_find(label, was);           // was < a: somebody re-parented a first - that parent must meet b too
-        b = components_find(label, b);
-    }
-}
-
 // inclusive maximum scan over the 256 threads of a block.  lds: >= 4 ints.
 __device__ __forceinline__ int components_block_max_scan(int v, int* lds) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -142,7 +111,7 @@ __global__ __launch_bounds__(256) void k_components_merge(ComponentsParams c) {
     // (inside <=> label >= 0, which no kernel after init changes: plain reads)
     if (label[l.p] < 0) return;
     const bool back = l.k > 0 && label[l.p - 1] >= 0;
-    if (back && threadIdx.x == 0) components_unite(label, l.p, l.p - 1);      // the z edge into the previous block
+    if (back && threadIdx.x == 0) mesh_uf_unite(label, l.p, l.p - 1);      // the z edge into the previous block
 #pragma unroll
     for (int d = 0; d < 7; ++d) {
         if (d == 2) continue;                      // z: the init kernel's runs and the line above
@@ -153,7 +122,7 @@ __global__ __launch_bounds__(256) void k_components_merge(ComponentsParams c) {
         // both backward z neighbours inside: p ~ p - 1 and q ~ q - 1 along z, and lane p - 1 unites p - 1 with q - 1 (or defers
         // the same way, down to the start of the run)
         if (back && label[q - 1] >= 0) continue;
-        components_unite(label, l.p, q);
+        mesh_uf_unite(label, l.p, q);
     }
 }
 
@@ -165,7 +134,7 @@ __global__ __launch_bounds__(256) void k_components_flatten(ComponentsParams c) 
     PR_GLOBAL_AS int32_t* size = as_global(c.size) + (size_t)l.group * c.points;
     int root = -1;
     if (l.live && label[l.p] >= 0) {
-        root = components_find(label, l.p);        // (no unions in this kernel: the roots are final)
+        root = mesh_uf_find(label, l.p);        // (no unions in this kernel: the roots are final)
         label[l.p] = root;
     }
     if (threadIdx.x == 0) {
@@ -264,12 +233,6 @@ struct ComponentsPlan {
     int points, blocks;
 };
 
-static size_t components_region(size_t* at, size_t bytes) {
-    const size_t begin = *at;
-    *at += (bytes + 255) / 256 * 256;
-    return begin;
-}
-
 // Host checks of both entry points: no device work.
 static int plan_components(const pr_components_t* c, const char* who, ComponentsPlan* plan) {
     PR_REQUIRE(c != nullptr, "%s: NULL description", who);
@@ -300,9 +263,9 @@ static int plan_components(const pr_components_t* c, const char* who, Components
     plan->blocks = (int)((points + 255) / 256);
     const size_t lattice = (size_t)c->groups * (size_t)points;
     size_t at = 0;
-    plan->label = components_region(&at, lattice * sizeof(int32_t));
-    plan->size = components_region(&at, lattice * sizeof(int32_t));
-    plan->winners = components_region(&at, (size_t)c->groups * COMPONENTS_MAX_RANKS * sizeof(unsigned long long));
+    plan->label = workspace_region(&at, lattice * sizeof(int32_t));
+    plan->size = workspace_region(&at, lattice * sizeof(int32_t));
+    plan->winners = workspace_region(&at, (size_t)c->groups * COMPONENTS_MAX_RANKS * sizeof(unsigned long long));
     plan->bytes = at;
     return PR_OK;
 }
@@ -322,12 +285,7 @@ extern "C" int pr_label_components(const pr_components_t* c, void* workspace, si
     static_assert(COMPONENTS_MAX_RANKS == PR_COMPONENTS_MAX_KEEP, "one winner slot per rank");
     ComponentsPlan plan;
     PR_TRY(plan_components(c, "pr_label_components", &plan));
-    PR_REQUIRE(workspace != nullptr, "pr_label_components: NULL workspace");
-    PR_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-    if (workspace_bytes < plan.bytes) {
-        set_error("workspace too small: %zu bytes given, %zu needed", workspace_bytes, plan.bytes);
-        return PR_ERR_INVALID;
-    }
+    PR_TRY(check_workspace("pr_label_components", workspace, workspace_bytes, plan.bytes));
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     ComponentsParams p;

@@ -6,7 +6,7 @@
 // listed in several cells of the column is summed in the first of them that the lane visits.  Per candidate: exact fp32 rejections,
 // then per edge a float64 filter, then the exact sign of the expanded determinant (an expansion sum in registers: every index is a
 // compile-time constant, there is no scratch).  No lane waits for another, no LDS, no atomics.
-#include "pr_common.h"
+#include "mesh_dev.h"
 
 #include <math.h>
 
@@ -28,8 +28,6 @@ struct InsideParams {
     const float* points;
     int32_t* winding; int32_t* crossings;
 };
-
-__device__ __forceinline__ bool in_finite(float x) { return __fsub_rn(x, x) == 0.f; }
 
 // s + e = a + b exactly (Knuth; no branch, no condition on the magnitudes)
 __device__ __forceinline__ void in_two_sum(double a, double b, double& s, double& e) {
@@ -103,7 +101,7 @@ __device__ __forceinline__ void inside_test(const InsideParams& s, const PR_GLOB
     if ((a[0] == b[0] && a[1] == b[1] && a[2] == b[2]) || (a[0] == c[0] && a[1] == c[1] && a[2] == c[2])) return;      // dead
     bool finite = true;
 #pragma unroll
-    for (int x = 0; x < 3; ++x) finite = finite && in_finite(a[x]) && in_finite(b[x]) && in_finite(c[x]);
+    for (int x = 0; x < 3; ++x) finite = finite && mesh_finite(a[x]) && mesh_finite(b[x]) && mesh_finite(c[x]);
     if (!finite) return;
     // exact rejections (closed intervals)
     if (p[I] < fminf(fminf(a[I], b[I]), c[I]) || p[I] > fmaxf(fmaxf(a[I], b[I]), c[I])) return;
@@ -155,7 +153,7 @@ __global__ __launch_bounds__(256) void k_inside_query(InsideParams s) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
         p[a] = as_global(s.points)[row * 3 + a];
-        finite = finite && in_finite(p[a]);
+        finite = finite && mesh_finite(p[a]);
     }
     int winding = 0, crossings = 0;
     auto test_list = [&](int list, bool tight, int m, int start) {
@@ -186,7 +184,6 @@ __global__ __launch_bounds__(256) void k_inside_query(InsideParams s) {
     if (s.crossings) as_global(s.crossings)[row] = crossings;
 }
 
-static bool inside_finite(float x) { return x - x == 0.f; }
 
 }  // namespace pr
 
@@ -200,8 +197,8 @@ extern "C" int pr_inside_query(const pr_inside_t* s, void* stream) {
         PR_REQUIRE(s->cells[a] >= 1 && s->cells[a] <= PR_RAYCAST_MAX_AXIS_CELLS, "%s: cells[%d] = %d (1 .. %d)", who, a, s->cells[a],
                    PR_RAYCAST_MAX_AXIS_CELLS);
         cells *= (double)s->cells[a];
-        PR_REQUIRE(inside_finite(s->cell[a]) && s->cell[a] > 0.f, "%s: cell[%d] = %g (finite, > 0)", who, a, (double)s->cell[a]);
-        PR_REQUIRE(inside_finite(s->origin[a]), "%s: origin[%d] = %g (finite)", who, a, (double)s->origin[a]);
+        PR_REQUIRE(host_finite(s->cell[a]) && s->cell[a] > 0.f, "%s: cell[%d] = %g (finite, > 0)", who, a, (double)s->cell[a]);
+        PR_REQUIRE(host_finite(s->origin[a]), "%s: origin[%d] = %g (finite)", who, a, (double)s->origin[a]);
     }
     PR_REQUIRE(cells <= (double)PR_RAYCAST_MAX_CELLS, "%s: %d x %d x %d cells (at most 2^21 = %d)", who, s->cells[0], s->cells[1],
                s->cells[2], PR_RAYCAST_MAX_CELLS);

@@ -4,7 +4,7 @@
 // Five launches on the caller's stream for a counting call, six for an emitting one, all kernels:
 //   k_intersect_groups   one lane: the clamped per-group offsets of both mesh sets and the first query block of every group
 //   k_intersect_walk     (counting) one lane per query triangle, 256-lane blocks that never span two groups (the block table of
-//                        simplify.hip): the lane tests the group's loose list, then walks the cells its box overlaps and tests their
+//                        mesh_dev.h): the lane tests the group's loose list, then walks the cells its box overlaps and tests their
 //                        lists; it writes count and first
 //   k_intersect_mark     per 256 packed rows: rows that no clamped group owns get count 0 / first -1; the block sum of the counts
 //                                                                                          -> k_scan_blocks_group
@@ -13,7 +13,7 @@
 // A tight target listed in several cells of a query's range is tested in ONE of them - the cell of max(g(min T), g(min Q)) per axis,
 // which lies in both ranges whenever the boxes overlap -: a sum, unlike a minimum, is not idempotent.  No lane waits for another, no
 // LDS outside the scans, no atomics.
-#include "pr_common.h"
+#include "mesh_dev.h"
 
 #include <math.h>
 
@@ -44,18 +44,7 @@ struct IntersectParams {
     int32_t* total;               // [P]
 };
 
-__device__ __forceinline__ float ix_dot(const float* x, const float* y) {
-    return __fadd_rn(__fadd_rn(__fmul_rn(x[0], y[0]), __fmul_rn(x[1], y[1])), __fmul_rn(x[2], y[2]));
-}
-__device__ __forceinline__ void ix_cross(const float* x, const float* y, float* out) {
-    out[0] = __fsub_rn(__fmul_rn(x[1], y[2]), __fmul_rn(x[2], y[1]));
-    out[1] = __fsub_rn(__fmul_rn(x[2], y[0]), __fmul_rn(x[0], y[2]));
-    out[2] = __fsub_rn(__fmul_rn(x[0], y[1]), __fmul_rn(x[1], y[0]));
-}
-__device__ __forceinline__ bool ix_finite(float x) { return __fsub_rn(x, x) == 0.f; }
-__device__ __forceinline__ bool ix_same(const float* x, const float* y) { return x[0] == y[0] && x[1] == y[1] && x[2] == y[2]; }
-
-// One lane, serial over the groups: offsets that leave [0, total] or decrease are clamped (as k_raycast_groups clamps them).
+// One lane, serial over the groups: offsets that leave [0, total] or decrease are clamped (the rule: mesh_dev.h).
 __global__ __launch_bounds__(64) void k_intersect_groups(IntersectParams s) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     int v = 0, t = 0, qv = 0, qt = 0, qb = 0;
@@ -85,7 +74,7 @@ __device__ __forceinline__ void ix_prepare(IxTriangle& x) {
         x.lo[k] = fminf(fminf(x.a[k], x.b[k]), x.c[k]);
         x.hi[k] = fmaxf(fmaxf(x.a[k], x.b[k]), x.c[k]);
     }
-    x.ee = __fmul_rn(ix_dot(x.e1, x.e1), ix_dot(x.e2, x.e2));
+    x.ee = __fmul_rn(mesh_dot(x.e1, x.e1), mesh_dot(x.e2, x.e2));
 }
 
 // The header's ray-triangle test of the edge o -> e against y with t in [0, 1], no culling, and the conditioning clause.
@@ -96,14 +85,14 @@ __device__ __forceinline__ bool ix_edge(const float* o, const float* e, const Ix
         d[k] = __fsub_rn(e[k], o[k]);
         sv[k] = __fsub_rn(o[k], y.a[k]);
     }
-    ix_cross(d, y.e2, p);
-    const float det = ix_dot(y.e1, p);
+    mesh_cross(d, y.e2, p);
+    const float det = mesh_dot(y.e1, p);
     if (!(det > 0.f || det < 0.f)) return false;
-    if (!(__fmul_rn(det, det) > __fmul_rn(INTERSECT_CONDITION, __fmul_rn(y.ee, ix_dot(d, d))))) return false;
-    const float u = __fdiv_rn(ix_dot(sv, p), det);
-    ix_cross(sv, y.e1, q);
-    const float v = __fdiv_rn(ix_dot(d, q), det);
-    const float t = __fdiv_rn(ix_dot(y.e2, q), det);
+    if (!(__fmul_rn(det, det) > __fmul_rn(INTERSECT_CONDITION, __fmul_rn(y.ee, mesh_dot(d, d))))) return false;
+    const float u = __fdiv_rn(mesh_dot(sv, p), det);
+    mesh_cross(sv, y.e1, q);
+    const float v = __fdiv_rn(mesh_dot(d, q), det);
+    const float t = __fdiv_rn(mesh_dot(y.e2, q), det);
     if (!(u >= 0.f && v >= 0.f && __fadd_rn(u, v) <= 1.f && t >= 0.f && t <= 1.f)) return false;
 #pragma unroll
     for (int k = 0; k < 3; ++k) point[k] = __fadd_rn(o[k], __fmul_rn(t, d[k]));
@@ -137,7 +126,7 @@ __device__ __forceinline__ void ix_add(IxSegment& seg, const float* point) {
     seg.p0y = first ? point[1] : seg.p0y;
     seg.p0z = first ? point[2] : seg.p0z;
     const float r[3] = {__fsub_rn(point[0], seg.p0x), __fsub_rn(point[1], seg.p0y), __fsub_rn(point[2], seg.p0z)};
-    const float d2 = ix_dot(r, r);
+    const float d2 = mesh_dot(r, r);
     const bool better = first || d2 > seg.far;                             // (the earliest point on ties)
     seg.far = first ? 0.f : (better ? d2 : seg.far);
     seg.p1x = better ? point[0] : seg.p1x;
@@ -214,7 +203,7 @@ __global__ __launch_bounds__(256) void k_intersect_walk(IntersectParams s, int e
                 }
             }
 #pragma unroll
-            for (int k = 0; k < 3; ++k) candidate = candidate && ix_finite(q.a[k]) && ix_finite(q.b[k]) && ix_finite(q.c[k]);
+            for (int k = 0; k < 3; ++k) candidate = candidate && mesh_finite(q.a[k]) && mesh_finite(q.b[k]) && mesh_finite(q.c[k]);
         }
     }
     int found = 0, lowest = -1;
@@ -237,9 +226,9 @@ __global__ __launch_bounds__(256) void k_intersect_walk(IntersectParams s, int e
                 t.a[k] = vertices[(size_t)i0 * 3 + k];
                 t.b[k] = vertices[(size_t)i1 * 3 + k];
                 t.c[k] = vertices[(size_t)i2 * 3 + k];
-                finite = finite && ix_finite(t.a[k]) && ix_finite(t.b[k]) && ix_finite(t.c[k]);
+                finite = finite && mesh_finite(t.a[k]) && mesh_finite(t.b[k]) && mesh_finite(t.c[k]);
             }
-            if (!finite || ix_same(t.a, t.b) || ix_same(t.a, t.c)) return;                           // no candidate, dead
+            if (!finite || mesh_same(t.a, t.b) || mesh_same(t.a, t.c)) return;                           // no candidate, dead
             bool box = true;
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
@@ -252,15 +241,15 @@ __global__ __launch_bounds__(256) void k_intersect_walk(IntersectParams s, int e
                              ix_own_cell(t.lo[1], s.origin[1], s.cell[1], gq1, s.cells[1], cy) &&
                              ix_own_cell(t.lo[2], s.origin[2], s.cell[2], gq2, s.cells[2], cz)))
                 return;                                                    // counted in another cell
-            if (s.self && (ix_same(q.a, t.a) || ix_same(q.a, t.b) || ix_same(q.a, t.c) || ix_same(q.b, t.a) || ix_same(q.b, t.b) ||
-                           ix_same(q.b, t.c) || ix_same(q.c, t.a) || ix_same(q.c, t.b) || ix_same(q.c, t.c)))
+            if (s.self && (mesh_same(q.a, t.a) || mesh_same(q.a, t.b) || mesh_same(q.a, t.c) || mesh_same(q.b, t.a) || mesh_same(q.b, t.b) ||
+                           mesh_same(q.b, t.c) || mesh_same(q.c, t.a) || mesh_same(q.c, t.b) || mesh_same(q.c, t.c)))
                 return;
 #pragma unroll
             for (int k = 0; k < 3; ++k) {
                 t.e1[k] = __fsub_rn(t.b[k], t.a[k]);
                 t.e2[k] = __fsub_rn(t.c[k], t.a[k]);
             }
-            t.ee = __fmul_rn(ix_dot(t.e1, t.e1), ix_dot(t.e2, t.e2));
+            t.ee = __fmul_rn(mesh_dot(t.e1, t.e1), mesh_dot(t.e2, t.e2));
             IxSegment seg;
             if (!ix_edges(q, t, all, seg)) return;
             if (emit) {
@@ -339,14 +328,6 @@ struct IntersectPlan {
     int C, QV, QT, BQ, NB, self;
 };
 
-static size_t intersect_region(size_t* at, size_t bytes) {
-    const size_t begin = *at;
-    *at += (bytes + 255) / 256 * 256;
-    return begin;
-}
-
-static bool intersect_finite(float x) { return x - x == 0.f; }
-
 // Host checks shared by the two entry points: no device work.
 static int plan_intersect(const pr_mesh_intersect_t* s, const char* who, IntersectPlan* plan) {
     PR_REQUIRE(s != nullptr, "%s: NULL description", who);
@@ -356,8 +337,8 @@ static int plan_intersect(const pr_mesh_intersect_t* s, const char* who, Interse
         PR_REQUIRE(s->cells[a] >= 1 && s->cells[a] <= PR_RAYCAST_MAX_AXIS_CELLS, "%s: cells[%d] = %d (1 .. %d)", who, a, s->cells[a],
                    PR_RAYCAST_MAX_AXIS_CELLS);
         cells *= (double)s->cells[a];
-        PR_REQUIRE(intersect_finite(s->cell[a]) && s->cell[a] > 0.f, "%s: cell[%d] = %g (finite, > 0)", who, a, (double)s->cell[a]);
-        PR_REQUIRE(intersect_finite(s->origin[a]), "%s: origin[%d] = %g (finite)", who, a, (double)s->origin[a]);
+        PR_REQUIRE(host_finite(s->cell[a]) && s->cell[a] > 0.f, "%s: cell[%d] = %g (finite, > 0)", who, a, (double)s->cell[a]);
+        PR_REQUIRE(host_finite(s->origin[a]), "%s: origin[%d] = %g (finite)", who, a, (double)s->origin[a]);
     }
     PR_REQUIRE(cells <= (double)PR_RAYCAST_MAX_CELLS, "%s: %d x %d x %d cells (at most 2^21 = %d)", who, s->cells[0], s->cells[1],
                s->cells[2], PR_RAYCAST_MAX_CELLS);
@@ -402,15 +383,15 @@ static int plan_intersect(const pr_mesh_intersect_t* s, const char* who, Interse
     plan->NB = plan->QT / 256 + 1;                         // (covers the element behind the last row, which receives P)
     const size_t table = ((size_t)s->groups + 1) * sizeof(int32_t);
     size_t at = 0;
-    plan->vfirst = intersect_region(&at, table);
-    plan->tfirst = intersect_region(&at, table);
-    plan->qvfirst = intersect_region(&at, table);
-    plan->qtfirst = intersect_region(&at, table);
-    plan->qtblk = intersect_region(&at, table);
-    plan->off = intersect_region(&at, 4 * ((size_t)plan->QT + 1));
-    plan->bsum = intersect_region(&at, 4 * (size_t)plan->NB);
-    plan->boff = intersect_region(&at, 4 * (size_t)plan->NB);
-    plan->total = intersect_region(&at, sizeof(int32_t));
+    plan->vfirst = workspace_region(&at, table);
+    plan->tfirst = workspace_region(&at, table);
+    plan->qvfirst = workspace_region(&at, table);
+    plan->qtfirst = workspace_region(&at, table);
+    plan->qtblk = workspace_region(&at, table);
+    plan->off = workspace_region(&at, 4 * ((size_t)plan->QT + 1));
+    plan->bsum = workspace_region(&at, 4 * (size_t)plan->NB);
+    plan->boff = workspace_region(&at, 4 * (size_t)plan->NB);
+    plan->total = workspace_region(&at, sizeof(int32_t));
     plan->bytes = at;
     return PR_OK;
 }
@@ -429,12 +410,7 @@ extern "C" int pr_mesh_intersect(const pr_mesh_intersect_t* s, void* workspace, 
     using namespace pr;
     IntersectPlan plan;
     PR_TRY(plan_intersect(s, "pr_mesh_intersect", &plan));
-    PR_REQUIRE(workspace != nullptr, "pr_mesh_intersect: NULL workspace");
-    PR_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-    if (workspace_bytes < plan.bytes) {
-        set_error("workspace too small: %zu bytes given, %zu needed", workspace_bytes, plan.bytes);
-        return PR_ERR_INVALID;
-    }
+    PR_TRY(check_workspace("pr_mesh_intersect", workspace, workspace_bytes, plan.bytes));
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     IntersectParams p;

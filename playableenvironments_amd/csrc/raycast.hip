@@ -10,14 +10,14 @@
 //   k_raycast_offsets   per cell: cell_offsets, and the same value as the cell's cursor (replaces the count)
 //   k_raycast_bin       (emitting, not launched without `references`) per (triangle, cell): the cursor's next slot receives the
 //                       triangle.  The order inside a cell is the order of arrival; the query takes a minimum.
-// Lanes: one per triangle, 256-lane blocks that never span two groups (the block table of simplify.hip).  A triangle that overlaps
+// Lanes: one per triangle, 256-lane blocks that never span two groups (the block table of mesh_dev.h).  A triangle that overlaps
 // many cells is a serial loop in its lane.  Every group has C + 1 lists: its C cells and, last, the loose list that every ray of the
 // group tests.
 //
 // Query, one launch: k_raycast_query, one lane per ray, wave64.  The lane tests the loose list, clips the ray to the grid's box and
 // walks the cells front to back (3D-DDA in cell units); every plane-crossing time is computed from the plane's integer index, so no
 // error accumulates along the walk.  No lane waits for another, no LDS, no atomics.
-#include "pr_common.h"
+#include "mesh_dev.h"
 
 #include <math.h>
 
@@ -50,22 +50,12 @@ struct RaycastParams {
     int32_t* total;               // [R]
 };
 
-__device__ __forceinline__ float rc_dot(const float* x, const float* y) {
-    return __fadd_rn(__fadd_rn(__fmul_rn(x[0], y[0]), __fmul_rn(x[1], y[1])), __fmul_rn(x[2], y[2]));
-}
-__device__ __forceinline__ void rc_cross(const float* x, const float* y, float* out) {
-    out[0] = __fsub_rn(__fmul_rn(x[1], y[2]), __fmul_rn(x[2], y[1]));
-    out[1] = __fsub_rn(__fmul_rn(x[2], y[0]), __fmul_rn(x[0], y[2]));
-    out[2] = __fsub_rn(__fmul_rn(x[0], y[1]), __fmul_rn(x[1], y[0]));
-}
-__device__ __forceinline__ bool rc_finite(float x) { return __fsub_rn(x, x) == 0.f; }
-
 __global__ __launch_bounds__(256) void k_raycast_init(RaycastParams s) {
     const size_t stride = (size_t)gridDim.x * 256;
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < (size_t)s.lists; i += stride) as_global(s.cnt)[i] = 0;
 }
 
-// One lane, serial over the groups: offsets that leave [0, total] or decrease are clamped (as k_simplify_groups clamps them).
+// One lane, serial over the groups: offsets that leave [0, total] or decrease are clamped (the rule: mesh_dev.h).
 __global__ __launch_bounds__(64) void k_raycast_groups(RaycastParams s) {
     if (blockIdx.x != 0 || threadIdx.x != 0) return;
     int v = 0, t = 0, tb = 0;
@@ -100,8 +90,8 @@ __device__ __forceinline__ int raycast_classify(const RaycastParams& s, const PR
         e1[k] = __fsub_rn(b[k], a[k]);
         e2[k] = __fsub_rn(c[k], a[k]);
     }
-    rc_cross(e1, e2, n);
-    const bool shaped = rc_dot(n, n) > __fmul_rn(RAYCAST_SLIVER, __fmul_rn(rc_dot(e1, e1), rc_dot(e2, e2)));
+    mesh_cross(e1, e2, n);
+    const bool shaped = mesh_dot(n, n) > __fmul_rn(RAYCAST_SLIVER, __fmul_rn(mesh_dot(e1, e1), mesh_dot(e2, e2)));
     bool inside = true;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -110,7 +100,7 @@ __device__ __forceinline__ int raycast_classify(const RaycastParams& s, const PR
         const float gc = __fdiv_rn(__fsub_rn(c[k], s.origin[k]), s.cell[k]);
         const float low = __fsub_rn(fminf(fminf(ga, gb), gc), RAYCAST_PAD);
         const float high = __fadd_rn(fmaxf(fmaxf(ga, gb), gc), RAYCAST_PAD);
-        const bool ok = rc_finite(ga) && rc_finite(gb) && rc_finite(gc) && low >= 0.f && high <= (float)s.cells[k];
+        const bool ok = mesh_finite(ga) && mesh_finite(gb) && mesh_finite(gc) && low >= 0.f && high <= (float)s.cells[k];
         inside = inside && ok;
         lo[k] = ok ? (int)low : 0;                                  // (0 <= low <= high <= cells: the casts truncate = floor)
         hi[k] = ok ? min((int)high, s.cells[k] - 1) : 0;
@@ -189,13 +179,13 @@ __device__ __forceinline__ void raycast_test(const RaycastParams& s, const PR_GL
         e2[k] = __fsub_rn(vertices[(size_t)i2 * 3 + k], a[k]);
         sv[k] = __fsub_rn(o[k], a[k]);
     }
-    rc_cross(d, e2, p);
-    const float det = rc_dot(e1, p);
+    mesh_cross(d, e2, p);
+    const float det = mesh_dot(e1, p);
     if (!(det > 0.f || (!s.cull && det < 0.f))) return;
-    const float u = __fdiv_rn(rc_dot(sv, p), det);
-    rc_cross(sv, e1, q);
-    const float v = __fdiv_rn(rc_dot(d, q), det);
-    const float t = __fdiv_rn(rc_dot(e2, q), det);
+    const float u = __fdiv_rn(mesh_dot(sv, p), det);
+    mesh_cross(sv, e1, q);
+    const float v = __fdiv_rn(mesh_dot(d, q), det);
+    const float t = __fdiv_rn(mesh_dot(e2, q), det);
     if (!(u >= 0.f && v >= 0.f && __fadd_rn(u, v) <= 1.f && t >= s.t_min && t <= s.t_max)) return;
     if (t < best.t || (t == best.t && index < best.index) || best.index < 0) {
         best.t = t;
@@ -230,7 +220,7 @@ __global__ __launch_bounds__(256) void k_raycast_query(RaycastParams s) {
         d[a] = as_global(s.directions)[row * 3 + a];
         og[a] = __fdiv_rn(__fsub_rn(o[a], s.origin[a]), s.cell[a]);
         dg[a] = __fdiv_rn(d[a], s.cell[a]);
-        finite = finite && rc_finite(o[a]) && rc_finite(d[a]);
+        finite = finite && mesh_finite(o[a]) && mesh_finite(d[a]);
     }
     RaycastHit best = {INFINITY, 0.f, 0.f, -1};
     auto test_list = [&](int list) {
@@ -243,7 +233,7 @@ __global__ __launch_bounds__(256) void k_raycast_query(RaycastParams s) {
     // A ray with a component that is not finite, or with the direction (0, 0, 0), is accepted by no triangle.
     if (finite && (d[0] != 0.f || d[1] != 0.f || d[2] != 0.f)) {
         test_list(s.C);
-        bool walk = rc_finite(og[0]) && rc_finite(og[1]) && rc_finite(og[2]) && rc_finite(dg[0]) && rc_finite(dg[1]) && rc_finite(dg[2]);
+        bool walk = mesh_finite(og[0]) && mesh_finite(og[1]) && mesh_finite(og[2]) && mesh_finite(dg[0]) && mesh_finite(dg[1]) && mesh_finite(dg[2]);
         float tlo = s.t_min, thi = s.t_max;
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
@@ -302,14 +292,6 @@ struct RaycastPlan {
     int C, C1, lists, BT, NB;
 };
 
-static size_t raycast_region(size_t* at, size_t bytes) {
-    const size_t begin = *at;
-    *at += (bytes + 255) / 256 * 256;
-    return begin;
-}
-
-static bool raycast_finite(float x) { return x - x == 0.f; }
-
 // Host checks shared by the three entry points: no device work.
 static int plan_raycast(const pr_raycast_t* s, const char* who, RaycastPlan* plan) {
     PR_REQUIRE(s != nullptr, "%s: NULL description", who);
@@ -319,8 +301,8 @@ static int plan_raycast(const pr_raycast_t* s, const char* who, RaycastPlan* pla
         PR_REQUIRE(s->cells[a] >= 1 && s->cells[a] <= PR_RAYCAST_MAX_AXIS_CELLS, "%s: cells[%d] = %d (1 .. %d)", who, a, s->cells[a],
                    PR_RAYCAST_MAX_AXIS_CELLS);
         cells *= (double)s->cells[a];
-        PR_REQUIRE(raycast_finite(s->cell[a]) && s->cell[a] > 0.f, "%s: cell[%d] = %g (finite, > 0)", who, a, (double)s->cell[a]);
-        PR_REQUIRE(raycast_finite(s->origin[a]), "%s: origin[%d] = %g (finite)", who, a, (double)s->origin[a]);
+        PR_REQUIRE(host_finite(s->cell[a]) && s->cell[a] > 0.f, "%s: cell[%d] = %g (finite, > 0)", who, a, (double)s->cell[a]);
+        PR_REQUIRE(host_finite(s->origin[a]), "%s: origin[%d] = %g (finite)", who, a, (double)s->origin[a]);
     }
     PR_REQUIRE(cells <= (double)PR_RAYCAST_MAX_CELLS, "%s: %d x %d x %d cells (at most 2^21 = %d)", who, s->cells[0], s->cells[1],
                s->cells[2], PR_RAYCAST_MAX_CELLS);
@@ -347,13 +329,13 @@ static int plan_raycast(const pr_raycast_t* s, const char* who, RaycastPlan* pla
     plan->NB = plan->lists / 256 + 1;                      // (covers the element behind the last list, which receives R)
     const size_t table = ((size_t)s->groups + 1) * sizeof(int32_t);
     size_t at = 0;
-    plan->cnt = raycast_region(&at, 4 * (size_t)plan->lists);
-    plan->vfirst = raycast_region(&at, table);
-    plan->tfirst = raycast_region(&at, table);
-    plan->tblk = raycast_region(&at, table);
-    plan->bsum = raycast_region(&at, 4 * (size_t)plan->NB);
-    plan->boff = raycast_region(&at, 4 * (size_t)plan->NB);
-    plan->total = raycast_region(&at, sizeof(int32_t));
+    plan->cnt = workspace_region(&at, 4 * (size_t)plan->lists);
+    plan->vfirst = workspace_region(&at, table);
+    plan->tfirst = workspace_region(&at, table);
+    plan->tblk = workspace_region(&at, table);
+    plan->bsum = workspace_region(&at, 4 * (size_t)plan->NB);
+    plan->boff = workspace_region(&at, 4 * (size_t)plan->NB);
+    plan->total = workspace_region(&at, sizeof(int32_t));
     plan->bytes = at;
     return PR_OK;
 }
@@ -406,12 +388,7 @@ extern "C" int pr_raycast_build(const pr_raycast_t* s, void* workspace, size_t w
     using namespace pr;
     RaycastPlan plan;
     PR_TRY(plan_raycast(s, "pr_raycast_build", &plan));
-    PR_REQUIRE(workspace != nullptr, "pr_raycast_build: NULL workspace");
-    PR_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-    if (workspace_bytes < plan.bytes) {
-        set_error("workspace too small: %zu bytes given, %zu needed", workspace_bytes, plan.bytes);
-        return PR_ERR_INVALID;
-    }
+    PR_TRY(check_workspace("pr_raycast_build", workspace, workspace_bytes, plan.bytes));
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     RaycastParams p;

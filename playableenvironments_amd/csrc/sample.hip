@@ -4,7 +4,7 @@
 // No output depends on the execution order: the only floating-point reduction is a maximum, every sum is an integer sum.
 //
 // Seven launches on the caller's stream, eight with out_attributes, all kernels:
-//   k_sample_init       one lane clamps the offsets and builds the triangle block table (what k_smooth_init does)
+//   k_sample_init       one lane clamps the offsets and builds the triangle block table (the rule: mesh_dev.h)
 //   k_sample_area       per triangle: valid or dropped, the fp64 area (-1 for a dropped one) into the 8-byte slot of the triangle;
 //                       per block the largest area and the number of valid triangles
 //   k_sample_max        a block per group: A_max and the counts of valid and dropped triangles
@@ -18,8 +18,8 @@
 //   k_sample_rows       (with out_attributes) lanes run across the columns: a flat index over (sample, column unit), a unit being four
 //                       columns where C and the two addresses allow 16-byte accesses, else one; the three corner rows are read as
 //                       whole coalesced rows and the output is written as one contiguous stream
-// Blocks of 256 triangles never span two groups (block table and bisection as in smooth.hip, COPIED here, not shared).  No atomics.
-#include "pr_common.h"
+// Blocks of 256 triangles never span two groups (mesh_lane, mesh_dev.h).  No atomics.
+#include "mesh_dev.h"
 
 namespace pr {
 
@@ -51,37 +51,6 @@ struct SampleParams {
     int32_t* record;              // (G n, 4) per sample: triangle (local, -1: none), U, V, 0
 };
 
-struct SampleLane {
-    int group;                    // -1: the block lies behind the last group
-    int first, size;              // the group's first row and its rows
-    int local;                    // row inside the group
-    bool live;
-};
-
-// the lane of block `b` of the triangle grid: `blk` / `first` are the block table and the clamped offsets
-__device__ __forceinline__ SampleLane sample_lane(int groups, const int32_t* blk, const int32_t* first, int b) {
-    SampleLane l;
-    const PR_GLOBAL_AS int32_t* table = as_global(blk);
-    l.group = -1;
-    l.first = l.size = l.local = 0;
-    l.live = false;
-    if (b >= table[groups]) return l;
-    int lo = 0, hi = groups;                  // table[lo] <= b < table[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (table[mid] <= b) lo = mid;
-        else hi = mid;
-    }
-    l.group = lo;
-    l.first = as_global(first)[lo];
-    l.size = as_global(first)[lo + 1] - l.first;
-    l.local = (b - table[lo]) * 256 + (int)threadIdx.x;
-    l.live = l.local < l.size;
-    return l;
-}
-
-__device__ __forceinline__ bool sample_finite(float x) { return __fsub_rn(x, x) == 0.f; }
-
 // One lane, serial over the groups (a handful): offsets that leave [0, total] or decrease are clamped, so that no later kernel follows
 // a bad offset out of an array; the block table is the running sum of ceil(size / 256).
 __global__ __launch_bounds__(64) void k_sample_init(SampleParams s) {
@@ -98,20 +67,10 @@ __global__ __launch_bounds__(64) void k_sample_init(SampleParams s) {
     }
 }
 
-struct SampleCorners {
-    int i[3];
-    bool in_range;                // three indices in [0, vsize)
-};
-
-// the corners of triangle `local` of the group whose triangles start at row `tfirst`; the indices are checked here
-__device__ __forceinline__ SampleCorners sample_corners(const SampleParams& s, int tfirst, int local, int vsize) {
-    SampleCorners c;
-    const PR_GLOBAL_AS int32_t* t = as_global(s.triangles) + ((size_t)tfirst + local) * 3;
-    c.i[0] = t[0];
-    c.i[1] = t[1];
-    c.i[2] = t[2];
-    c.in_range = c.i[0] >= 0 && c.i[0] < vsize && c.i[1] >= 0 && c.i[1] < vsize && c.i[2] >= 0 && c.i[2] < vsize;
-    return c;
+// mesh_corners of the call's triangles.  It takes the parameter block and reads the pointer itself: handed the pointer, k_sample_rows
+// loads its kernel arguments in another order.
+__device__ __forceinline__ MeshCorners sample_corners(const SampleParams& s, int tfirst, int local, int vsize) {
+    return mesh_corners(s.triangles, tfirst, local, vsize);
 }
 
 // the largest of the block's 256 values (none is NaN), valid in every thread.  lds: >= 4 doubles.
@@ -149,13 +108,13 @@ __device__ __forceinline__ unsigned long long sample_block_scan(unsigned long lo
 __global__ __launch_bounds__(256) void k_sample_area(SampleParams s) {
     __shared__ double lds[4];
     __shared__ int ilds[4];
-    const SampleLane l = sample_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
+    const MeshLane l = mesh_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
     if (l.group < 0) return;                  // (the whole block: nothing reads the rows of a block behind the last group)
     double area = -1.0;
     if (l.live) {
         const int vfirst = as_global(s.vfirst)[l.group];
         const int vsize = as_global(s.vfirst)[l.group + 1] - vfirst;
-        const SampleCorners c = sample_corners(s, l.first, l.local, vsize);
+        const MeshCorners c = sample_corners(s, l.first, l.local, vsize);
         bool valid = c.in_range && c.i[0] != c.i[1] && c.i[0] != c.i[2] && c.i[1] != c.i[2];
         if (valid) {
             const PR_GLOBAL_AS float* v = as_global(s.vertices) + (size_t)vfirst * 3;
@@ -165,7 +124,7 @@ __global__ __launch_bounds__(256) void k_sample_area(SampleParams s) {
 #pragma unroll
                 for (int x = 0; x < 3; ++x) {
                     p[e][x] = v[(size_t)c.i[e] * 3 + x];
-                    valid = valid && sample_finite(p[e][x]);
+                    valid = valid && mesh_finite(p[e][x]);
                 }
             }
             if (valid) {                      // k_audit_measure's area: every product and difference rounded on its own
@@ -222,7 +181,7 @@ __device__ __forceinline__ unsigned long long sample_weight(double area, double 
 __global__ __launch_bounds__(256) void k_sample_weight(SampleParams s) {
     __shared__ unsigned long long lds[4];
     __shared__ int ilds[4];
-    const SampleLane l = sample_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
+    const MeshLane l = mesh_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
     if (l.group < 0) return;                  // (the whole block)
     unsigned long long w = 0, total;
     bool valid = false;
@@ -268,7 +227,7 @@ __global__ __launch_bounds__(256) void k_sample_scan(SampleParams s) {
 
 __global__ __launch_bounds__(256) void k_sample_prefix(SampleParams s) {
     __shared__ unsigned long long lds[4];
-    const SampleLane l = sample_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
+    const MeshLane l = mesh_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
     if (l.group < 0) return;                  // (the whole block)
     unsigned long long w = 0, total;
     bool valid;
@@ -305,7 +264,7 @@ __device__ __forceinline__ float sample_mix(float b0, float b1, float b2, float 
 __device__ __forceinline__ void sample_normalise(const float* N, float* out) {
     // sqrtf, not __fsqrt_rn: the latter compiles to the bare v_sqrt_f32 (1 ulp), sqrtf to its correctly rounded refinement
     const float length = __builtin_sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(N[0], N[0]), __fmul_rn(N[1], N[1])), __fmul_rn(N[2], N[2])));
-    const bool fine = sample_finite(length) && length > 0.f;
+    const bool fine = mesh_finite(length) && length > 0.f;
 #pragma unroll
     for (int d = 0; d < 3; ++d) out[d] = fine ? __fdiv_rn(N[d], length) : 0.f;
 }
@@ -331,7 +290,7 @@ __global__ __launch_bounds__(256) void k_sample_draw(SampleParams s) {
             else lo = mid + 1;
         }
         if (lo < tsize) {                     // (always: W_last = W > pick - unless the workspace was damaged)
-            const SampleCorners c = sample_corners(s, tfirst, lo, vsize);
+            const MeshCorners c = sample_corners(s, tfirst, lo, vsize);
             if (c.in_range) {                 // (always: only a valid triangle has a weight)
                 t = lo;
                 U = d.U;
@@ -404,7 +363,7 @@ __global__ __launch_bounds__(256) void k_sample_rows(SampleParams s) {
         const unsigned int U = (unsigned int)rec.y, V = (unsigned int)rec.z;
         // the record is read from the workspace: checked here
         if (rec.x >= 0 && rec.x < tsize && U <= SAMPLE_ONE && V <= SAMPLE_ONE && U + V <= SAMPLE_ONE) {
-            const SampleCorners c = sample_corners(s, tfirst, rec.x, vsize);
+            const MeshCorners c = sample_corners(s, tfirst, rec.x, vsize);
             if (c.in_range) {
                 const float b1 = (float)U * 5.9604644775390625e-8f, b2 = (float)V * 5.9604644775390625e-8f;
                 const float b0 = (float)(SAMPLE_ONE - U - V) * 5.9604644775390625e-8f;
@@ -438,12 +397,6 @@ struct SamplePlan {
     int BT;
 };
 
-static size_t sample_region(size_t* at, size_t bytes) {
-    const size_t begin = *at;
-    *at += (bytes + 255) / 256 * 256;
-    return begin;
-}
-
 // Host checks of both entry points: no device work.
 static int plan_sample(const pr_mesh_sample_t* s, const char* who, SamplePlan* plan) {
     PR_REQUIRE(s != nullptr, "%s: NULL description", who);
@@ -475,18 +428,18 @@ static int plan_sample(const pr_mesh_sample_t* s, const char* who, SamplePlan* p
     const size_t T = (size_t)s->total_triangles, B = (size_t)plan->BT, G = (size_t)s->groups;
     const size_t table = (G + 1) * sizeof(int32_t);
     size_t at = 0;
-    plan->vfirst = sample_region(&at, table);
-    plan->tfirst = sample_region(&at, table);
-    plan->tblk = sample_region(&at, table);
-    plan->area = sample_region(&at, 8 * T);
-    plan->bmax = sample_region(&at, 8 * B);
-    plan->bvalid = sample_region(&at, 4 * B);
-    plan->bzero = sample_region(&at, 4 * B);
-    plan->bsum = sample_region(&at, 8 * B);
-    plan->boff = sample_region(&at, 8 * B);
-    plan->gmax = sample_region(&at, 8 * G);
-    plan->gtotal = sample_region(&at, 8 * G);
-    plan->record = sample_region(&at, 16 * G * (size_t)s->samples);
+    plan->vfirst = workspace_region(&at, table);
+    plan->tfirst = workspace_region(&at, table);
+    plan->tblk = workspace_region(&at, table);
+    plan->area = workspace_region(&at, 8 * T);
+    plan->bmax = workspace_region(&at, 8 * B);
+    plan->bvalid = workspace_region(&at, 4 * B);
+    plan->bzero = workspace_region(&at, 4 * B);
+    plan->bsum = workspace_region(&at, 8 * B);
+    plan->boff = workspace_region(&at, 8 * B);
+    plan->gmax = workspace_region(&at, 8 * G);
+    plan->gtotal = workspace_region(&at, 8 * G);
+    plan->record = workspace_region(&at, 16 * G * (size_t)s->samples);
     plan->bytes = at;
     return PR_OK;
 }
@@ -506,12 +459,7 @@ extern "C" int pr_mesh_sample(const pr_mesh_sample_t* s, void* workspace, size_t
     static_assert(sizeof(pr_mesh_sample_t) == 144, "the header states this size");
     SamplePlan plan;
     PR_TRY(plan_sample(s, "pr_mesh_sample", &plan));
-    PR_REQUIRE(workspace != nullptr, "pr_mesh_sample: NULL workspace");
-    PR_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-    if (workspace_bytes < plan.bytes) {
-        set_error("workspace too small: %zu bytes given, %zu needed", workspace_bytes, plan.bytes);
-        return PR_ERR_INVALID;
-    }
+    PR_TRY(check_workspace("pr_mesh_sample", workspace, workspace_bytes, plan.bytes));
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     SampleParams p;

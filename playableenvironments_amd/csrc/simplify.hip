@@ -15,9 +15,9 @@
 //   k_simplify_emit       per triangle: the survivors, in input order (not launched without out_triangles)
 // Lanes: one per element, 256-lane blocks that never span two groups.  The group sizes live on the device, so the vertex and triangle
 // grids are the host's upper bounds ceil(V / 256) + G and ceil(T / 256) + G; a block finds its group by bisection of the block table
-// and the blocks behind the last group only report a zero sum.  Integer atomics only.  No lane ever waits for another: an insertion
+// (mesh_lane, mesh_dev.h) and the blocks behind the last group only report a zero sum.  Integer atomics only.  No lane ever waits for another: an insertion
 // probes at most the 2 T_g slots of its group's region, which hold at most T_g keys.
-#include "pr_common.h"
+#include "mesh_dev.h"
 
 #include <math.h>
 
@@ -51,36 +51,6 @@ struct SimplifyParams {
     int32_t* tsum; int32_t* toff;       // (BT)
     int32_t* totals;              // [clusters, output triangles]
 };
-
-struct SimplifyLane {
-    int group;                    // -1: the block lies behind the last group
-    int first, size;              // the group's first row and its rows
-    int local;                    // row inside the group
-    bool live;
-};
-
-// the lane of a vertex or triangle block: `blk` / `first` are the block table and the clamped offsets of that kind
-__device__ __forceinline__ SimplifyLane simplify_lane(int groups, const int32_t* blk, const int32_t* first) {
-    SimplifyLane l;
-    const int b = (int)blockIdx.x;
-    const PR_GLOBAL_AS int32_t* table = as_global(blk);
-    l.group = -1;
-    l.first = l.size = l.local = 0;
-    l.live = false;
-    if (b >= table[groups]) return l;
-    int lo = 0, hi = groups;                  // table[lo] <= b < table[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (table[mid] <= b) lo = mid;
-        else hi = mid;
-    }
-    l.group = lo;
-    l.first = as_global(first)[lo];
-    l.size = as_global(first)[lo + 1] - l.first;
-    l.local = (b - table[lo]) * 256 + (int)threadIdx.x;
-    l.live = l.local < l.size;
-    return l;
-}
 
 __global__ __launch_bounds__(256) void k_simplify_init(SimplifyParams s) {
     const size_t stride = (size_t)gridDim.x * 256;
@@ -125,7 +95,7 @@ __global__ __launch_bounds__(64) void k_simplify_groups(SimplifyParams s) {
 // a wave is summed with a segmented scan first (a lane's terms are below 2^23, 64 of them fit an int) and only the last lane of the run
 // goes to memory.  Integer sums: the grouping does not show in the result.
 __global__ __launch_bounds__(256) void k_simplify_cluster(SimplifyParams s) {
-    const SimplifyLane l = simplify_lane(s.groups, s.vblk, s.vfirst);
+    const MeshLane l = mesh_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
     if (l.group < 0) return;                  // (the whole block)
     int cell = -1;
     int sum[7] = {0, 0, 0, 0, 0, 0, 0};       // members, f, quantised normal
@@ -228,7 +198,7 @@ __global__ __launch_bounds__(256) void k_simplify_vertices(SimplifyParams s) {
 }
 
 __global__ __launch_bounds__(256) void k_simplify_map(SimplifyParams s) {
-    const SimplifyLane l = simplify_lane(s.groups, s.vblk, s.vfirst);
+    const MeshLane l = mesh_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
     if (!l.live) return;
     const size_t row = (size_t)l.first + l.local;
     const int index = as_global(s.cnt)[(size_t)l.group * s.C + as_global(s.vmap)[row]];
@@ -238,7 +208,7 @@ __global__ __launch_bounds__(256) void k_simplify_map(SimplifyParams s) {
 
 // The corners of triangle `row` of the lane's group as output indices, rotated so that the smallest comes first.
 // Returns 0: kept, 1: degenerate, 2: an input index outside [0, V_g).
-__device__ __forceinline__ int simplify_corners(const SimplifyParams& s, const SimplifyLane& l, size_t row, int* o) {
+__device__ __forceinline__ int simplify_corners(const SimplifyParams& s, const MeshLane& l, size_t row, int* o) {
     const PR_GLOBAL_AS int32_t* t = as_global(s.triangles) + row * 3;
     const int vfirst = as_global(s.vfirst)[l.group];
     const int vsize = as_global(s.vfirst)[l.group + 1] - vfirst;
@@ -255,7 +225,7 @@ __device__ __forceinline__ int simplify_corners(const SimplifyParams& s, const S
 
 __global__ __launch_bounds__(256) void k_simplify_triangles(SimplifyParams s) {
     __shared__ int lds[4];
-    const SimplifyLane l = simplify_lane(s.groups, s.tblk, s.tfirst);
+    const MeshLane l = mesh_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
     if (l.group < 0) return;                  // (the whole block)
     int state = -1;
     if (l.live) {
@@ -293,7 +263,7 @@ __global__ __launch_bounds__(256) void k_simplify_triangles(SimplifyParams s) {
     }
 }
 
-__device__ __forceinline__ bool simplify_survives(const SimplifyParams& s, const SimplifyLane& l) {
+__device__ __forceinline__ bool simplify_survives(const SimplifyParams& s, const MeshLane& l) {
     if (!l.live) return false;
     const int row = l.first + l.local;
     const int slot = as_global(s.tslot)[row];
@@ -302,7 +272,7 @@ __device__ __forceinline__ bool simplify_survives(const SimplifyParams& s, const
 
 __global__ __launch_bounds__(256) void k_simplify_survivors(SimplifyParams s) {
     __shared__ int lds[4];
-    const SimplifyLane l = simplify_lane(s.groups, s.tblk, s.tfirst);
+    const MeshLane l = mesh_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
     int total;
     block_exclusive_scan_256(simplify_survives(s, l) ? 1 : 0, lds, &total);
     if (threadIdx.x == 0) as_global(s.tsum)[blockIdx.x] = total;
@@ -328,7 +298,7 @@ __global__ __launch_bounds__(256) void k_simplify_offsets(SimplifyParams s) {
 
 __global__ __launch_bounds__(256) void k_simplify_emit(SimplifyParams s) {
     __shared__ int lds[4];
-    const SimplifyLane l = simplify_lane(s.groups, s.tblk, s.tfirst);
+    const MeshLane l = mesh_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
     if (l.group < 0) return;                  // (the whole block)
     const bool survives = simplify_survives(s, l);
     int total;
@@ -346,14 +316,6 @@ struct SimplifyPlan {
     int C, D, BV, BT;
 };
 
-static size_t simplify_region(size_t* at, size_t bytes) {
-    const size_t begin = *at;
-    *at += (bytes + 255) / 256 * 256;
-    return begin;
-}
-
-static bool simplify_finite(float x) { return x - x == 0.f; }
-
 // Host checks of both entry points: no device work.
 static int plan_simplify(const pr_simplify_t* s, const char* who, SimplifyPlan* plan) {
     PR_REQUIRE(s != nullptr, "%s: NULL description", who);
@@ -362,8 +324,8 @@ static int plan_simplify(const pr_simplify_t* s, const char* who, SimplifyPlan* 
     for (int a = 0; a < 3; ++a) {
         PR_REQUIRE(s->cells[a] >= 1, "%s: cells[%d] = %d (>= 1)", who, a, s->cells[a]);
         cells *= (double)s->cells[a];
-        PR_REQUIRE(simplify_finite(s->cell[a]) && s->cell[a] > 0.f, "%s: cell[%d] = %g (finite, > 0)", who, a, (double)s->cell[a]);
-        PR_REQUIRE(simplify_finite(s->origin[a]), "%s: origin[%d] = %g (finite)", who, a, (double)s->origin[a]);
+        PR_REQUIRE(host_finite(s->cell[a]) && s->cell[a] > 0.f, "%s: cell[%d] = %g (finite, > 0)", who, a, (double)s->cell[a]);
+        PR_REQUIRE(host_finite(s->origin[a]), "%s: origin[%d] = %g (finite)", who, a, (double)s->origin[a]);
     }
     PR_REQUIRE(cells <= (double)PR_SIMPLIFY_MAX_CELLS, "%s: %d x %d x %d cells (at most 2^21 = %d)", who, s->cells[0], s->cells[1],
                s->cells[2], PR_SIMPLIFY_MAX_CELLS);
@@ -392,22 +354,22 @@ static int plan_simplify(const pr_simplify_t* s, const char* who, SimplifyPlan* 
     const size_t GC = (size_t)s->groups * (size_t)plan->C, V = (size_t)s->total_vertices, T = (size_t)s->total_triangles;
     const size_t table = ((size_t)s->groups + 1) * sizeof(int32_t);
     size_t at = 0;
-    plan->cnt = simplify_region(&at, 4 * GC);
-    plan->fsum = simplify_region(&at, 24 * GC);
-    plan->nsum = simplify_region(&at, s->normals ? 24 * GC : 0);
-    plan->vmap = simplify_region(&at, 4 * V);
-    plan->tslot = simplify_region(&at, 4 * T);
-    plan->keys = simplify_region(&at, 16 * T);
-    plan->tmin = simplify_region(&at, 8 * T);
-    plan->vfirst = simplify_region(&at, table);
-    plan->tfirst = simplify_region(&at, table);
-    plan->vblk = simplify_region(&at, table);
-    plan->tblk = simplify_region(&at, table);
-    plan->csum = simplify_region(&at, 4 * (size_t)s->groups * plan->D);
-    plan->coff = simplify_region(&at, 4 * (size_t)s->groups * plan->D);
-    plan->tsum = simplify_region(&at, 4 * (size_t)plan->BT);
-    plan->toff = simplify_region(&at, 4 * (size_t)plan->BT);
-    plan->totals = simplify_region(&at, 2 * sizeof(int32_t));
+    plan->cnt = workspace_region(&at, 4 * GC);
+    plan->fsum = workspace_region(&at, 24 * GC);
+    plan->nsum = workspace_region(&at, s->normals ? 24 * GC : 0);
+    plan->vmap = workspace_region(&at, 4 * V);
+    plan->tslot = workspace_region(&at, 4 * T);
+    plan->keys = workspace_region(&at, 16 * T);
+    plan->tmin = workspace_region(&at, 8 * T);
+    plan->vfirst = workspace_region(&at, table);
+    plan->tfirst = workspace_region(&at, table);
+    plan->vblk = workspace_region(&at, table);
+    plan->tblk = workspace_region(&at, table);
+    plan->csum = workspace_region(&at, 4 * (size_t)s->groups * plan->D);
+    plan->coff = workspace_region(&at, 4 * (size_t)s->groups * plan->D);
+    plan->tsum = workspace_region(&at, 4 * (size_t)plan->BT);
+    plan->toff = workspace_region(&at, 4 * (size_t)plan->BT);
+    plan->totals = workspace_region(&at, 2 * sizeof(int32_t));
     plan->bytes = at;
     PR_REQUIRE(at < ((size_t)1 << 62), "%s: the workspace sum overflows", who);       // (cannot happen below the bounds above)
     return PR_OK;
@@ -427,12 +389,7 @@ extern "C" int pr_simplify_mesh(const pr_simplify_t* s, void* workspace, size_t 
     using namespace pr;
     SimplifyPlan plan;
     PR_TRY(plan_simplify(s, "pr_simplify_mesh", &plan));
-    PR_REQUIRE(workspace != nullptr, "pr_simplify_mesh: NULL workspace");
-    PR_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-    if (workspace_bytes < plan.bytes) {
-        set_error("workspace too small: %zu bytes given, %zu needed", workspace_bytes, plan.bytes);
-        return PR_ERR_INVALID;
-    }
+    PR_TRY(check_workspace("pr_simplify_mesh", workspace, workspace_bytes, plan.bytes));
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     SimplifyParams p;

@@ -5,7 +5,7 @@
 // Nine launches plus one per step on the caller's stream, all kernels:
 //   k_smooth_init       zeroes the per-vertex counts and cursors, copies the positions into out_vertices (and into the second buffer when
 //                       there are steps), fills out_normals with zeros and vertex_state with -1; one lane of block 0 clamps the offsets
-//                       and builds the block tables (what k_weld_init does)
+//                       and builds the block tables (the rule: mesh_dev.h)
 //   k_smooth_count      per triangle: valid or dropped, an atomic add on its three vertices' counts; the kept flag with the three
 //                       positions the atomics returned; block sums
 //   k_smooth_sums       per vertex block: the sum of its counts
@@ -18,10 +18,10 @@
 //   k_smooth_step       (`steps` times) per movable vertex: the ordered umbrella mean and the step, from one buffer into the other
 //   k_smooth_normals    per vertex with 1 <= k <= max_degree: the ordered sum of its triangles' cross products, normalised
 //   k_smooth_finish     one grid, two block ranges: the CSR outputs (if asked for), per group the counts
-// Lanes: one per element, wave64, 256-lane blocks that never span two groups (block tables and bisection as in weld.hip, COPIED here,
-// not shared).  Integer atomics only, in the count and in the fill; the sort removes the order of arrival from every list that anything
-// later reads in order.
-#include "pr_common.h"
+// Lanes: one per element, wave64, 256-lane blocks that never span two groups (mesh_lane, mesh_dev.h; a triangle's checked corners are
+// mesh_corners).  Integer atomics only, in the count and in the fill; the sort removes the order of arrival from every list that
+// anything later reads in order.
+#include "mesh_dev.h"
 
 namespace pr {
 
@@ -56,37 +56,6 @@ struct SmoothParams {
     int32_t* tsum;                // (BT) valid triangles per triangle block
     int32_t* vpart;               // (BV, 6) per vertex block: the SMOOTH_P_ columns
 };
-
-struct SmoothLane {
-    int group;                    // -1: the block lies behind the last group
-    int first, size;              // the group's first row and its rows
-    int local;                    // row inside the group
-    bool live;
-};
-
-// the lane of block `b` of a vertex or triangle grid: `blk` / `first` are the block table and the clamped offsets of that kind
-__device__ __forceinline__ SmoothLane smooth_lane(int groups, const int32_t* blk, const int32_t* first, int b) {
-    SmoothLane l;
-    const PR_GLOBAL_AS int32_t* table = as_global(blk);
-    l.group = -1;
-    l.first = l.size = l.local = 0;
-    l.live = false;
-    if (b >= table[groups]) return l;
-    int lo = 0, hi = groups;                  // table[lo] <= b < table[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (table[mid] <= b) lo = mid;
-        else hi = mid;
-    }
-    l.group = lo;
-    l.first = as_global(first)[lo];
-    l.size = as_global(first)[lo + 1] - l.first;
-    l.local = (b - table[lo]) * 256 + (int)threadIdx.x;
-    l.live = l.local < l.size;
-    return l;
-}
-
-__device__ __forceinline__ bool smooth_finite(float x) { return __fsub_rn(x, x) == 0.f; }
 
 __global__ __launch_bounds__(256) void k_smooth_init(SmoothParams s) {
     const size_t stride = (size_t)gridDim.x * 256, at = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -125,25 +94,9 @@ __global__ __launch_bounds__(256) void k_smooth_init(SmoothParams s) {
     }
 }
 
-struct SmoothCorners {
-    int i[3];
-    bool in_range;                // three indices in [0, vsize)
-};
-
-// the corners of triangle `local` of the group whose triangles start at row `tfirst`; the indices are checked here
-__device__ __forceinline__ SmoothCorners smooth_corners(const SmoothParams& s, int tfirst, int local, int vsize) {
-    SmoothCorners c;
-    const PR_GLOBAL_AS int32_t* t = as_global(s.triangles) + ((size_t)tfirst + local) * 3;
-    c.i[0] = t[0];
-    c.i[1] = t[1];
-    c.i[2] = t[2];
-    c.in_range = c.i[0] >= 0 && c.i[0] < vsize && c.i[1] >= 0 && c.i[1] < vsize && c.i[2] >= 0 && c.i[2] < vsize;
-    return c;
-}
-
 __global__ __launch_bounds__(256) void k_smooth_count(SmoothParams s) {
     __shared__ int lds[4];
-    const SmoothLane l = smooth_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
+    const MeshLane l = mesh_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
     if (l.group < 0) {                        // (the whole block: behind the last group, its sum is 0)
         if (threadIdx.x == 0) as_global(s.tsum)[blockIdx.x] = 0;
         return;
@@ -152,14 +105,14 @@ __global__ __launch_bounds__(256) void k_smooth_count(SmoothParams s) {
     if (l.live) {
         const int vfirst = as_global(s.vfirst)[l.group];
         const int vsize = as_global(s.vfirst)[l.group + 1] - vfirst;
-        const SmoothCorners c = smooth_corners(s, l.first, l.local, vsize);
+        const MeshCorners c = mesh_corners(s.triangles, l.first, l.local, vsize);
         valid = c.in_range && c.i[0] != c.i[1] && c.i[0] != c.i[2] && c.i[1] != c.i[2];
         if (valid) {
             const PR_GLOBAL_AS float* v = as_global(s.vertices) + (size_t)vfirst * 3;
 #pragma unroll
             for (int e = 0; e < 3; ++e) {
                 const PR_GLOBAL_AS float* p = v + (size_t)c.i[e] * 3;
-                valid = valid && smooth_finite(p[0]) && smooth_finite(p[1]) && smooth_finite(p[2]);
+                valid = valid && mesh_finite(p[0]) && mesh_finite(p[1]) && mesh_finite(p[2]);
             }
         }
         // the value an atomic returns is a position in the vertex's list that nobody else gets: kept, 10 bits per corner, beside the
@@ -181,7 +134,7 @@ __global__ __launch_bounds__(256) void k_smooth_count(SmoothParams s) {
 }
 
 // k of the lane's vertex as the count kernel left it, kept inside [0, 3 T_g] (a triangle adds at most three)
-__device__ __forceinline__ int smooth_degree(const SmoothParams& s, const SmoothLane& l) {
+__device__ __forceinline__ int smooth_degree(const SmoothParams& s, const MeshLane& l) {
     const int tsize = as_global(s.tfirst)[l.group + 1] - as_global(s.tfirst)[l.group];
     const int k = as_global(s.vcount)[(size_t)l.first + l.local];
     return k < 0 ? 0 : (k > tsize ? tsize : k);
@@ -189,7 +142,7 @@ __device__ __forceinline__ int smooth_degree(const SmoothParams& s, const Smooth
 
 __global__ __launch_bounds__(256) void k_smooth_sums(SmoothParams s) {
     __shared__ int lds[4];
-    const SmoothLane l = smooth_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
+    const MeshLane l = mesh_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
     if (l.group < 0) {                        // (the whole block: behind the last group, its sum is 0)
         if (threadIdx.x == 0) as_global(s.vsum)[blockIdx.x] = 0;
         return;
@@ -220,7 +173,7 @@ __global__ __launch_bounds__(256) void k_smooth_scan(SmoothParams s) {
 
 __global__ __launch_bounds__(256) void k_smooth_offsets(SmoothParams s) {
     __shared__ int lds[4];
-    const SmoothLane l = smooth_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
+    const MeshLane l = mesh_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
     if (l.group < 0) return;                  // (the whole block)
     int total;
     const int ex = block_exclusive_scan_256(l.live ? smooth_degree(s, l) : 0, lds, &total);
@@ -236,13 +189,13 @@ __device__ __forceinline__ long long smooth_list_begin(const SmoothParams& s, si
 }
 
 __global__ __launch_bounds__(256) void k_smooth_fill(SmoothParams s) {
-    const SmoothLane l = smooth_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
+    const MeshLane l = mesh_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
     if (!l.live) return;
     const int packed = as_global(s.tkeep)[(size_t)l.first + l.local];
     if (!(packed & SMOOTH_KEPT)) return;
     const int vfirst = as_global(s.vfirst)[l.group];
     const int vsize = as_global(s.vfirst)[l.group + 1] - vfirst;
-    const SmoothCorners c = smooth_corners(s, l.first, l.local, vsize);      // (read again: checked again)
+    const MeshCorners c = mesh_corners(s.triangles, l.first, l.local, vsize);      // (read again: checked again)
     if (!c.in_range) return;
 #pragma unroll
     for (int e = 0; e < 3; ++e) {
@@ -266,7 +219,7 @@ __device__ __forceinline__ SmoothOthers smooth_others(const SmoothParams& s, int
     SmoothOthers o;
     o.x = o.y = -1;
     if ((unsigned)t >= (unsigned)tsize) return o;
-    const SmoothCorners c = smooth_corners(s, tfirst, t, vsize);
+    const MeshCorners c = mesh_corners(s.triangles, tfirst, t, vsize);
     if (!c.in_range) return o;
     if (v == c.i[0]) { o.x = c.i[1]; o.y = c.i[2]; }
     else if (v == c.i[1]) { o.x = c.i[2]; o.y = c.i[0]; }
@@ -277,7 +230,7 @@ __device__ __forceinline__ SmoothOthers smooth_others(const SmoothParams& s, int
 __global__ __launch_bounds__(256) void k_smooth_classify(SmoothParams s) {
     __shared__ int lds[4];
     __shared__ int largest[256];
-    const SmoothLane l = smooth_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
+    const MeshLane l = mesh_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
     if (l.group < 0) return;                  // (the whole block: k_smooth_finish reads the partials of the groups' blocks only)
     int state = 0, k = 0;
     if (l.live) {
@@ -286,7 +239,7 @@ __global__ __launch_bounds__(256) void k_smooth_classify(SmoothParams s) {
         const int tsize = as_global(s.tfirst)[l.group + 1] - tfirst;
         k = smooth_degree(s, l);
         const PR_GLOBAL_AS float* p = as_global(s.vertices) + row * 3;
-        const bool finite = smooth_finite(p[0]) && smooth_finite(p[1]) && smooth_finite(p[2]);
+        const bool finite = mesh_finite(p[0]) && mesh_finite(p[1]) && mesh_finite(p[2]);
         const bool pinned = s.pinned && as_global(s.pinned)[row] != 0;
         const long long begin = smooth_list_begin(s, row, k);
         const bool listed = k >= 1 && k <= s.max_degree && begin >= 0;
@@ -370,7 +323,7 @@ __global__ __launch_bounds__(256) void k_smooth_classify(SmoothParams s) {
 // One step: p' = p + f (mean - p) with the ordered umbrella mean, from `src` into `dst`.  A vertex that is not movable is not written:
 // both buffers hold its input words since k_smooth_init.
 __global__ __launch_bounds__(256) void k_smooth_step(SmoothParams s, const float* src, float* dst, float f) {
-    const SmoothLane l = smooth_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
+    const MeshLane l = mesh_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
     if (!l.live) return;
     const size_t row = (size_t)l.first + l.local;
     if (!(as_global(s.vstate)[row] & SMOOTH_MOVABLE)) return;
@@ -404,7 +357,7 @@ __global__ __launch_bounds__(256) void k_smooth_step(SmoothParams s, const float
 
 __global__ __launch_bounds__(256) void k_smooth_normals(SmoothParams s) {
     if (!s.out_normals) return;
-    const SmoothLane l = smooth_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
+    const MeshLane l = mesh_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
     if (!l.live) return;
     const size_t row = (size_t)l.first + l.local;
     const int state = as_global(s.vstate)[row];
@@ -420,7 +373,7 @@ __global__ __launch_bounds__(256) void k_smooth_normals(SmoothParams s) {
         for (int i = 0; i < k; ++i) {
             const int t = list[i];
             if ((unsigned)t >= (unsigned)tsize) { covered = false; break; }      // (never)
-            const SmoothCorners c = smooth_corners(s, tfirst, t, l.size);
+            const MeshCorners c = mesh_corners(s.triangles, tfirst, t, l.size);
             if (!c.in_range) { covered = false; break; }
             const PR_GLOBAL_AS float* a = v + (size_t)c.i[0] * 3;
             const PR_GLOBAL_AS float* b = v + (size_t)c.i[1] * 3;
@@ -443,7 +396,7 @@ __global__ __launch_bounds__(256) void k_smooth_normals(SmoothParams s) {
     if (covered) {
         // sqrtf, not __fsqrt_rn: the latter compiles to the bare v_sqrt_f32 (1 ulp), sqrtf to its correctly rounded refinement
         const float length = __builtin_sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(N[0], N[0]), __fmul_rn(N[1], N[1])), __fmul_rn(N[2], N[2])));
-        if (smooth_finite(length) && length > 0.f) {
+        if (mesh_finite(length) && length > 0.f) {
 #pragma unroll
             for (int d = 0; d < 3; ++d) out[d] = __fdiv_rn(N[d], length);
         }
@@ -507,12 +460,6 @@ struct SmoothPlan {
     int BV, BT;
 };
 
-static size_t smooth_region(size_t* at, size_t bytes) {
-    const size_t begin = *at;
-    *at += (bytes + 255) / 256 * 256;
-    return begin;
-}
-
 // Host checks of both entry points: no device work.
 static int plan_smooth(const pr_mesh_smooth_t* s, const char* who, SmoothPlan* plan) {
     PR_REQUIRE(s != nullptr, "%s: NULL description", who);
@@ -542,21 +489,21 @@ static int plan_smooth(const pr_mesh_smooth_t* s, const char* who, SmoothPlan* p
     const size_t V = (size_t)s->total_vertices, T = (size_t)s->total_triangles;
     const size_t table = ((size_t)s->groups + 1) * sizeof(int32_t);
     size_t at = 0;
-    plan->vfirst = smooth_region(&at, table);
-    plan->tfirst = smooth_region(&at, table);
-    plan->vblk = smooth_region(&at, table);
-    plan->tblk = smooth_region(&at, table);
-    plan->vcount = smooth_region(&at, 4 * V);
-    plan->voffset = smooth_region(&at, 4 * (V + 1));
-    plan->vcursor = smooth_region(&at, 4 * V);
-    plan->list = smooth_region(&at, 12 * T);
-    plan->tkeep = smooth_region(&at, 4 * T);
-    plan->second = smooth_region(&at, 12 * V);
-    plan->vstate = smooth_region(&at, 4 * V);
-    plan->vsum = smooth_region(&at, 4 * (size_t)plan->BV);
-    plan->voff = smooth_region(&at, 4 * ((size_t)plan->BV + 1));
-    plan->tsum = smooth_region(&at, 4 * (size_t)plan->BT);
-    plan->vpart = smooth_region(&at, (size_t)SMOOTH_PARTIALS * sizeof(int32_t) * (size_t)plan->BV);
+    plan->vfirst = workspace_region(&at, table);
+    plan->tfirst = workspace_region(&at, table);
+    plan->vblk = workspace_region(&at, table);
+    plan->tblk = workspace_region(&at, table);
+    plan->vcount = workspace_region(&at, 4 * V);
+    plan->voffset = workspace_region(&at, 4 * (V + 1));
+    plan->vcursor = workspace_region(&at, 4 * V);
+    plan->list = workspace_region(&at, 12 * T);
+    plan->tkeep = workspace_region(&at, 4 * T);
+    plan->second = workspace_region(&at, 12 * V);
+    plan->vstate = workspace_region(&at, 4 * V);
+    plan->vsum = workspace_region(&at, 4 * (size_t)plan->BV);
+    plan->voff = workspace_region(&at, 4 * ((size_t)plan->BV + 1));
+    plan->tsum = workspace_region(&at, 4 * (size_t)plan->BT);
+    plan->vpart = workspace_region(&at, (size_t)SMOOTH_PARTIALS * sizeof(int32_t) * (size_t)plan->BV);
     plan->bytes = at;
     return PR_OK;
 }
@@ -576,12 +523,7 @@ extern "C" int pr_mesh_smooth(const pr_mesh_smooth_t* s, void* workspace, size_t
     static_assert(sizeof(pr_mesh_smooth_t) == 120, "the header states this size");
     SmoothPlan plan;
     PR_TRY(plan_smooth(s, "pr_mesh_smooth", &plan));
-    PR_REQUIRE(workspace != nullptr, "pr_mesh_smooth: NULL workspace");
-    PR_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-    if (workspace_bytes < plan.bytes) {
-        set_error("workspace too small: %zu bytes given, %zu needed", workspace_bytes, plan.bytes);
-        return PR_ERR_INVALID;
-    }
+    PR_TRY(check_workspace("pr_mesh_smooth", workspace, workspace_bytes, plan.bytes));
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     SmoothParams p;

@@ -6,7 +6,7 @@
 // block sums), the block scan of both sums (k_scan_blocks_group), k_surface_offsets (the per-group offsets and the totals),
 // k_surface_vertices (vertex base per point, positions, normals), k_surface_triangles (indices).  A count-only call ends behind
 // the third.  Lanes: one per lattice point, 256-lane blocks that never span two groups.
-#include "pr_common.h"
+#include "mesh_dev.h"
 
 namespace pr {
 
@@ -298,12 +298,6 @@ struct SurfacePlan {
     int points, blocks;
 };
 
-static size_t surface_region(size_t* at, size_t bytes) {
-    const size_t begin = *at;
-    *at += (bytes + 255) / 256 * 256;
-    return begin;
-}
-
 // Host checks of both entry points: no device work.
 static int plan_surface(const pr_surface_t* s, const char* who, SurfacePlan* plan) {
     PR_REQUIRE(s != nullptr, "%s: NULL description", who);
@@ -327,14 +321,14 @@ static int plan_surface(const pr_surface_t* s, const char* who, SurfacePlan* pla
     plan->blocks = (int)((points + 255) / 256);
     const size_t lattice = (size_t)s->groups * (size_t)points, sums = (size_t)s->groups * plan->blocks * sizeof(int32_t);
     size_t at = 0;
-    plan->mask = surface_region(&at, lattice);
-    plan->tcount = surface_region(&at, lattice);
-    plan->base = surface_region(&at, lattice * sizeof(int32_t));
-    plan->vsum = surface_region(&at, sums);
-    plan->tsum = surface_region(&at, sums);
-    plan->voff = surface_region(&at, sums);
-    plan->toff = surface_region(&at, sums);
-    plan->totals = surface_region(&at, 2 * sizeof(int32_t));
+    plan->mask = workspace_region(&at, lattice);
+    plan->tcount = workspace_region(&at, lattice);
+    plan->base = workspace_region(&at, lattice * sizeof(int32_t));
+    plan->vsum = workspace_region(&at, sums);
+    plan->tsum = workspace_region(&at, sums);
+    plan->voff = workspace_region(&at, sums);
+    plan->toff = workspace_region(&at, sums);
+    plan->totals = workspace_region(&at, 2 * sizeof(int32_t));
     plan->bytes = at;
     return PR_OK;
 }
@@ -353,12 +347,7 @@ extern "C" int pr_extract_surface(const pr_surface_t* s, void* workspace, size_t
     using namespace pr;
     SurfacePlan plan;
     PR_TRY(plan_surface(s, "pr_extract_surface", &plan));
-    PR_REQUIRE(workspace != nullptr, "pr_extract_surface: NULL workspace");
-    PR_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-    if (workspace_bytes < plan.bytes) {
-        set_error("workspace too small: %zu bytes given, %zu needed", workspace_bytes, plan.bytes);
-        return PR_ERR_INVALID;
-    }
+    PR_TRY(check_workspace("pr_extract_surface", workspace, workspace_bytes, plan.bytes));
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     SurfaceParams p;

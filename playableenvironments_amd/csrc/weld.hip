@@ -4,7 +4,7 @@
 //
 // Eight launches on the caller's stream (seven with PR_WELD_COMPACT_ONLY, which has no table), all kernels:
 //   k_weld_init       empties the table, zeroes the referenced flags, fills both maps with -1; one lane of block 0 clamps the offsets
-//                     and builds the block tables (what k_audit_init does)
+//                     and builds the block tables (the rule: mesh_dev.h)
 //   k_weld_insert     per vertex: k_audit_weld's insertion into the group's open-addressing table of 2 V_g slots (value mode only)
 //   k_weld_lookup     per vertex: its representative - the final content of its key's slot; its own index with PR_WELD_COMPACT_ONLY;
 //                     -1 where a component is not finite
@@ -17,14 +17,14 @@
 //                     words where the width is a multiple of 4 and both arrays are 16-byte aligned, else in 32-bit words)
 //   k_weld_finish     one grid, three block ranges: per triangle the re-indexed corners and the triangle map, per vertex the vertex
 //                     map, per group the counts and the output offsets
-// Lanes: one per element, wave64, 256-lane blocks that never span two groups (block tables and bisection as in audit.hip, whose weld
-// scheme - weld_lane, weld_vertex, weld_same_values, the insertion and the lookup - is COPIED here, not shared: audit.hip stays as it
-// is).  Integer atomics only, in the insertion; everything later is plain stores of values that do not depend on arrival.
-#include "pr_common.h"
+// Lanes: one per element, wave64, 256-lane blocks that never span two groups (mesh_lane, mesh_dev.h).  The vertex classes are
+// pr_mesh_audit's because both units take them from mesh_vertex and mesh_same_values (mesh_dev.h, which also states the table's rule);
+// the two probe loops are written out here as in audit.hip.  Integer atomics only, in the insertion; everything later is plain stores
+// of values that do not depend on arrival.
+#include "mesh_dev.h"
 
 namespace pr {
 
-constexpr int WELD_EMPTY_VERTEX = 0x7FFFFFFF;              // above every vertex index: an atomic minimum can only lower a slot
 constexpr int WELD_COUNTS = 8;
 constexpr int WELD_MAX_ATTRIBUTE_WIDTH = 4096;
 enum { WELD_P_NON_FINITE, WELD_P_MERGED, WELD_P_UNREFERENCED, WELD_PARTIALS };
@@ -53,42 +53,11 @@ struct WeldParams {
     int32_t* vpart;               // (BV, 3) per vertex block: the WELD_P_ columns
 };
 
-struct WeldLane {
-    int group;                    // -1: the block lies behind the last group
-    int first, size;              // the group's first row and its rows
-    int local;                    // row inside the group
-    bool live;
-};
-
-// the lane of block `b` of a vertex or triangle grid: `blk` / `first` are the block table and the clamped offsets of that kind
-__device__ __forceinline__ WeldLane weld_lane(int groups, const int32_t* blk, const int32_t* first, int b) {
-    WeldLane l;
-    const PR_GLOBAL_AS int32_t* table = as_global(blk);
-    l.group = -1;
-    l.first = l.size = l.local = 0;
-    l.live = false;
-    if (b >= table[groups]) return l;
-    int lo = 0, hi = groups;                  // table[lo] <= b < table[hi]
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (table[mid] <= b) lo = mid;
-        else hi = mid;
-    }
-    l.group = lo;
-    l.first = as_global(first)[lo];
-    l.size = as_global(first)[lo + 1] - l.first;
-    l.local = (b - table[lo]) * 256 + (int)threadIdx.x;
-    l.live = l.local < l.size;
-    return l;
-}
-
-__device__ __forceinline__ bool weld_finite(float x) { return __fsub_rn(x, x) == 0.f; }
-
 __global__ __launch_bounds__(256) void k_weld_init(WeldParams s) {
     const size_t stride = (size_t)gridDim.x * 256, at = (size_t)blockIdx.x * 256 + threadIdx.x;
     const size_t V = (size_t)s.V, T = (size_t)s.T;
     if (!s.compact_only)
-        for (size_t i = at; i < 2 * V; i += stride) as_global(s.vslot)[i] = WELD_EMPTY_VERTEX;
+        for (size_t i = at; i < 2 * V; i += stride) as_global(s.vslot)[i] = MESH_EMPTY_VERTEX;
     for (size_t i = at; i < V; i += stride) {
         as_global(s.vref)[i] = 0;
         if (s.vertex_map) as_global(s.vertex_map)[i] = -1;       // (a row that no clamped group owns keeps this)
@@ -114,48 +83,19 @@ __global__ __launch_bounds__(256) void k_weld_init(WeldParams s) {
     }
 }
 
-struct WeldVertex {
-    float x[3];
-    bool finite;
-    unsigned int at;              // first slot of the probe sequence (local to the group's region)
-};
-
-// the values of vertex `row` and the start of its probe sequence in a region of `size` slots; -0 hashes as +0 (they compare equal)
-__device__ __forceinline__ WeldVertex weld_vertex(const WeldParams& s, size_t row, unsigned int size) {
-    WeldVertex v;
-    unsigned int bits[3];
-    v.finite = true;
-#pragma unroll
-    for (int a = 0; a < 3; ++a) {
-        v.x[a] = as_global(s.vertices)[row * 3 + a];
-        v.finite = v.finite && weld_finite(v.x[a]);
-        bits[a] = v.x[a] == 0.f ? 0u : __float_as_uint(v.x[a]);
-    }
-    const unsigned long long h = noise_mix(noise_mix((unsigned long long)bits[0] | (unsigned long long)bits[1] << 32) ^ bits[2]);
-    v.at = size ? (unsigned int)(h % size) : 0u;
-    return v;
-}
-
-// whether vertex `index` (local, read from a slot: checked here) of the group that starts at row `first` has the values of `v`
-__device__ __forceinline__ bool weld_same_values(const WeldParams& s, int first, int size, int index, const WeldVertex& v) {
-    if ((unsigned)index >= (unsigned)size) return false;
-    const PR_GLOBAL_AS float* o = as_global(s.vertices) + ((size_t)first + index) * 3;
-    return o[0] == v.x[0] && o[1] == v.x[1] && o[2] == v.x[2];
-}
-
 __global__ __launch_bounds__(256) void k_weld_insert(WeldParams s) {
-    const WeldLane l = weld_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
+    const MeshLane l = mesh_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
     if (!l.live) return;
     const unsigned int size = 2u * (unsigned int)l.size;
-    const WeldVertex v = weld_vertex(s, (size_t)l.first + l.local, size);
+    const MeshVertex v = mesh_vertex(s.vertices, (size_t)l.first + l.local, size);
     if (!v.finite) return;                    // (not inserted: it has no class)
     PR_GLOBAL_AS int32_t* region = as_global(s.vslot) + 2 * (size_t)l.first;
     unsigned int at = v.at;
     for (unsigned int probe = 0; probe < size; ++probe) {      // (ends at an empty slot or at the class: at most V_g classes in 2 V_g slots)
-        int seen = WELD_EMPTY_VERTEX;
+        int seen = MESH_EMPTY_VERTEX;
         if (__hip_atomic_compare_exchange_strong(region + at, &seen, l.local, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))
             return;
-        if (weld_same_values(s, l.first, l.size, seen, v)) {
+        if (mesh_same_values(s.vertices, l.first, l.size, seen, v)) {
             __hip_atomic_fetch_min(region + at, l.local, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             return;
         }
@@ -164,11 +104,11 @@ __global__ __launch_bounds__(256) void k_weld_insert(WeldParams s) {
 }
 
 __global__ __launch_bounds__(256) void k_weld_lookup(WeldParams s) {
-    const WeldLane l = weld_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
+    const MeshLane l = mesh_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
     if (!l.live) return;
     const unsigned int size = 2u * (unsigned int)l.size;
     const size_t row = (size_t)l.first + l.local;
-    const WeldVertex v = weld_vertex(s, row, size);
+    const MeshVertex v = mesh_vertex(s.vertices, row, size);
     int rep = -1;
     if (v.finite && s.compact_only) rep = l.local;             // (every finite vertex is its own representative)
     else if (v.finite) {
@@ -176,8 +116,8 @@ __global__ __launch_bounds__(256) void k_weld_lookup(WeldParams s) {
         unsigned int at = v.at;
         for (unsigned int probe = 0; probe < size; ++probe) {  // (the insertion has finished: the slots hold the minima)
             const int seen = region[at];
-            if (seen == WELD_EMPTY_VERTEX) break;
-            if (weld_same_values(s, l.first, l.size, seen, v)) {
+            if (seen == MESH_EMPTY_VERTEX) break;
+            if (mesh_same_values(s.vertices, l.first, l.size, seen, v)) {
                 rep = seen;
                 break;
             }
@@ -191,7 +131,7 @@ __global__ __launch_bounds__(256) void k_weld_lookup(WeldParams s) {
 // is read; with PR_WELD_COMPACT_ONLY a representative is an index, so a == b and a == c are decided on the nine coordinates.
 __global__ __launch_bounds__(256) void k_weld_classify(WeldParams s) {
     __shared__ int lds[4];
-    const WeldLane l = weld_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
+    const MeshLane l = mesh_lane(s.groups, s.tblk, s.tfirst, (int)blockIdx.x);
     if (l.group < 0) {                        // (the whole block: behind the last group, its sum is 0)
         if (threadIdx.x == 0) as_global(s.tsum)[blockIdx.x] = 0;
         return;
@@ -234,7 +174,7 @@ __global__ __launch_bounds__(256) void k_weld_classify(WeldParams s) {
 }
 
 // 0: not finite, 1: merged into a lower index, 2: a representative without a kept triangle, 3: a referenced representative
-__device__ __forceinline__ int weld_vertex_kind(const WeldParams& s, const WeldLane& l) {
+__device__ __forceinline__ int weld_vertex_kind(const WeldParams& s, const MeshLane& l) {
     const size_t row = (size_t)l.first + l.local;
     const int rep = as_global(s.vrep)[row];
     if (rep < 0) return 0;
@@ -244,7 +184,7 @@ __device__ __forceinline__ int weld_vertex_kind(const WeldParams& s, const WeldL
 
 __global__ __launch_bounds__(256) void k_weld_mark(WeldParams s) {
     __shared__ int lds[4];
-    const WeldLane l = weld_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
+    const MeshLane l = mesh_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
     if (l.group < 0) {                        // (the whole block: behind the last group, its sum is 0)
         if (threadIdx.x == 0) as_global(s.vsum)[blockIdx.x] = 0;
         return;
@@ -301,7 +241,7 @@ __device__ __forceinline__ void weld_copy_rows(const float* src, float* dst, int
 __global__ __launch_bounds__(256) void k_weld_vertices(WeldParams s) {
     __shared__ int lds[4];
     __shared__ int source[256];               // local index of the block's k-th output vertex
-    const WeldLane l = weld_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
+    const MeshLane l = mesh_lane(s.groups, s.vblk, s.vfirst, (int)blockIdx.x);
     if (l.group < 0) return;                  // (the whole block)
     const bool referenced = l.live && weld_vertex_kind(s, l) == 3;
     int rows;
@@ -325,7 +265,7 @@ __global__ __launch_bounds__(256) void k_weld_finish(WeldParams s) {
     __shared__ int lds[4];
     const int b = (int)blockIdx.x;
     if (b < s.BT) {
-        const WeldLane l = weld_lane(s.groups, s.tblk, s.tfirst, b);
+        const MeshLane l = mesh_lane(s.groups, s.tblk, s.tfirst, b);
         if (l.group < 0) return;              // (the whole block)
         const size_t row = (size_t)l.first + l.local;
         const bool kept = l.live && as_global(s.tkeep)[row] != 0;
@@ -348,7 +288,7 @@ __global__ __launch_bounds__(256) void k_weld_finish(WeldParams s) {
     }
     if (b < s.BT + s.BV) {
         if (!s.vertex_map) return;
-        const WeldLane l = weld_lane(s.groups, s.vblk, s.vfirst, b - s.BT);
+        const MeshLane l = mesh_lane(s.groups, s.vblk, s.vfirst, b - s.BT);
         if (!l.live) return;
         const size_t row = (size_t)l.first + l.local;
         const int rep = as_global(s.vrep)[row];
@@ -393,12 +333,6 @@ struct WeldPlan {
     int BV, BT;
 };
 
-static size_t weld_region(size_t* at, size_t bytes) {
-    const size_t begin = *at;
-    *at += (bytes + 255) / 256 * 256;
-    return begin;
-}
-
 // Host checks of both entry points: no device work.
 static int plan_weld(const pr_mesh_weld_t* s, const char* who, WeldPlan* plan) {
     PR_REQUIRE(s != nullptr, "%s: NULL description", who);
@@ -428,20 +362,20 @@ static int plan_weld(const pr_mesh_weld_t* s, const char* who, WeldPlan* plan) {
     const size_t V = (size_t)s->total_vertices, T = (size_t)s->total_triangles;
     const size_t table = ((size_t)s->groups + 1) * sizeof(int32_t);
     size_t at = 0;
-    plan->vfirst = weld_region(&at, table);
-    plan->tfirst = weld_region(&at, table);
-    plan->vblk = weld_region(&at, table);
-    plan->tblk = weld_region(&at, table);
-    plan->vslot = weld_region(&at, 8 * V);
-    plan->vrep = weld_region(&at, 4 * V);
-    plan->vref = weld_region(&at, 4 * V);
-    plan->vout = weld_region(&at, 4 * V);
-    plan->tkeep = weld_region(&at, 4 * T);
-    plan->vsum = weld_region(&at, 4 * (size_t)plan->BV);
-    plan->voff = weld_region(&at, 4 * ((size_t)plan->BV + 1));
-    plan->tsum = weld_region(&at, 4 * (size_t)plan->BT);
-    plan->toff = weld_region(&at, 4 * ((size_t)plan->BT + 1));
-    plan->vpart = weld_region(&at, (size_t)WELD_PARTIALS * sizeof(int32_t) * (size_t)plan->BV);
+    plan->vfirst = workspace_region(&at, table);
+    plan->tfirst = workspace_region(&at, table);
+    plan->vblk = workspace_region(&at, table);
+    plan->tblk = workspace_region(&at, table);
+    plan->vslot = workspace_region(&at, 8 * V);
+    plan->vrep = workspace_region(&at, 4 * V);
+    plan->vref = workspace_region(&at, 4 * V);
+    plan->vout = workspace_region(&at, 4 * V);
+    plan->tkeep = workspace_region(&at, 4 * T);
+    plan->vsum = workspace_region(&at, 4 * (size_t)plan->BV);
+    plan->voff = workspace_region(&at, 4 * ((size_t)plan->BV + 1));
+    plan->tsum = workspace_region(&at, 4 * (size_t)plan->BT);
+    plan->toff = workspace_region(&at, 4 * ((size_t)plan->BT + 1));
+    plan->vpart = workspace_region(&at, (size_t)WELD_PARTIALS * sizeof(int32_t) * (size_t)plan->BV);
     plan->bytes = at;
     return PR_OK;
 }
@@ -461,12 +395,7 @@ extern "C" int pr_mesh_weld(const pr_mesh_weld_t* s, void* workspace, size_t wor
     static_assert(sizeof(pr_mesh_weld_t) == 152, "the header states this size");
     WeldPlan plan;
     PR_TRY(plan_weld(s, "pr_mesh_weld", &plan));
-    PR_REQUIRE(workspace != nullptr, "pr_mesh_weld: NULL workspace");
-    PR_REQUIRE(((uintptr_t)workspace & 255) == 0, "workspace must be 256-byte aligned");
-    if (workspace_bytes < plan.bytes) {
-        set_error("workspace too small: %zu bytes given, %zu needed", workspace_bytes, plan.bytes);
-        return PR_ERR_INVALID;
-    }
+    PR_TRY(check_workspace("pr_mesh_weld", workspace, workspace_bytes, plan.bytes));
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     WeldParams p;
