@@ -175,11 +175,9 @@ class Mesh:
         if not (self.vertices.is_cuda and self.triangles.is_cuda):
             raise RuntimeError(NO_CPU)
         _, _, _, max_degree = _smooth_arguments(0, 0.0, None, max_degree)
-        V, T = self.vertices.size(0), self.triangles.size(0)
-        out = _smooth_packed(self.vertices.detach().to(torch.float32).reshape(-1, 3).contiguous(),
-                             self.triangles.detach().to(torch.int32).reshape(-1, 3).contiguous(), [0, V], [0, T], steps=0, lam=0.0,
-                             mu=0.0, max_degree=max_degree, pin_border=True, normals=False, incidence=True)
-        return out["incidence_offsets"], out["incidence"][:3 * T]
+        out = _smooth_packed(_pack_meshes([self], self.vertices.device), steps=0, lam=0.0, mu=0.0, max_degree=max_degree,
+                             pin_border=True, normals=False, incidence=True)
+        return out["incidence_offsets"], out["incidence"][:3 * self.triangles.size(0)]
 
     def keep_shells(self, n: int, compact: bool = False) -> "Mesh":
         """The mesh restricted to its ``n`` largest shells by triangle count (ties: the lower label first; ``MeshAudit.labels``):
@@ -212,6 +210,136 @@ class Mesh:
         return Mesh(self.vertices, self.triangles[keep], self.normals, self.features)
 
 
+@dataclass
+class _PackedMeshes:
+    """G meshes as the library reads them: ``vertices (max(V, 1), 3)`` fp32 and ``triangles (max(T, 1), 3)`` int32, concatenated,
+    contiguous, on one device; the host lists ``vo`` / ``to`` of G + 1 running offsets into them; ``V = vo[G]``, ``T = to[G]``;
+    ``normals (max(V, 1), 3)`` and ``attributes (max(V, 1), A)`` fp32 or None.  ``_packed`` makes one and states the rule for the
+    rows beyond V and T."""
+    vertices: torch.Tensor
+    triangles: torch.Tensor
+    vo: List[int]
+    to: List[int]
+    V: int
+    T: int
+    normals: Optional[torch.Tensor] = None
+    attributes: Optional[torch.Tensor] = None
+
+    @property
+    def groups(self) -> int:
+        return len(self.vo) - 1
+
+    def arguments(self):
+        """What every mesh description starts with - ``(vertices, triangles, vertex_offsets, triangle_offsets, V, T)`` - with the two
+        offset arrays as the rows of one new ``(2, G + 1)`` int32 device tensor."""
+        offsets = torch.tensor([self.vo, self.to], dtype=torch.int32).to(self.vertices.device)
+        return self.vertices, self.triangles, offsets[0], offsets[1], self.V, self.T
+
+
+def _packed(vertices, triangles, vo, to, normals=None, attributes=None) -> _PackedMeshes:
+    """The record of arrays that are packed already (``vo`` / ``to``: host lists).  THE PLACEHOLDER RULE: an empty tensor has no
+    address and the library refuses NULL for an input array, so with V == 0 every per-vertex array that is given - vertices, normals,
+    attributes - and with T == 0 the triangles are replaced by one uninitialised row, which nothing reads because the totals stay 0.
+    Outputs are the caller's: each site sizes them by its own rule."""
+    dev = vertices.device
+    if vo[-1] == 0:
+        vertices, normals, attributes = [None if x is None else torch.empty((1, x.size(1)), dtype=torch.float32, device=dev)
+                                         for x in (vertices, normals, attributes)]
+    if to[-1] == 0:
+        triangles = torch.empty((1, 3), dtype=torch.int32, device=dev)
+    return _PackedMeshes(vertices, triangles, vo, to, vo[-1], to[-1], normals, attributes)
+
+
+def _mesh_shapes(meshes) -> None:
+    for m in meshes:
+        if m.vertices.dim() != 2 or m.vertices.size(1) != 3 or m.triangles.dim() != 2 or m.triangles.size(1) != 3:
+            raise ValueError(f"a mesh has vertices (V, 3) and triangles (T, 3), got {list(m.vertices.shape)} / {list(m.triangles.shape)}")
+
+
+def _pack_meshes(meshes, dev, *, normals: bool = False, features: Optional[int] = None) -> _PackedMeshes:
+    """The meshes of a non-empty list concatenated on ``dev`` as fp32 / int32 rows - whatever their dtype - with their running
+    offsets (``_packed``).  ``normals``: the ``Mesh.normals`` too.  ``features``: their common width (``_feature_width``) - the
+    ``Mesh.features`` as fp32 attribute rows, none at width 0.  Pure torch: CPU tensors pack as device tensors do."""
+    _mesh_shapes(meshes)
+    pack = lambda parts, dtype, width=3: torch.cat([p.detach().to(device=dev, dtype=dtype).reshape(-1, width) for p in parts]).contiguous()
+    vertices = pack([m.vertices for m in meshes], torch.float32)
+    triangles = pack([m.triangles for m in meshes], torch.int32)
+    rows = pack([m.normals for m in meshes], torch.float32) if normals else None
+    if rows is not None and rows.size(0) != vertices.size(0):
+        raise ValueError("normals must have one row per vertex")
+    attributes = None
+    if features is not None:
+        if any(m.features.size(0) != m.vertices.size(0) for m in meshes):
+            raise ValueError("features must have one row per vertex")
+        attributes = pack([m.features for m in meshes], torch.float32, features) if features else None
+    vo, to = [0], [0]
+    for m in meshes:
+        vo.append(vo[-1] + m.vertices.size(0))
+        to.append(to[-1] + m.triangles.size(0))
+    return _packed(vertices, triangles, vo, to, rows, attributes)
+
+
+def _feature_width(meshes, cap: int) -> Optional[int]:
+    """The width of the meshes' feature rows where EVERY mesh has ``(V, F)`` features with one common F - 0 included: the caller
+    says what no columns mean -, else None.  More than ``cap`` columns raise."""
+    if not all(m.features is not None and m.features.dim() == 2 for m in meshes) or len({m.features.size(1) for m in meshes}) != 1:
+        return None
+    width = meshes[0].features.size(1)
+    if width > cap:
+        raise ValueError(f"features can be at most {cap} wide, got {width}")
+    return width
+
+
+def _listed(meshes, who: str) -> List[Mesh]:
+    meshes = list(meshes)
+    if not meshes:
+        raise ValueError(f"{who} needs at least one mesh")
+    return meshes
+
+
+def _device_of(meshes):
+    if not all(m.vertices.is_cuda and m.triangles.is_cuda for m in meshes):
+        raise RuntimeError(NO_CPU)
+    return meshes[0].vertices.device
+
+
+def _set_mesh_header(s, vertex_offsets, total_vertices, total_triangles, flags: int = 0) -> None:
+    s.groups = vertex_offsets.numel() - 1
+    s.total_vertices = int(total_vertices)
+    s.total_triangles = int(total_triangles)
+    s.flags = flags
+
+
+def _set_grid(s, origin, cell, cells) -> None:
+    for a in range(3):
+        s.origin[a] = float(origin[a])
+        s.cell[a] = float(cell[a])
+        s.cells[a] = int(cells[a])
+
+
+def _set_pointers(s, **tensors):
+    """The pointer fields of a description by name: the tensor's address, NULL for None.  Returns the description."""
+    for name, t in tensors.items():
+        setattr(s, name, None if t is None else t.data_ptr())
+    return s
+
+
+def _call(name: str, description, workspace: torch.Tensor, size: int, dev) -> None:
+    """One library call with a workspace, on the current stream of ``dev``."""
+    _lib.check(getattr(_lib.load(), name)(C.byref(description), workspace.data_ptr(), size, torch.cuda.current_stream(dev).cuda_stream),
+               name)
+
+
+def _call_with_workspace(size_name: str, name: str, description, dev):
+    """Asks ``size_name`` what ``description`` needs, allocates it on ``dev`` and makes the call ``name`` with it.  Returns
+    ``(workspace, size)`` for the count-then-emit sites, whose second ``_call`` uses the same workspace."""
+    size = C.c_size_t()
+    _lib.check(getattr(_lib.load(), size_name)(C.byref(description), C.byref(size)), size_name)
+    workspace = torch.empty(size.value, dtype=torch.uint8, device=dev)
+    _call(name, description, workspace, size.value, dev)
+    return workspace, size.value
+
+
 def surface_struct(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float, vertex_offsets: torch.Tensor,
                    triangle_offsets: torch.Tensor, vertices: Optional[torch.Tensor] = None, normals: Optional[torch.Tensor] = None,
                    triangles: Optional[torch.Tensor] = None) -> _lib.Surface:
@@ -222,15 +350,10 @@ def surface_struct(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: flo
         s.points[a] = sigma.size(1 + a)
         s.axis[a] = axes[a].data_ptr()
     s.level = float(level)
-    s.sigma = sigma.data_ptr()
     s.max_vertices = 0 if vertices is None else vertices.size(0)
     s.max_triangles = 0 if triangles is None else triangles.size(0)
-    s.vertices = None if vertices is None else vertices.data_ptr()
-    s.normals = None if normals is None else normals.data_ptr()
-    s.triangles = None if triangles is None else triangles.data_ptr()
-    s.vertex_offsets = vertex_offsets.data_ptr()
-    s.triangle_offsets = triangle_offsets.data_ptr()
-    return s
+    return _set_pointers(s, sigma=sigma, vertices=vertices, normals=normals, triangles=triangles, vertex_offsets=vertex_offsets,
+                         triangle_offsets=triangle_offsets)
 
 
 def components_struct(sigma: torch.Tensor, level: float, counts: torch.Tensor, *, labels: Optional[torch.Tensor] = None,
@@ -246,12 +369,7 @@ def components_struct(sigma: torch.Tensor, level: float, counts: torch.Tensor, *
     c.min_points = int(min_points)
     c.keep_largest = int(keep_largest)
     c.fill = float(level if fill is None else fill)
-    c.sigma = sigma.data_ptr()
-    c.labels = None if labels is None else labels.data_ptr()
-    c.sizes = None if sizes is None else sizes.data_ptr()
-    c.sigma_out = None if sigma_out is None else sigma_out.data_ptr()
-    c.counts = counts.data_ptr()
-    return c
+    return _set_pointers(c, sigma=sigma, labels=labels, sizes=sizes, sigma_out=sigma_out, counts=counts)
 
 
 def _lattice(sigma: torch.Tensor) -> torch.Tensor:
@@ -264,16 +382,10 @@ def _lattice(sigma: torch.Tensor) -> torch.Tensor:
 
 def _run_components(sigma: torch.Tensor, level: float, **outputs) -> torch.Tensor:
     """One ``pr_label_components`` call on the current stream of ``sigma``'s device; returns ``counts (G, 4)``."""
-    lib = _lib.load()
     dev = sigma.device
     with torch.cuda.device(dev):
         counts = torch.empty((sigma.size(0), 4), dtype=torch.int32, device=dev)
-        c = components_struct(sigma, level, counts, **outputs)
-        size = C.c_size_t()
-        _lib.check(lib.pr_components_workspace_size(C.byref(c), C.byref(size)), "pr_components_workspace_size")
-        workspace = torch.empty(size.value, dtype=torch.uint8, device=dev)
-        _lib.check(lib.pr_label_components(C.byref(c), workspace.data_ptr(), size.value, torch.cuda.current_stream(dev).cuda_stream),
-                   "pr_label_components")
+        _call_with_workspace("pr_components_workspace_size", "pr_label_components", components_struct(sigma, level, counts, **outputs), dev)
     return counts
 
 
@@ -342,12 +454,9 @@ def band_struct(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float,
         rows = [t.size(0) for t in (point_index, positions, values) if t is not None]
         max_points = rows[0] if rows else 0
     b.max_points = int(max_points)
-    b.sigma = sigma.data_ptr()
-    b.point_offsets = point_offsets.data_ptr()
-    b.counts = counts.data_ptr()
-    for name, t in (("active", active), ("point_index", point_index), ("positions", positions), ("values", values), ("exact", exact)):
-        setattr(b, name, None if t is None or t.numel() == 0 else t.data_ptr())
-    return b
+    some = lambda t: None if t is None or t.numel() == 0 else t       # (the band's own rule: an optional array without elements is NULL)
+    return _set_pointers(b, sigma=sigma, point_offsets=point_offsets, counts=counts, active=some(active),
+                         point_index=some(point_index), positions=some(positions), values=some(values), exact=some(exact))
 
 
 def refine_band(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float, *, stride: int, guard: int = 1, evaluate):
@@ -385,23 +494,18 @@ def refine_band(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float,
         if axes[a].dim() != 1 or axes[a].numel() != sigma.size(1 + a):
             raise ValueError(f"axes[{a}] must hold {sigma.size(1 + a)} coordinates, got {list(axes[a].shape)}")
     G = sigma.size(0)
-    lib = _lib.load()
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
         point_offsets = torch.empty(G + 1, dtype=torch.int32, device=dev)
         counts = torch.empty((G, 4), dtype=torch.int32, device=dev)
         count = band_struct(sigma, axes, level, stride, guard, point_offsets, counts)
-        size = C.c_size_t()
-        _lib.check(lib.pr_band_workspace_size(C.byref(count), C.byref(size)), "pr_band_workspace_size")
-        workspace = torch.empty(size.value, dtype=torch.uint8, device=dev)
-        _lib.check(lib.pr_band_plan(C.byref(count), workspace.data_ptr(), size.value, stream), "pr_band_plan")
+        workspace, size = _call_with_workspace("pr_band_workspace_size", "pr_band_plan", count, dev)
         offsets = point_offsets.cpu().tolist()                               # (the host synchronisation)
         rows = offsets[G]
         positions = torch.empty((rows, 3), dtype=torch.float32, device=dev)
         values = torch.empty(rows, dtype=torch.float32, device=dev)
         if rows > 0:
             emit = band_struct(sigma, axes, level, stride, guard, point_offsets, counts, positions=positions)
-            _lib.check(lib.pr_band_plan(C.byref(emit), workspace.data_ptr(), size.value, stream), "pr_band_plan")
+            _call("pr_band_plan", emit, workspace, size, dev)
             for g in range(G):
                 if offsets[g + 1] > offsets[g]:
                     got = evaluate(g, positions[offsets[g]:offsets[g + 1]])
@@ -410,7 +514,7 @@ def refine_band(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float,
                     values[offsets[g]:offsets[g + 1]] = got.detach().reshape(-1).to(device=dev, dtype=torch.float32)
         exact = torch.empty(sigma.shape, dtype=torch.uint8, device=dev)
         fill = band_struct(sigma, axes, level, stride, guard, point_offsets, counts, values=values, exact=exact)
-        _lib.check(lib.pr_band_fill(C.byref(fill), workspace.data_ptr(), size.value, stream), "pr_band_fill")
+        _call("pr_band_fill", fill, workspace, size, dev)
     return sigma, exact, counts
 
 
@@ -422,22 +526,14 @@ def simplify_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offs
                     keep_duplicates: bool = False) -> _lib.Simplify:
     """``pr_simplify_t`` over prepared tensors (fp32 / int32, contiguous, one device); the capacities are the outputs' rows."""
     s = _lib.Simplify()
-    s.groups = vertex_offsets.numel() - 1
-    s.total_vertices = int(total_vertices)
-    s.total_triangles = int(total_triangles)
-    s.flags = _lib.SIMPLIFY_KEEP_DUPLICATES if keep_duplicates else 0
-    for a in range(3):
-        s.origin[a] = float(origin[a])
-        s.cell[a] = float(cell[a])
-        s.cells[a] = int(cells[a])
+    _set_mesh_header(s, vertex_offsets, total_vertices, total_triangles, _lib.SIMPLIFY_KEEP_DUPLICATES if keep_duplicates else 0)
+    _set_grid(s, origin, cell, cells)
     s.max_vertices = 0 if out_vertices is None else out_vertices.size(0)
     s.max_triangles = 0 if out_triangles is None else out_triangles.size(0)
-    for name, t in (("vertices", vertices), ("normals", normals), ("triangles", triangles), ("vertex_offsets", vertex_offsets),
-                    ("triangle_offsets", triangle_offsets), ("out_vertices", out_vertices), ("out_normals", out_normals),
-                    ("out_triangles", out_triangles), ("vertex_map", vertex_map), ("counts", counts),
-                    ("out_vertex_offsets", out_vertex_offsets), ("out_triangle_offsets", out_triangle_offsets)):
-        setattr(s, name, None if t is None else t.data_ptr())
-    return s
+    return _set_pointers(s, vertices=vertices, normals=normals, triangles=triangles, vertex_offsets=vertex_offsets,
+                         triangle_offsets=triangle_offsets, out_vertices=out_vertices, out_normals=out_normals,
+                         out_triangles=out_triangles, vertex_map=vertex_map, counts=counts, out_vertex_offsets=out_vertex_offsets,
+                         out_triangle_offsets=out_triangle_offsets)
 
 
 def _cluster_grid(origin, cell, cells):
@@ -475,36 +571,24 @@ def lattice_cluster_grid(axes: Sequence, k: int):
     return origin, cell, cells
 
 
-def _simplify_packed(vertices, normals, triangles, vertex_offsets, triangle_offsets, origin, cell, cells, keep_duplicates):
-    """``pr_simplify_mesh`` on packed meshes (device tensors; ``vertex_offsets`` / ``triangle_offsets`` are host lists): a counting
-    call, one read-back of the two offset arrays, an exactly sized emitting call.  Returns the list of meshes."""
-    lib = _lib.load()
-    dev = vertices.device
-    G, V, T = len(vertex_offsets) - 1, vertex_offsets[-1], triangle_offsets[-1]
-    if vertices.size(0) == 0:                                      # (an empty tensor has no address: the library refuses NULL)
-        vertices = torch.empty((1, 3), dtype=torch.float32, device=dev)
-        normals = None if normals is None else torch.empty((1, 3), dtype=torch.float32, device=dev)
-    if triangles.size(0) == 0:
-        triangles = torch.empty((1, 3), dtype=torch.int32, device=dev)
+def _simplify_packed(p: _PackedMeshes, origin, cell, cells, keep_duplicates):
+    """``pr_simplify_mesh`` on packed meshes: a counting call, one read-back of the two offset arrays, an exactly sized emitting
+    call.  Returns the list of meshes."""
+    dev, G = p.vertices.device, p.groups
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        offsets_in = torch.tensor([vertex_offsets, triangle_offsets], dtype=torch.int32).to(dev)
         offsets = torch.empty((2, G + 1), dtype=torch.int32, device=dev)
         counts = torch.empty((G, 4), dtype=torch.int32, device=dev)
-        common = (vertices, triangles, offsets_in[0], offsets_in[1], V, T, origin, cell, cells, counts, offsets[0], offsets[1])
-        count = simplify_struct(*common, normals=normals, keep_duplicates=keep_duplicates)
-        size = C.c_size_t()
-        _lib.check(lib.pr_simplify_workspace_size(C.byref(count), C.byref(size)), "pr_simplify_workspace_size")
-        workspace = torch.empty(size.value, dtype=torch.uint8, device=dev)
-        _lib.check(lib.pr_simplify_mesh(C.byref(count), workspace.data_ptr(), size.value, stream), "pr_simplify_mesh")
+        common = (*p.arguments(), origin, cell, cells, counts, offsets[0], offsets[1])
+        count = simplify_struct(*common, normals=p.normals, keep_duplicates=keep_duplicates)
+        workspace, size = _call_with_workspace("pr_simplify_workspace_size", "pr_simplify_mesh", count, dev)
         out_vo, out_to = offsets.cpu().tolist()                             # (the host synchronisation)
         out_v = torch.empty((out_vo[G], 3), dtype=torch.float32, device=dev)
-        out_n = None if normals is None else torch.empty((out_vo[G], 3), dtype=torch.float32, device=dev)
+        out_n = None if p.normals is None else torch.empty((out_vo[G], 3), dtype=torch.float32, device=dev)
         out_t = torch.empty((out_to[G], 3), dtype=torch.int32, device=dev)
         if out_vo[G] > 0:
-            emit = simplify_struct(*common, normals=normals, out_vertices=out_v, out_normals=out_n,
+            emit = simplify_struct(*common, normals=p.normals, out_vertices=out_v, out_normals=out_n,
                                    out_triangles=out_t if out_to[G] > 0 else None, keep_duplicates=keep_duplicates)
-            _lib.check(lib.pr_simplify_mesh(C.byref(emit), workspace.data_ptr(), size.value, stream), "pr_simplify_mesh")
+            _call("pr_simplify_mesh", emit, workspace, size, dev)
     return [Mesh(out_v[out_vo[g]:out_vo[g + 1]], out_t[out_to[g]:out_to[g + 1]], None if out_n is None else out_n[out_vo[g]:out_vo[g + 1]])
             for g in range(G)]
 
@@ -519,28 +603,11 @@ def simplify_meshes(meshes: Sequence[Mesh], origin, cell, cells, *, keep_duplica
     The meshes are packed, counted, and - after reading the two offset arrays back, the ONE host synchronisation - emitted into
     exactly sized tensors.  Returns one mesh per input; they have normals iff every input has them; ``features`` are not carried
     over.  There is no CPU fallback."""
-    meshes = list(meshes)
-    if not meshes:
-        raise ValueError("simplify_meshes needs at least one mesh")
-    if not all(m.vertices.is_cuda and m.triangles.is_cuda for m in meshes):
-        raise RuntimeError(NO_CPU)
+    meshes = _listed(meshes, "simplify_meshes")
+    dev = _device_of(meshes)
     origin, cell, cells = _cluster_grid(origin, cell, cells)
-    dev = meshes[0].vertices.device
-    for m in meshes:
-        if m.vertices.dim() != 2 or m.vertices.size(1) != 3 or m.triangles.dim() != 2 or m.triangles.size(1) != 3:
-            raise ValueError(f"a mesh has vertices (V, 3) and triangles (T, 3), got {list(m.vertices.shape)} / {list(m.triangles.shape)}")
-    with_normals = all(m.normals is not None for m in meshes)
-    pack = lambda parts, dtype: torch.cat([p.detach().to(device=dev, dtype=dtype).reshape(-1, 3) for p in parts]).contiguous()
-    vertices = pack([m.vertices for m in meshes], torch.float32)
-    triangles = pack([m.triangles for m in meshes], torch.int32)
-    normals = pack([m.normals for m in meshes], torch.float32) if with_normals else None
-    if normals is not None and normals.size(0) != vertices.size(0):
-        raise ValueError("normals must have one row per vertex")
-    vertex_offsets, triangle_offsets = [0], [0]
-    for m in meshes:
-        vertex_offsets.append(vertex_offsets[-1] + m.vertices.size(0))
-        triangle_offsets.append(triangle_offsets[-1] + m.triangles.size(0))
-    return _simplify_packed(vertices, normals, triangles, vertex_offsets, triangle_offsets, origin, cell, cells, keep_duplicates)
+    p = _pack_meshes(meshes, dev, normals=all(m.normals is not None for m in meshes))
+    return _simplify_packed(p, origin, cell, cells, keep_duplicates)
 
 
 def raycast_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offsets: torch.Tensor, triangle_offsets: torch.Tensor,
@@ -552,23 +619,15 @@ def raycast_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offse
     """``pr_raycast_t`` over prepared tensors (fp32 / int32, contiguous, one device); ``max_references`` is the rows of ``references``,
     ``rays`` the second dimension of ``origins (G, N, 3)``."""
     s = _lib.Raycast()
-    s.groups = vertex_offsets.numel() - 1
-    s.total_vertices = int(total_vertices)
-    s.total_triangles = int(total_triangles)
-    s.flags = _lib.RAYCAST_CULL_BACK if cull_back else 0
-    for a in range(3):
-        s.origin[a] = float(origin[a])
-        s.cell[a] = float(cell[a])
-        s.cells[a] = int(cells[a])
+    _set_mesh_header(s, vertex_offsets, total_vertices, total_triangles, _lib.RAYCAST_CULL_BACK if cull_back else 0)
+    _set_grid(s, origin, cell, cells)
     s.max_references = 0 if references is None else references.size(0)
     s.rays = 0 if origins is None else origins.size(1)
     s.t_min = float(t_min)
     s.t_max = float(t_max)
-    for name, x in (("vertices", vertices), ("triangles", triangles), ("vertex_offsets", vertex_offsets),
-                    ("triangle_offsets", triangle_offsets), ("cell_offsets", cell_offsets), ("references", references),
-                    ("origins", origins), ("directions", directions), ("t", t), ("triangle", triangle), ("barycentric", barycentric)):
-        setattr(s, name, None if x is None else x.data_ptr())
-    return s
+    return _set_pointers(s, vertices=vertices, triangles=triangles, vertex_offsets=vertex_offsets, triangle_offsets=triangle_offsets,
+                         cell_offsets=cell_offsets, references=references, origins=origins, directions=directions, t=t,
+                         triangle=triangle, barycentric=barycentric)
 
 
 def _ray_grid(origin, cell, cells):
@@ -591,6 +650,13 @@ class RayHits:
     group: Optional[torch.Tensor] = None
 
 
+def _nearest_group(values: torch.Tensor, triangle: torch.Tensor):
+    """The smallest of ``values (G, N)`` over the groups and the group it belongs to, -1 where that group found no triangle."""
+    nearest, group = torch.min(values, dim=0)
+    hit = triangle.gather(0, group.unsqueeze(0)).squeeze(0) >= 0
+    return nearest, torch.where(hit, group, torch.full_like(group, -1))
+
+
 class RayGrid:
     """G meshes sorted into a uniform cell grid for closest-hit ray queries (``pr_raycast_build`` / ``pr_raycast_query``,
     include/playrender.h).  ``RayGrid.build`` makes one; it holds the packed meshes, the per-cell lists and nothing else, and serves
@@ -603,61 +669,59 @@ class RayGrid:
         self.total_vertices, self.total_triangles = totals
         self.origin, self.cell, self.cells = grid
         self.cell_offsets, self.references = cell_offsets, references
+        self.host_triangle_offsets = None                               # (``build`` knows them; ``_triangle_bounds`` reads them)
 
     @property
     def groups(self) -> int:
         return self.vertex_offsets.numel() - 1
 
+    def _description(self):
+        """The ten arguments every description of a query against this grid starts with."""
+        return (self.vertices, self.triangles, self.vertex_offsets, self.triangle_offsets, self.total_vertices, self.total_triangles,
+                self.origin, self.cell, self.cells, self.cell_offsets)
+
+    @property
+    def _references(self) -> Optional[torch.Tensor]:
+        return self.references if self.references.numel() else None     # (a grid without references passes NULL)
+
+    def _triangle_bounds(self) -> List[int]:
+        """The G + 1 triangle offsets on the host; a grid that ``build`` did not make reads them back."""
+        return self.host_triangle_offsets or self.triangle_offsets.cpu().tolist()
+
+    def _group_points(self, x: torch.Tensor, what: str = "points") -> torch.Tensor:
+        """``x (G, N, 3)``, or ``(N, 3)`` for every group, as fp32 ``(G, N, 3)`` on the grid's device."""
+        G = self.groups
+        if x.dim() not in (2, 3) or x.size(-1) != 3:
+            raise ValueError(f"{what} must be (G, N, 3) or (N, 3), got {list(x.shape)}")
+        if x.dim() == 3 and x.size(0) != G:
+            raise ValueError(f"the grid holds {G} groups, the {what} are {list(x.shape)}")
+        return (x if x.dim() == 3 else x.unsqueeze(0).expand(G, -1, -1)).detach().to(device=self.vertices.device, dtype=torch.float32).contiguous()
+
     @classmethod
     def build(cls, meshes: Sequence[Mesh], origin, cell, cells) -> "RayGrid":
-        """Packs the meshes as ``simplify_meshes`` does and sorts their triangles into the grid of ``cells[a]`` cells of size ``cell[a]``
+        """Packs the meshes (``_pack_meshes``) and sorts their triangles into the grid of ``cells[a]`` cells of size ``cell[a]``
         from ``origin[a]`` on (at most 1024 per axis, 2^21 in all; ``bounding_grid`` and ``lattice_cluster_grid`` supply one): a
         counting call, one read-back of the number of references - the ONE host synchronisation - and an exactly sized emitting call.
         A triangle that is not inside the grid's box is tested by every ray: a grid around the meshes is the fast one."""
-        meshes = list(meshes)
-        if not meshes:
-            raise ValueError("RayGrid.build needs at least one mesh")
-        if not all(m.vertices.is_cuda and m.triangles.is_cuda for m in meshes):
-            raise RuntimeError(NO_CPU)
+        meshes = _listed(meshes, "RayGrid.build")
+        dev = _device_of(meshes)
         grid = _ray_grid(origin, cell, cells)
-        dev = meshes[0].vertices.device
-        for m in meshes:
-            if m.vertices.dim() != 2 or m.vertices.size(1) != 3 or m.triangles.dim() != 2 or m.triangles.size(1) != 3:
-                raise ValueError(f"a mesh has vertices (V, 3) and triangles (T, 3), got {list(m.vertices.shape)} / {list(m.triangles.shape)}")
-        pack = lambda parts, dtype: torch.cat([p.detach().to(device=dev, dtype=dtype).reshape(-1, 3) for p in parts]).contiguous()
-        vertices = pack([m.vertices for m in meshes], torch.float32)
-        triangles = pack([m.triangles for m in meshes], torch.int32)
-        vo, to = [0], [0]
-        for m in meshes:
-            vo.append(vo[-1] + m.vertices.size(0))
-            to.append(to[-1] + m.triangles.size(0))
-        if vertices.size(0) == 0:                                      # (an empty tensor has no address: the library refuses NULL)
-            vertices = torch.empty((1, 3), dtype=torch.float32, device=dev)
-        if triangles.size(0) == 0:
-            triangles = torch.empty((1, 3), dtype=torch.int32, device=dev)
-        G = len(meshes)
-        lists = G * (grid[2][0] * grid[2][1] * grid[2][2] + 1)
-        lib = _lib.load()
+        p = _pack_meshes(meshes, dev)
+        lists = p.groups * (grid[2][0] * grid[2][1] * grid[2][2] + 1)
         with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            offsets = torch.tensor([vo, to], dtype=torch.int32).to(dev)
+            mesh = p.arguments()
             cell_offsets = torch.empty(lists + 1, dtype=torch.int32, device=dev)
-            common = (vertices, triangles, offsets[0], offsets[1], vo[-1], to[-1], *grid, cell_offsets)
-            count = raycast_struct(*common)
-            size = C.c_size_t()
-            _lib.check(lib.pr_raycast_workspace_size(C.byref(count), C.byref(size)), "pr_raycast_workspace_size")
-            workspace = torch.empty(size.value, dtype=torch.uint8, device=dev)
-            _lib.check(lib.pr_raycast_build(C.byref(count), workspace.data_ptr(), size.value, stream), "pr_raycast_build")
+            workspace, size = _call_with_workspace("pr_raycast_workspace_size", "pr_raycast_build",
+                                                   raycast_struct(*mesh, *grid, cell_offsets), dev)
             R = int(cell_offsets[lists].item())                                 # (the host synchronisation)
             if R < 0:
                 raise RuntimeError("the grid holds 2^31 or more references: use a coarser grid")
             references = torch.empty(R, dtype=torch.int32, device=dev)
             if R > 0:
-                emit = raycast_struct(*common, references=references)
-                _lib.check(lib.pr_raycast_build(C.byref(emit), workspace.data_ptr(), size.value, stream), "pr_raycast_build")
-        grid_ = cls(vertices, triangles, offsets[0], offsets[1], (vo[-1], to[-1]), grid, cell_offsets, references)
-        grid_.host_triangle_offsets = to
-        return grid_
+                _call("pr_raycast_build", raycast_struct(*mesh, *grid, cell_offsets, references=references), workspace, size, dev)
+        made = cls(*mesh[:4], (p.V, p.T), grid, cell_offsets, references)
+        made.host_triangle_offsets = p.to
+        return made
 
     def audit(self, labels: bool = False) -> List["MeshAudit"]:
         """How the meshes this grid holds are made up (``pr_mesh_audit`` on the packed arrays, one ``MeshAudit`` per group): the
@@ -666,11 +730,8 @@ class RayGrid:
         was not made by ``build`` reads the triangle offsets back)."""
         if not self.vertices.is_cuda:
             raise RuntimeError(NO_CPU)
-        counts, measures, shell = _audit_packed(self.vertices, self.triangles, self.vertex_offsets, self.triangle_offsets,
-                                                self.total_vertices, self.total_triangles, bool(labels))
-        to = None
-        if labels:
-            to = getattr(self, "host_triangle_offsets", None) or self.triangle_offsets.cpu().tolist()
+        counts, measures, shell = _audit_packed(*self._description()[:6], bool(labels))
+        to = self._triangle_bounds() if labels else None
         return [MeshAudit(counts[g], measures[g], shell[to[g]:to[g + 1]] if labels else None) for g in range(self.groups)]
 
     def sample(self, n: int, *, seed: int, first: int = 0, normals: Optional[str] = "face") -> List["SurfaceSamples"]:
@@ -683,9 +744,7 @@ class RayGrid:
         n, seed, first = _sample_arguments(n, seed, first, self.groups)
         if not self.vertices.is_cuda:
             raise RuntimeError(NO_CPU)
-        out = _sample_packed(self.vertices, self.triangles, self.vertex_offsets, self.triangle_offsets, self.total_vertices,
-                             self.total_triangles, n, seed, first, face=normals == "face")
-        return _surface_samples(out, self.groups)
+        return _surface_samples(_sample_packed(*self._description()[:6], n, seed, first, face=normals == "face"), self.groups)
 
     def cast(self, origins: torch.Tensor, directions: torch.Tensor, *, t_min: float = 0.0, t_max: float = math.inf,
              cull_back: bool = False, barycentric: bool = False, nearest: bool = False) -> RayHits:
@@ -699,27 +758,20 @@ class RayGrid:
         if math.isnan(float(t_min)) or math.isnan(float(t_max)):
             raise ValueError(f"t_min and t_max must not be NaN, got {t_min}, {t_max}")
         G, dev = self.groups, self.vertices.device
-        if origins.shape != directions.shape or origins.dim() not in (2, 3) or origins.size(-1) != 3:
+        if origins.shape != directions.shape or origins.dim() not in (2, 3) or origins.size(-1) != 3:          # (the two as a pair)
             raise ValueError(f"origins and directions must both be (G, N, 3) or (N, 3), got {list(origins.shape)} / {list(directions.shape)}")
-        if origins.dim() == 3 and origins.size(0) != G:
-            raise ValueError(f"the grid holds {G} groups, the rays are {list(origins.shape)}")
-        prepare = lambda x: (x if x.dim() == 3 else x.unsqueeze(0).expand(G, -1, -1)).detach().to(device=dev, dtype=torch.float32).contiguous()
-        origins, directions = prepare(origins), prepare(directions)
+        origins, directions = self._group_points(origins, "rays"), self._group_points(directions, "rays")
         N = origins.size(1)
         hits = RayHits(torch.empty((G, N), dtype=torch.float32, device=dev), torch.empty((G, N), dtype=torch.int32, device=dev),
                        torch.empty((G, N, 2), dtype=torch.float32, device=dev) if barycentric else None)
         if N > 0:
             with torch.cuda.device(dev):
-                s = raycast_struct(self.vertices, self.triangles, self.vertex_offsets, self.triangle_offsets, self.total_vertices,
-                                   self.total_triangles, self.origin, self.cell, self.cells, self.cell_offsets,
-                                   references=self.references if self.references.numel() else None, origins=origins, directions=directions,
+                s = raycast_struct(*self._description(), references=self._references, origins=origins, directions=directions,
                                    t=hits.t, triangle=hits.triangle, barycentric=hits.barycentric, t_min=t_min, t_max=t_max,
                                    cull_back=cull_back)
                 _lib.check(_lib.load().pr_raycast_query(C.byref(s), torch.cuda.current_stream(dev).cuda_stream), "pr_raycast_query")
         if nearest:
-            hits.nearest_t, group = torch.min(hits.t, dim=0)
-            hit = hits.triangle.gather(0, group.unsqueeze(0)).squeeze(0) >= 0
-            hits.group = torch.where(hit, group, torch.full_like(group, -1))
+            hits.nearest_t, hits.group = _nearest_group(hits.t, hits.triangle)
         return hits
 
     def closest(self, points: torch.Tensor, *, max_distance: float, point: bool = False, barycentric: bool = False,
@@ -736,27 +788,18 @@ class RayGrid:
         if math.isnan(float(max_distance)) or float(max_distance) < 0:
             raise ValueError(f"max_distance must be >= 0 and not NaN, got {max_distance}")
         G, dev = self.groups, self.vertices.device
-        if points.dim() not in (2, 3) or points.size(-1) != 3:
-            raise ValueError(f"points must be (G, N, 3) or (N, 3), got {list(points.shape)}")
-        if points.dim() == 3 and points.size(0) != G:
-            raise ValueError(f"the grid holds {G} groups, the points are {list(points.shape)}")
-        points = (points if points.dim() == 3 else points.unsqueeze(0).expand(G, -1, -1)).detach().to(device=dev, dtype=torch.float32).contiguous()
+        points = self._group_points(points)
         N = points.size(1)
         found = ClosestPoints(torch.empty((G, N), dtype=torch.float32, device=dev), torch.empty((G, N), dtype=torch.int32, device=dev),
                               torch.empty((G, N, 3), dtype=torch.float32, device=dev) if point else None,
                               torch.empty((G, N, 2), dtype=torch.float32, device=dev) if barycentric else None)
         if N > 0:
             with torch.cuda.device(dev):
-                s = closest_struct(self.vertices, self.triangles, self.vertex_offsets, self.triangle_offsets, self.total_vertices,
-                                   self.total_triangles, self.origin, self.cell, self.cells, self.cell_offsets,
-                                   references=self.references if self.references.numel() else None, points=points,
-                                   distance=found.distance, triangle=found.triangle, point=found.point, barycentric=found.barycentric,
-                                   max_distance=max_distance)
+                s = closest_struct(*self._description(), references=self._references, points=points, distance=found.distance,
+                                   triangle=found.triangle, point=found.point, barycentric=found.barycentric, max_distance=max_distance)
                 _lib.check(_lib.load().pr_closest_query(C.byref(s), torch.cuda.current_stream(dev).cuda_stream), "pr_closest_query")
         if nearest:
-            found.nearest_distance, group = torch.min(found.distance, dim=0)
-            hit = found.triangle.gather(0, group.unsqueeze(0)).squeeze(0) >= 0
-            found.group = torch.where(hit, group, torch.full_like(group, -1))
+            found.nearest_distance, found.group = _nearest_group(found.distance, found.triangle)
         return found
 
     def winding(self, points: torch.Tensor, *, axis: int = 2, crossings: bool = False) -> "Winding":
@@ -771,11 +814,7 @@ class RayGrid:
         if not points.is_cuda:
             raise RuntimeError(NO_CPU)
         G, dev = self.groups, self.vertices.device
-        if points.dim() not in (2, 3) or points.size(-1) != 3:
-            raise ValueError(f"points must be (G, N, 3) or (N, 3), got {list(points.shape)}")
-        if points.dim() == 3 and points.size(0) != G:
-            raise ValueError(f"the grid holds {G} groups, the points are {list(points.shape)}")
-        points = (points if points.dim() == 3 else points.unsqueeze(0).expand(G, -1, -1)).detach().to(device=dev, dtype=torch.float32).contiguous()
+        points = self._group_points(points)
         try:
             axis = operator.index(axis)
         except TypeError:
@@ -787,10 +826,8 @@ class RayGrid:
                         torch.empty((G, N), dtype=torch.int32, device=dev) if crossings else None)
         if N > 0:
             with torch.cuda.device(dev):
-                s = inside_struct(self.vertices, self.triangles, self.vertex_offsets, self.triangle_offsets, self.total_vertices,
-                                  self.total_triangles, self.origin, self.cell, self.cells, self.cell_offsets,
-                                  references=self.references if self.references.numel() else None, points=points, axis=axis,
-                                  winding=found.winding, crossings=found.crossings)
+                s = inside_struct(*self._description(), references=self._references, points=points, axis=axis, winding=found.winding,
+                                  crossings=found.crossings)
                 _lib.check(_lib.load().pr_inside_query(C.byref(s), torch.cuda.current_stream(dev).cuda_stream), "pr_inside_query")
         return found
 
@@ -835,49 +872,28 @@ class RayGrid:
         if self_:
             if meshes is not None or transform is not None:
                 raise ValueError("self_=True queries the grid's own meshes: meshes and transform must be None")
-            to = getattr(self, "host_triangle_offsets", None) or self.triangle_offsets.cpu().tolist()
+            to = self._triangle_bounds()
             query = {}
             QT = self.total_triangles
         else:
             meshes = list(meshes) if meshes is not None else []
             if len(meshes) != G:
                 raise ValueError(f"the grid holds {G} groups, got {len(meshes)} meshes")
-            if not all(m.vertices.is_cuda and m.triangles.is_cuda for m in meshes):
-                raise RuntimeError(NO_CPU)
-            for m in meshes:
-                if m.vertices.dim() != 2 or m.vertices.size(1) != 3 or m.triangles.dim() != 2 or m.triangles.size(1) != 3:
-                    raise ValueError(f"a mesh has vertices (V, 3) and triangles (T, 3), got {list(m.vertices.shape)} / {list(m.triangles.shape)}")
-            pack = lambda parts, dtype: torch.cat([p.detach().to(device=dev, dtype=dtype).reshape(-1, 3) for p in parts]).contiguous()
-            q_vertices, q_triangles = pack([m.vertices for m in meshes], torch.float32), pack([m.triangles for m in meshes], torch.int32)
-            vo, to = [0], [0]
-            for m in meshes:
-                vo.append(vo[-1] + m.vertices.size(0))
-                to.append(to[-1] + m.triangles.size(0))
-            QT = to[-1]
-            if q_vertices.size(0) == 0:                                # (an empty tensor has no address: the library refuses NULL)
-                q_vertices = torch.empty((1, 3), dtype=torch.float32, device=dev)
-            if q_triangles.size(0) == 0:
-                q_triangles = torch.empty((1, 3), dtype=torch.int32, device=dev)
-            q_offsets = torch.tensor([vo, to], dtype=torch.int32).to(dev)
-            query = dict(q_vertices=q_vertices, q_triangles=q_triangles, q_vertex_offsets=q_offsets[0], q_triangle_offsets=q_offsets[1],
-                         q_total_vertices=vo[-1], q_total_triangles=QT, transform=_pose_rows(transform, G, dev))
-        lib = _lib.load()
+            _device_of(meshes)
+            q = _pack_meshes(meshes, dev)                              # (on the grid's device)
+            to, QT = q.to, q.T
+            names = ("q_vertices", "q_triangles", "q_vertex_offsets", "q_triangle_offsets", "q_total_vertices", "q_total_triangles")
+            query = dict(zip(names, q.arguments()), transform=_pose_rows(transform, G, dev))
         count = torch.empty(max(QT, 1), dtype=torch.int32, device=dev)
         first = torch.empty(max(QT, 1), dtype=torch.int32, device=dev)
         offsets = torch.empty(QT + 1, dtype=torch.int32, device=dev)
         pair_rows = segment_rows = None
         bounds = [0] * (G + 1)
         with torch.cuda.device(dev):
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            common = (self.vertices, self.triangles, self.vertex_offsets, self.triangle_offsets, self.total_vertices,
-                      self.total_triangles, self.origin, self.cell, self.cells, self.cell_offsets)
-            outputs = dict(references=self.references if self.references.numel() else None, count=count, first=first,
-                           pair_offsets=offsets, self_=self_, **query)
-            s = intersect_struct(*common, **outputs)
-            size = C.c_size_t()
-            _lib.check(lib.pr_mesh_intersect_workspace_size(C.byref(s), C.byref(size)), "pr_mesh_intersect_workspace_size")
-            workspace = torch.empty(size.value, dtype=torch.uint8, device=dev)
-            _lib.check(lib.pr_mesh_intersect(C.byref(s), workspace.data_ptr(), size.value, stream), "pr_mesh_intersect")
+            common = self._description()
+            outputs = dict(references=self._references, count=count, first=first, pair_offsets=offsets, self_=self_, **query)
+            workspace, size = _call_with_workspace("pr_mesh_intersect_workspace_size", "pr_mesh_intersect",
+                                                   intersect_struct(*common, **outputs), dev)
             if pairs or segments:
                 bounds = offsets[torch.tensor(to, dtype=torch.int64, device=dev)].cpu().tolist()          # (the host synchronisation)
                 P = bounds[-1]
@@ -886,8 +902,7 @@ class RayGrid:
                 pair_rows = torch.empty((P, 2), dtype=torch.int32, device=dev)
                 segment_rows = torch.empty((P, 2, 3), dtype=torch.float32, device=dev) if segments else None
                 if P > 0:
-                    s = intersect_struct(*common, pairs=pair_rows, segments=segment_rows, **outputs)
-                    _lib.check(lib.pr_mesh_intersect(C.byref(s), workspace.data_ptr(), size.value, stream), "pr_mesh_intersect")
+                    _call("pr_mesh_intersect", intersect_struct(*common, pairs=pair_rows, segments=segment_rows, **outputs), workspace, size, dev)
                     # (packed query row, target) as one key: the rows of a query are already adjacent, the sort orders them inside
                     row = torch.repeat_interleave(torch.arange(QT, dtype=torch.int64, device=dev), count[:QT].to(torch.int64), output_size=P)
                     order = torch.sort(row * (self.total_triangles + 1) + pair_rows[:, 1].to(torch.int64)).indices
@@ -917,22 +932,13 @@ def inside_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offset
     """``pr_inside_t`` over prepared tensors (fp32 / int32, contiguous, one device); ``max_references`` is the rows of ``references``,
     ``count`` the second dimension of ``points (G, N, 3)``."""
     s = _lib.Inside()
-    s.groups = vertex_offsets.numel() - 1
-    s.total_vertices = int(total_vertices)
-    s.total_triangles = int(total_triangles)
-    s.flags = 0
-    for a in range(3):
-        s.origin[a] = float(origin[a])
-        s.cell[a] = float(cell[a])
-        s.cells[a] = int(cells[a])
+    _set_mesh_header(s, vertex_offsets, total_vertices, total_triangles)
+    _set_grid(s, origin, cell, cells)
     s.max_references = 0 if references is None else references.size(0)
     s.count = 0 if points is None else points.size(1)
     s.axis = int(axis)
-    for name, x in (("vertices", vertices), ("triangles", triangles), ("vertex_offsets", vertex_offsets),
-                    ("triangle_offsets", triangle_offsets), ("cell_offsets", cell_offsets), ("references", references),
-                    ("points", points), ("winding", winding), ("crossings", crossings)):
-        setattr(s, name, None if x is None else x.data_ptr())
-    return s
+    return _set_pointers(s, vertices=vertices, triangles=triangles, vertex_offsets=vertex_offsets, triangle_offsets=triangle_offsets,
+                         cell_offsets=cell_offsets, references=references, points=points, winding=winding, crossings=crossings)
 
 
 def closest_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offsets: torch.Tensor, triangle_offsets: torch.Tensor,
@@ -944,22 +950,14 @@ def closest_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offse
     """``pr_closest_t`` over prepared tensors (fp32 / int32, contiguous, one device); ``max_references`` is the rows of ``references``,
     ``count`` the second dimension of ``points (G, N, 3)``."""
     s = _lib.Closest()
-    s.groups = vertex_offsets.numel() - 1
-    s.total_vertices = int(total_vertices)
-    s.total_triangles = int(total_triangles)
-    s.flags = 0
-    for a in range(3):
-        s.origin[a] = float(origin[a])
-        s.cell[a] = float(cell[a])
-        s.cells[a] = int(cells[a])
+    _set_mesh_header(s, vertex_offsets, total_vertices, total_triangles)
+    _set_grid(s, origin, cell, cells)
     s.max_references = 0 if references is None else references.size(0)
     s.count = 0 if points is None else points.size(1)
     s.max_distance = float(max_distance)
-    for name, x in (("vertices", vertices), ("triangles", triangles), ("vertex_offsets", vertex_offsets),
-                    ("triangle_offsets", triangle_offsets), ("cell_offsets", cell_offsets), ("references", references),
-                    ("points", points), ("distance", distance), ("triangle", triangle), ("point", point), ("barycentric", barycentric)):
-        setattr(s, name, None if x is None else x.data_ptr())
-    return s
+    return _set_pointers(s, vertices=vertices, triangles=triangles, vertex_offsets=vertex_offsets, triangle_offsets=triangle_offsets,
+                         cell_offsets=cell_offsets, references=references, points=points, distance=distance, triangle=triangle,
+                         point=point, barycentric=barycentric)
 
 
 @dataclass
@@ -1007,20 +1005,14 @@ def audit_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offsets
                  labels: Optional[torch.Tensor] = None) -> _lib.MeshAudit:
     """``pr_mesh_audit_t`` over prepared tensors (fp32 / int32 / fp64, contiguous, one device)."""
     s = _lib.MeshAudit()
-    s.groups = vertex_offsets.numel() - 1
-    s.total_vertices = int(total_vertices)
-    s.total_triangles = int(total_triangles)
-    s.flags = 0
-    for name, x in (("vertices", vertices), ("triangles", triangles), ("vertex_offsets", vertex_offsets),
-                    ("triangle_offsets", triangle_offsets), ("counts", counts), ("measures", measures), ("labels", labels)):
-        setattr(s, name, None if x is None else x.data_ptr())
-    return s
+    _set_mesh_header(s, vertex_offsets, total_vertices, total_triangles)
+    return _set_pointers(s, vertices=vertices, triangles=triangles, vertex_offsets=vertex_offsets, triangle_offsets=triangle_offsets,
+                         counts=counts, measures=measures, labels=labels)
 
 
 def _audit_packed(vertices, triangles, vertex_offsets, triangle_offsets, V: int, T: int, labels: bool):
-    """One ``pr_mesh_audit`` call on packed device tensors, on the current stream: ``(counts (G, 12), measures (G, 8), labels (T) or
-    None)``.  The workspace is sized on the host; nothing is read back."""
-    lib = _lib.load()
+    """One ``pr_mesh_audit`` call on packed device tensors (``_PackedMeshes.arguments`` or a grid's), on the current stream:
+    ``(counts (G, 12), measures (G, 8), labels (T) or None)``.  The workspace is sized on the host; nothing is read back."""
     dev = vertices.device
     G = vertex_offsets.numel() - 1
     with torch.cuda.device(dev):
@@ -1028,12 +1020,8 @@ def _audit_packed(vertices, triangles, vertex_offsets, triangle_offsets, V: int,
         measures = torch.empty((G, _lib.AUDIT_MEASURES), dtype=torch.float64, device=dev)
         shell = torch.empty(T, dtype=torch.int32, device=dev) if labels else None
         s = audit_struct(vertices, triangles, vertex_offsets, triangle_offsets, V, T, counts, measures=measures,
-                         labels=shell if labels and T > 0 else None)
-        size = C.c_size_t()
-        _lib.check(lib.pr_mesh_audit_workspace_size(C.byref(s), C.byref(size)), "pr_mesh_audit_workspace_size")
-        workspace = torch.empty(size.value, dtype=torch.uint8, device=dev)
-        _lib.check(lib.pr_mesh_audit(C.byref(s), workspace.data_ptr(), size.value, torch.cuda.current_stream(dev).cuda_stream),
-                   "pr_mesh_audit")
+                         labels=shell if labels and T > 0 else None)         # (no triangles: an empty ``shell`` is returned, NULL is passed)
+        _call_with_workspace("pr_mesh_audit_workspace_size", "pr_mesh_audit", s, dev)
     return counts, measures, shell
 
 
@@ -1045,31 +1033,12 @@ def audit_meshes(meshes: Sequence[Mesh], *, labels: bool = False) -> List[MeshAu
     signed volume (positive for the mesher's orientation), area-weighted centroid - float64 sums in a fixed tree, equal from run to
     run.  ``labels=True``: also the shell of every triangle (``Mesh.keep_shells`` uses them).
 
-    The meshes are packed as ``simplify_meshes`` packs them; the workspace is sized on the host; one call on the current stream
+    The meshes are packed (``_pack_meshes``); the workspace is sized on the host; one call on the current stream
     and NO host synchronisation - ``MeshAudit.report()`` is the read-back.  There is no CPU fallback."""
-    meshes = list(meshes)
-    if not meshes:
-        raise ValueError("audit_meshes needs at least one mesh")
-    if not all(m.vertices.is_cuda and m.triangles.is_cuda for m in meshes):
-        raise RuntimeError(NO_CPU)
-    dev = meshes[0].vertices.device
-    for m in meshes:
-        if m.vertices.dim() != 2 or m.vertices.size(1) != 3 or m.triangles.dim() != 2 or m.triangles.size(1) != 3:
-            raise ValueError(f"a mesh has vertices (V, 3) and triangles (T, 3), got {list(m.vertices.shape)} / {list(m.triangles.shape)}")
-    pack = lambda parts, dtype: torch.cat([p.detach().to(device=dev, dtype=dtype).reshape(-1, 3) for p in parts]).contiguous()
-    vertices = pack([m.vertices for m in meshes], torch.float32)
-    triangles = pack([m.triangles for m in meshes], torch.int32)
-    vo, to = [0], [0]
-    for m in meshes:
-        vo.append(vo[-1] + m.vertices.size(0))
-        to.append(to[-1] + m.triangles.size(0))
-    if vertices.size(0) == 0:                                      # (an empty tensor has no address: the library refuses NULL)
-        vertices = torch.empty((1, 3), dtype=torch.float32, device=dev)
-    if triangles.size(0) == 0:
-        triangles = torch.empty((1, 3), dtype=torch.int32, device=dev)
-    offsets = torch.tensor([vo, to], dtype=torch.int32).to(dev)
-    counts, measures, shell = _audit_packed(vertices, triangles, offsets[0], offsets[1], vo[-1], to[-1], bool(labels))
-    return [MeshAudit(counts[g], measures[g], shell[to[g]:to[g + 1]] if labels else None) for g in range(len(meshes))]
+    meshes = _listed(meshes, "audit_meshes")
+    p = _pack_meshes(meshes, _device_of(meshes))
+    counts, measures, shell = _audit_packed(*p.arguments(), bool(labels))
+    return [MeshAudit(counts[g], measures[g], shell[p.to[g]:p.to[g + 1]] if labels else None) for g in range(p.groups)]
 
 
 def weld_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offsets: torch.Tensor, triangle_offsets: torch.Tensor,
@@ -1082,69 +1051,45 @@ def weld_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offsets:
     """``pr_mesh_weld_t`` over prepared tensors (fp32 / int32, contiguous, one device); the capacities are the outputs' rows and the
     attribute width is the second dimension of ``attributes``."""
     s = _lib.MeshWeld()
-    s.groups = vertex_offsets.numel() - 1
-    s.total_vertices = int(total_vertices)
-    s.total_triangles = int(total_triangles)
-    s.flags = 0 if merge else _lib.WELD_COMPACT_ONLY
+    _set_mesh_header(s, vertex_offsets, total_vertices, total_triangles, 0 if merge else _lib.WELD_COMPACT_ONLY)
     s.attribute_width = 0 if attributes is None else attributes.size(1)
     s.max_vertices = 0 if out_vertices is None else out_vertices.size(0)
     s.max_triangles = 0 if out_triangles is None else out_triangles.size(0)
-    for name, t in (("vertices", vertices), ("normals", normals), ("attributes", attributes), ("triangles", triangles),
-                    ("vertex_offsets", vertex_offsets), ("triangle_offsets", triangle_offsets), ("out_vertices", out_vertices),
-                    ("out_normals", out_normals), ("out_attributes", out_attributes), ("out_triangles", out_triangles),
-                    ("vertex_map", vertex_map), ("triangle_map", triangle_map), ("counts", counts),
-                    ("out_vertex_offsets", out_vertex_offsets), ("out_triangle_offsets", out_triangle_offsets)):
-        setattr(s, name, None if t is None else t.data_ptr())
-    return s
+    return _set_pointers(s, vertices=vertices, normals=normals, attributes=attributes, triangles=triangles,
+                         vertex_offsets=vertex_offsets, triangle_offsets=triangle_offsets, out_vertices=out_vertices,
+                         out_normals=out_normals, out_attributes=out_attributes, out_triangles=out_triangles, vertex_map=vertex_map,
+                         triangle_map=triangle_map, counts=counts, out_vertex_offsets=out_vertex_offsets,
+                         out_triangle_offsets=out_triangle_offsets)
 
 
-def _weld_packed(vertices, normals, attributes, triangles, vertex_offsets, triangle_offsets, merge: bool, maps: bool):
-    """``pr_mesh_weld`` on packed meshes (device tensors; ``vertex_offsets`` / ``triangle_offsets`` are host lists), on
-    ``_simplify_packed``'s route: a counting call, one read-back of the two offset arrays, an exactly sized emitting call.  Returns
-    ``(meshes, vertex_maps, triangle_maps)``; the maps are None without ``maps``."""
-    lib = _lib.load()
-    dev = vertices.device
-    G, V, T = len(vertex_offsets) - 1, vertex_offsets[-1], triangle_offsets[-1]
-    A = 0 if attributes is None else attributes.size(1)
-    if A == 0:
-        attributes = None
-    if vertices.size(0) == 0:                                      # (an empty tensor has no address: the library refuses NULL)
-        vertices = torch.empty((1, 3), dtype=torch.float32, device=dev)
-        normals = None if normals is None else torch.empty((1, 3), dtype=torch.float32, device=dev)
-        attributes = None if attributes is None else torch.empty((1, A), dtype=torch.float32, device=dev)
-    if triangles.size(0) == 0:
-        triangles = torch.empty((1, 3), dtype=torch.int32, device=dev)
+def _weld_packed(p: _PackedMeshes, merge: bool, maps: bool):
+    """``pr_mesh_weld`` on packed meshes, on ``_simplify_packed``'s route: a counting call, one read-back of the two offset arrays,
+    an exactly sized emitting call.  Returns ``(meshes, vertex_maps, triangle_maps)``; the maps are None without ``maps``."""
+    dev, G, V, T = p.vertices.device, p.groups, p.V, p.T
+    inputs = dict(normals=p.normals, attributes=p.attributes, merge=merge)
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        offsets_in = torch.tensor([vertex_offsets, triangle_offsets], dtype=torch.int32).to(dev)
         offsets = torch.empty((2, G + 1), dtype=torch.int32, device=dev)
         counts = torch.empty((G, _lib.WELD_COUNTS), dtype=torch.int32, device=dev)
-        common = (vertices, triangles, offsets_in[0], offsets_in[1], V, T, counts, offsets[0], offsets[1])
-        count = weld_struct(*common, normals=normals, attributes=attributes, merge=merge)
-        size = C.c_size_t()
-        _lib.check(lib.pr_mesh_weld_workspace_size(C.byref(count), C.byref(size)), "pr_mesh_weld_workspace_size")
-        workspace = torch.empty(size.value, dtype=torch.uint8, device=dev)
-        _lib.check(lib.pr_mesh_weld(C.byref(count), workspace.data_ptr(), size.value, stream), "pr_mesh_weld")
+        common = (*p.arguments(), counts, offsets[0], offsets[1])
+        workspace, size = _call_with_workspace("pr_mesh_weld_workspace_size", "pr_mesh_weld", weld_struct(*common, **inputs), dev)
         out_vo, out_to = offsets.cpu().tolist()                             # (the host synchronisation)
         out_v = torch.empty((out_vo[G], 3), dtype=torch.float32, device=dev)
-        out_n = None if normals is None else torch.empty((out_vo[G], 3), dtype=torch.float32, device=dev)
-        out_a = None if attributes is None else torch.empty((out_vo[G], A), dtype=torch.float32, device=dev)
+        out_n = None if p.normals is None else torch.empty((out_vo[G], 3), dtype=torch.float32, device=dev)
+        out_a = None if p.attributes is None else torch.empty((out_vo[G], p.attributes.size(1)), dtype=torch.float32, device=dev)
         out_t = torch.empty((out_to[G], 3), dtype=torch.int32, device=dev)
         vmap = torch.full((V,), -1, dtype=torch.int32, device=dev) if maps else None
         tmap = torch.full((T,), -1, dtype=torch.int32, device=dev) if maps else None
         if out_vo[G] > 0 or (maps and V + T > 0):
             some = out_vo[G] > 0                                    # (a kept triangle refers to three output vertices)
-            emit = weld_struct(*common, normals=normals, attributes=attributes, out_vertices=out_v if some else None,
-                               out_normals=out_n if some else None, out_attributes=out_a if some else None,
-                               out_triangles=out_t if some else None, vertex_map=vmap if maps and V > 0 else None,
-                               triangle_map=tmap if maps and T > 0 else None, merge=merge)
-            _lib.check(lib.pr_mesh_weld(C.byref(emit), workspace.data_ptr(), size.value, stream), "pr_mesh_weld")
+            emit = weld_struct(*common, **inputs, out_vertices=out_v if some else None, out_normals=out_n if some else None,
+                               out_attributes=out_a if some else None, out_triangles=out_t if some else None,
+                               vertex_map=vmap if maps and V > 0 else None, triangle_map=tmap if maps and T > 0 else None)
+            _call("pr_mesh_weld", emit, workspace, size, dev)
     meshes = [Mesh(out_v[out_vo[g]:out_vo[g + 1]], out_t[out_to[g]:out_to[g + 1]], None if out_n is None else out_n[out_vo[g]:out_vo[g + 1]],
                    None if out_a is None else out_a[out_vo[g]:out_vo[g + 1]]) for g in range(G)]
     if not maps:
         return meshes, None, None
-    return (meshes, [vmap[vertex_offsets[g]:vertex_offsets[g + 1]] for g in range(G)],
-            [tmap[triangle_offsets[g]:triangle_offsets[g + 1]] for g in range(G)])
+    return meshes, [vmap[p.vo[g]:p.vo[g + 1]] for g in range(G)], [tmap[p.to[g]:p.to[g + 1]] for g in range(G)]
 
 
 def weld_meshes(meshes: Sequence[Mesh], *, merge: bool = True, maps: bool = False):
@@ -1155,43 +1100,18 @@ def weld_meshes(meshes: Sequence[Mesh], *, merge: bool = True, maps: bool = Fals
     orientation.  In the result identity by index IS identity by value: what an OBJ viewer or an adjacency builder needs, while
     ``RayGrid.contains`` and ``audit_meshes`` answer as on the input.  ``merge=False`` merges nothing and only drops the dead rows.
 
-    The meshes are packed as ``simplify_meshes`` packs them, counted, and - after reading the two offset arrays back, the ONE host
+    The meshes are packed (``_pack_meshes``), counted, and - after reading the two offset arrays back, the ONE host
     synchronisation - emitted into exactly sized tensors.  Returns one mesh per input; they have normals iff every input has them,
     and ``features`` iff every input has them with one common width - carried as fp32 attribute rows, so the result's features
     are fp32 whatever the input's dtype.  ``maps=True``: a triple ``(meshes, vertex_maps, triangle_maps)`` of lists, per mesh int32
     ``(V)`` - the output index of every input vertex's representative, -1 if it is not finite or unreferenced - and int32 ``(T)`` -
     the output index of every kept triangle, -1 for a dropped one.  There is no CPU fallback."""
-    meshes = list(meshes)
-    if not meshes:
-        raise ValueError("weld_meshes needs at least one mesh")
-    if not all(m.vertices.is_cuda and m.triangles.is_cuda for m in meshes):
-        raise RuntimeError(NO_CPU)
-    dev = meshes[0].vertices.device
-    for m in meshes:
-        if m.vertices.dim() != 2 or m.vertices.size(1) != 3 or m.triangles.dim() != 2 or m.triangles.size(1) != 3:
-            raise ValueError(f"a mesh has vertices (V, 3) and triangles (T, 3), got {list(m.vertices.shape)} / {list(m.triangles.shape)}")
-    with_normals = all(m.normals is not None for m in meshes)
-    with_features = all(m.features is not None and m.features.dim() == 2 for m in meshes) and \
-        len({m.features.size(1) for m in meshes}) == 1
-    if with_features and meshes[0].features.size(1) > _lib.WELD_MAX_ATTRIBUTE_WIDTH:
-        raise ValueError(f"features can be at most {_lib.WELD_MAX_ATTRIBUTE_WIDTH} wide, got {meshes[0].features.size(1)}")
-    pack = lambda parts, dtype, width=3: torch.cat([p.detach().to(device=dev, dtype=dtype).reshape(-1, width) for p in parts]).contiguous()
-    vertices = pack([m.vertices for m in meshes], torch.float32)
-    triangles = pack([m.triangles for m in meshes], torch.int32)
-    normals = pack([m.normals for m in meshes], torch.float32) if with_normals else None
-    if normals is not None and normals.size(0) != vertices.size(0):
-        raise ValueError("normals must have one row per vertex")
-    features = None
-    if with_features:
-        if any(m.features.size(0) != m.vertices.size(0) for m in meshes):
-            raise ValueError("features must have one row per vertex")
-        width = meshes[0].features.size(1)
-        features = pack([m.features for m in meshes], torch.float32, width) if width else None
-    vertex_offsets, triangle_offsets = [0], [0]
-    for m in meshes:
-        vertex_offsets.append(vertex_offsets[-1] + m.vertices.size(0))
-        triangle_offsets.append(triangle_offsets[-1] + m.triangles.size(0))
-    out, vmaps, tmaps = _weld_packed(vertices, normals, features, triangles, vertex_offsets, triangle_offsets, bool(merge), bool(maps))
+    meshes = _listed(meshes, "weld_meshes")
+    dev = _device_of(meshes)
+    _mesh_shapes(meshes)                                            # (refused before the features' width, which the packer needs)
+    width = _feature_width(meshes, _lib.WELD_MAX_ATTRIBUTE_WIDTH)   # (0: the rows are still counted, nothing is carried)
+    p = _pack_meshes(meshes, dev, normals=all(m.normals is not None for m in meshes), features=width)
+    out, vmaps, tmaps = _weld_packed(p, bool(merge), bool(maps))
     return (out, vmaps, tmaps) if maps else out
 
 
@@ -1203,37 +1123,23 @@ def smooth_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offset
                   vertex_state: Optional[torch.Tensor] = None) -> _lib.MeshSmooth:
     """``pr_mesh_smooth_t`` over prepared tensors (fp32 / int32 / uint8, contiguous, one device)."""
     s = _lib.MeshSmooth()
-    s.groups = vertex_offsets.numel() - 1
-    s.total_vertices = int(total_vertices)
-    s.total_triangles = int(total_triangles)
-    s.flags = _lib.SMOOTH_PIN_BORDER if pin_border else 0
+    _set_mesh_header(s, vertex_offsets, total_vertices, total_triangles, _lib.SMOOTH_PIN_BORDER if pin_border else 0)
     s.steps = int(steps)
     s.max_degree = int(max_degree)
     s.lambda_ = float(lam)
     s.mu = float(mu)
-    for name, t in (("vertices", vertices), ("triangles", triangles), ("vertex_offsets", vertex_offsets),
-                    ("triangle_offsets", triangle_offsets), ("pinned", pinned), ("out_vertices", out_vertices),
-                    ("out_normals", out_normals), ("incidence_offsets", incidence_offsets), ("incidence", incidence),
-                    ("vertex_state", vertex_state), ("counts", counts)):
-        setattr(s, name, None if t is None else t.data_ptr())
-    return s
+    return _set_pointers(s, vertices=vertices, triangles=triangles, vertex_offsets=vertex_offsets, triangle_offsets=triangle_offsets,
+                         pinned=pinned, out_vertices=out_vertices, out_normals=out_normals, incidence_offsets=incidence_offsets,
+                         incidence=incidence, vertex_state=vertex_state, counts=counts)
 
 
-def _smooth_packed(vertices, triangles, vertex_offsets, triangle_offsets, *, steps, lam, mu, max_degree, pin_border, pinned=None,
-                   normals=True, incidence=False, state=False):
-    """``pr_mesh_smooth`` on packed meshes (device tensors; the two offset arrays are host lists): ONE call into exactly sized
-    tensors - the sizes do not change - and no host synchronisation.  Returns a dict of the packed outputs."""
-    lib = _lib.load()
-    dev = vertices.device
-    G, V, T = len(vertex_offsets) - 1, vertex_offsets[-1], triangle_offsets[-1]
-    row = lambda n: max(n, 1)                                       # (an empty tensor has no address: the library refuses NULL)
-    if vertices.size(0) == 0:
-        vertices = torch.empty((1, 3), dtype=torch.float32, device=dev)
-    if triangles.size(0) == 0:
-        triangles = torch.empty((1, 3), dtype=torch.int32, device=dev)
+def _smooth_packed(p: _PackedMeshes, *, steps, lam, mu, max_degree, pin_border, pinned=None, normals=True, incidence=False, state=False):
+    """``pr_mesh_smooth`` on packed meshes: ONE call into exactly sized tensors - the sizes do not change - and no host
+    synchronisation.  Returns a dict of the packed outputs."""
+    dev, G, V, T = p.vertices.device, p.groups, p.V, p.T
+    row = lambda n: max(n, 1)            # (outputs the library wants an address for: one row at least, sliced back to V below)
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        offsets = torch.tensor([vertex_offsets, triangle_offsets], dtype=torch.int32).to(dev)
+        mesh = p.arguments()
         out = {"vertices": torch.empty((row(V), 3), dtype=torch.float32, device=dev),
                "counts": torch.empty((G, _lib.SMOOTH_COUNTS), dtype=torch.int32, device=dev)}
         if normals:
@@ -1244,14 +1150,11 @@ def _smooth_packed(vertices, triangles, vertex_offsets, triangle_offsets, *, ste
         if state:
             out["state"] = torch.empty(row(V), dtype=torch.int32, device=dev)
         if pinned is not None and pinned.numel() == 0:
-            pinned = None
-        s = smooth_struct(vertices, triangles, offsets[0], offsets[1], V, T, out["vertices"], out["counts"], steps=steps, lam=lam, mu=mu,
-                          max_degree=max_degree, pin_border=pin_border, pinned=pinned, out_normals=out.get("normals"),
+            pinned = None                                             # (an optional input: NULL, not a placeholder)
+        s = smooth_struct(*mesh, out["vertices"], out["counts"], steps=steps, lam=lam, mu=mu, max_degree=max_degree,
+                          pin_border=pin_border, pinned=pinned, out_normals=out.get("normals"),
                           incidence_offsets=out.get("incidence_offsets"), incidence=out.get("incidence"), vertex_state=out.get("state"))
-        size = C.c_size_t()
-        _lib.check(lib.pr_mesh_smooth_workspace_size(C.byref(s), C.byref(size)), "pr_mesh_smooth_workspace_size")
-        workspace = torch.empty(size.value, dtype=torch.uint8, device=dev)
-        _lib.check(lib.pr_mesh_smooth(C.byref(s), workspace.data_ptr(), size.value, stream), "pr_mesh_smooth")
+        _call_with_workspace("pr_mesh_smooth_workspace_size", "pr_mesh_smooth", s, dev)
     for key in ("vertices", "normals", "state"):
         if key in out:
             out[key] = out[key][:V]
@@ -1293,25 +1196,12 @@ def smooth_meshes(meshes: Sequence[Mesh], *, iterations: int = 10, lam: float = 
     are carried row for row (vertex counts do not change after the weld).  Returns one mesh per input; ``report=True``: a triple
     ``(meshes, counts, states)`` of lists with the ``(8)`` counts and the ``(V)`` state words of every mesh (header), still on the
     device.  There is no CPU fallback."""
-    meshes = list(meshes)
-    if not meshes:
-        raise ValueError("smooth_meshes needs at least one mesh")
-    if not all(m.vertices.is_cuda and m.triangles.is_cuda for m in meshes):
-        raise RuntimeError(NO_CPU)
+    meshes = _listed(meshes, "smooth_meshes")
+    dev = _device_of(meshes)
     steps, lam, mu, max_degree = _smooth_arguments(iterations, lam, mu, max_degree)
-    for m in meshes:
-        if m.vertices.dim() != 2 or m.vertices.size(1) != 3 or m.triangles.dim() != 2 or m.triangles.size(1) != 3:
-            raise ValueError(f"a mesh has vertices (V, 3) and triangles (T, 3), got {list(m.vertices.shape)} / {list(m.triangles.shape)}")
     if weld:
-        meshes = weld_meshes(meshes)
-    dev = meshes[0].vertices.device
-    pack = lambda parts, dtype: torch.cat([p.detach().to(device=dev, dtype=dtype).reshape(-1, 3) for p in parts]).contiguous()
-    vertices = pack([m.vertices for m in meshes], torch.float32)
-    triangles = pack([m.triangles for m in meshes], torch.int32)
-    vertex_offsets, triangle_offsets = [0], [0]
-    for m in meshes:
-        vertex_offsets.append(vertex_offsets[-1] + m.vertices.size(0))
-        triangle_offsets.append(triangle_offsets[-1] + m.triangles.size(0))
+        meshes = weld_meshes(meshes)                                  # (its first refusal is the packer's: the shapes)
+    packed = _pack_meshes(meshes, dev)
     mask = None
     if pinned is not None:
         pinned = list(pinned)
@@ -1327,16 +1217,15 @@ def smooth_meshes(meshes: Sequence[Mesh], *, iterations: int = 10, lam: float = 
                                  f"got {p.numel()}")
             parts.append((p.detach().to(dev).reshape(-1) != 0).to(torch.uint8))
         mask = torch.cat(parts).contiguous()
-    out = _smooth_packed(vertices, triangles, vertex_offsets, triangle_offsets, steps=steps, lam=lam, mu=mu, max_degree=max_degree,
-                         pin_border=bool(pin_border), pinned=mask, normals=bool(normals), state=bool(report))
+    out = _smooth_packed(packed, steps=steps, lam=lam, mu=mu, max_degree=max_degree, pin_border=bool(pin_border), pinned=mask,
+                         normals=bool(normals), state=bool(report))
     result = []
     for g, m in enumerate(meshes):
-        v0, v1 = vertex_offsets[g], vertex_offsets[g + 1]
+        v0, v1 = packed.vo[g], packed.vo[g + 1]
         result.append(Mesh(out["vertices"][v0:v1], m.triangles, out["normals"][v0:v1] if normals else m.normals, m.features))
     if not report:
         return result
-    return (result, [out["counts"][g] for g in range(len(meshes))],
-            [out["state"][vertex_offsets[g]:vertex_offsets[g + 1]] for g in range(len(meshes))])
+    return result, [out["counts"][g] for g in range(packed.groups)], [out["state"][packed.vo[g]:packed.vo[g + 1]] for g in range(packed.groups)]
 
 
 def sample_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offsets: torch.Tensor, triangle_offsets: torch.Tensor,
@@ -1348,20 +1237,14 @@ def sample_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offset
     """``pr_mesh_sample_t`` over prepared tensors (fp32 / int32 / fp64, contiguous, one device); the attribute width is the second
     dimension of ``attributes``."""
     s = _lib.MeshSample()
-    s.groups = vertex_offsets.numel() - 1
-    s.total_vertices = int(total_vertices)
-    s.total_triangles = int(total_triangles)
-    s.flags = _lib.SAMPLE_FACE_NORMALS if face_normals else 0
+    _set_mesh_header(s, vertex_offsets, total_vertices, total_triangles, _lib.SAMPLE_FACE_NORMALS if face_normals else 0)
     s.samples = int(samples)
     s.attribute_width = 0 if attributes is None else attributes.size(1)
     s.seed = int(seed)
     s.first_sample = int(first)
-    for name, t in (("vertices", vertices), ("triangles", triangles), ("vertex_offsets", vertex_offsets),
-                    ("triangle_offsets", triangle_offsets), ("normals", normals), ("attributes", attributes), ("points", points),
-                    ("triangle", triangle), ("barycentric", barycentric), ("out_normals", out_normals),
-                    ("out_attributes", out_attributes), ("counts", counts), ("measures", measures)):
-        setattr(s, name, None if t is None else t.data_ptr())
-    return s
+    return _set_pointers(s, vertices=vertices, triangles=triangles, vertex_offsets=vertex_offsets, triangle_offsets=triangle_offsets,
+                         normals=normals, attributes=attributes, points=points, triangle=triangle, barycentric=barycentric,
+                         out_normals=out_normals, out_attributes=out_attributes, counts=counts, measures=measures)
 
 
 @dataclass
@@ -1397,10 +1280,9 @@ def _sample_packed(vertices, triangles, vertex_offsets, triangle_offsets, V: int
                    face: bool = False, normals=None, attributes=None):
     """One ``pr_mesh_sample`` call on packed device tensors (the offsets too), on the current stream, into exactly sized tensors:
     a dict of the ``(G, n, ...)`` outputs.  The workspace is sized on the host; nothing is read back."""
-    lib = _lib.load()
     dev = vertices.device
     G = vertex_offsets.numel() - 1
-    rows = max(G * n, 1)                                            # (an empty tensor has no address: the library refuses NULL)
+    rows = max(G * n, 1)                                            # (outputs the library wants an address for; sliced back below)
     with torch.cuda.device(dev):
         new = lambda width, dtype=torch.float32: torch.empty((rows, width), dtype=dtype, device=dev)
         out = {"points": new(3), "triangle": new(1, torch.int32), "barycentric": new(2),
@@ -1414,11 +1296,7 @@ def _sample_packed(vertices, triangles, vertex_offsets, triangle_offsets, V: int
                           out["measures"], first=first, face_normals=face, normals=None if face else normals, attributes=attributes,
                           triangle=out["triangle"], barycentric=out["barycentric"], out_normals=out.get("normals"),
                           out_attributes=out.get("features"))
-        size = C.c_size_t()
-        _lib.check(lib.pr_mesh_sample_workspace_size(C.byref(s), C.byref(size)), "pr_mesh_sample_workspace_size")
-        workspace = torch.empty(size.value, dtype=torch.uint8, device=dev)
-        _lib.check(lib.pr_mesh_sample(C.byref(s), workspace.data_ptr(), size.value, torch.cuda.current_stream(dev).cuda_stream),
-                   "pr_mesh_sample")
+        _call_with_workspace("pr_mesh_sample_workspace_size", "pr_mesh_sample", s, dev)
     for key in ("points", "triangle", "barycentric", "normals", "features"):
         if key in out:
             out[key] = out[key][:G * n].reshape((G, n) + ((out[key].size(1),) if key != "triangle" else ()))
@@ -1447,53 +1325,20 @@ def sample_meshes(meshes: Sequence[Mesh], n: int, *, seed: int, first: int = 0, 
     ``features=True`` carries ``Mesh.features`` to the points where every mesh has them with one common width - as fp32 rows,
     whatever their dtype, as ``weld_meshes`` carries them.
 
-    The meshes are packed as ``simplify_meshes`` packs them; the workspace is sized on the host; one call on the current stream and
+    The meshes are packed (``_pack_meshes``); the workspace is sized on the host; one call on the current stream and
     NO host synchronisation.  There is no CPU fallback."""
-    meshes = list(meshes)
-    if not meshes:
-        raise ValueError("sample_meshes needs at least one mesh")
+    meshes = _listed(meshes, "sample_meshes")
     if normals not in ("vertex", "face", None):
         raise ValueError(f"normals must be 'vertex', 'face' or None, got {normals!r}")
     n, seed, first = _sample_arguments(n, seed, first, len(meshes))
-    if not all(m.vertices.is_cuda and m.triangles.is_cuda for m in meshes):
-        raise RuntimeError(NO_CPU)
-    dev = meshes[0].vertices.device
-    for m in meshes:
-        if m.vertices.dim() != 2 or m.vertices.size(1) != 3 or m.triangles.dim() != 2 or m.triangles.size(1) != 3:
-            raise ValueError(f"a mesh has vertices (V, 3) and triangles (T, 3), got {list(m.vertices.shape)} / {list(m.triangles.shape)}")
+    dev = _device_of(meshes)
+    _mesh_shapes(meshes)                                            # (refused before the two below, which the packer needs)
     if normals == "vertex" and not all(m.normals is not None for m in meshes):
         raise ValueError("normals='vertex' needs meshes with normals (Mesh.vertex_normals() computes them); 'face' needs none")
-    with_features = bool(features) and all(m.features is not None and m.features.dim() == 2 for m in meshes) and \
-        len({m.features.size(1) for m in meshes}) == 1 and meshes[0].features.size(1) > 0
-    if with_features and meshes[0].features.size(1) > _lib.SAMPLE_MAX_ATTRIBUTE_WIDTH:
-        raise ValueError(f"features can be at most {_lib.SAMPLE_MAX_ATTRIBUTE_WIDTH} wide, got {meshes[0].features.size(1)}")
-    pack = lambda parts, dtype, width=3: torch.cat([p.detach().to(device=dev, dtype=dtype).reshape(-1, width) for p in parts]).contiguous()
-    vertices = pack([m.vertices for m in meshes], torch.float32)
-    triangles = pack([m.triangles for m in meshes], torch.int32)
-    rows = None
-    if normals == "vertex":
-        rows = pack([m.normals for m in meshes], torch.float32)
-        if rows.size(0) != vertices.size(0):
-            raise ValueError("normals must have one row per vertex")
-    attributes = None
-    if with_features:
-        if any(m.features.size(0) != m.vertices.size(0) for m in meshes):
-            raise ValueError("features must have one row per vertex")
-        attributes = pack([m.features for m in meshes], torch.float32, meshes[0].features.size(1))
-    vo, to = [0], [0]
-    for m in meshes:
-        vo.append(vo[-1] + m.vertices.size(0))
-        to.append(to[-1] + m.triangles.size(0))
-    if vertices.size(0) == 0:                                      # (an empty tensor has no address: the library refuses NULL)
-        vertices = torch.empty((1, 3), dtype=torch.float32, device=dev)
-        rows = None if rows is None else torch.empty((1, 3), dtype=torch.float32, device=dev)
-        attributes = None if attributes is None else torch.empty((1, attributes.size(1)), dtype=torch.float32, device=dev)
-    if triangles.size(0) == 0:
-        triangles = torch.empty((1, 3), dtype=torch.int32, device=dev)
-    offsets = torch.tensor([vo, to], dtype=torch.int32).to(dev)
-    out = _sample_packed(vertices, triangles, offsets[0], offsets[1], vo[-1], to[-1], n, seed, first, face=normals == "face",
-                         normals=rows, attributes=attributes)
-    return _surface_samples(out, len(meshes))
+    width = _feature_width(meshes, _lib.SAMPLE_MAX_ATTRIBUTE_WIDTH) if features else None
+    p = _pack_meshes(meshes, dev, normals=normals == "vertex", features=width or None)     # (0: as without features)
+    out = _sample_packed(*p.arguments(), n, seed, first, face=normals == "face", normals=p.normals, attributes=p.attributes)
+    return _surface_samples(out, p.groups)
 
 
 DEVIATION_FIELDS = ("samples", "misses", "mean", "rms", "max", "p99", "normal_consistency")
@@ -1625,14 +1470,8 @@ def intersect_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_off
     ``references``, ``max_pairs`` the rows of ``pairs``.  The query totals default to the targets' with ``self_`` and to the rows of the
     query tensors otherwise."""
     s = _lib.MeshIntersect()
-    s.groups = vertex_offsets.numel() - 1
-    s.total_vertices = int(total_vertices)
-    s.total_triangles = int(total_triangles)
-    s.flags = _lib.INTERSECT_SELF if self_ else 0
-    for a in range(3):
-        s.origin[a] = float(origin[a])
-        s.cell[a] = float(cell[a])
-        s.cells[a] = int(cells[a])
+    _set_mesh_header(s, vertex_offsets, total_vertices, total_triangles, _lib.INTERSECT_SELF if self_ else 0)
+    _set_grid(s, origin, cell, cells)
     s.max_references = 0 if references is None else references.size(0)
     if q_total_vertices is None:
         q_total_vertices = total_vertices if self_ else (0 if q_vertices is None else q_vertices.size(0))
@@ -1641,13 +1480,10 @@ def intersect_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_off
     s.q_total_vertices = int(q_total_vertices)
     s.q_total_triangles = int(q_total_triangles)
     s.max_pairs = 0 if pairs is None else pairs.size(0)
-    for name, x in (("vertices", vertices), ("triangles", triangles), ("vertex_offsets", vertex_offsets),
-                    ("triangle_offsets", triangle_offsets), ("cell_offsets", cell_offsets), ("references", references),
-                    ("q_vertices", q_vertices), ("q_triangles", q_triangles), ("q_vertex_offsets", q_vertex_offsets),
-                    ("q_triangle_offsets", q_triangle_offsets), ("transform", transform), ("count", count), ("first", first),
-                    ("pair_offsets", pair_offsets), ("pairs", pairs), ("segments", segments)):
-        setattr(s, name, None if x is None else x.data_ptr())
-    return s
+    return _set_pointers(s, vertices=vertices, triangles=triangles, vertex_offsets=vertex_offsets, triangle_offsets=triangle_offsets,
+                         cell_offsets=cell_offsets, references=references, q_vertices=q_vertices, q_triangles=q_triangles,
+                         q_vertex_offsets=q_vertex_offsets, q_triangle_offsets=q_triangle_offsets, transform=transform, count=count,
+                         first=first, pair_offsets=pair_offsets, pairs=pairs, segments=segments)
 
 
 @dataclass
@@ -1832,15 +1668,10 @@ def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: fl
         if axes[a].dim() != 1 or axes[a].numel() != sigma.size(1 + a):
             raise ValueError(f"axes[{a}] must hold {sigma.size(1 + a)} coordinates, got {list(axes[a].shape)}")
     G = sigma.size(0)
-    lib = _lib.load()
     with torch.cuda.device(dev):
-        stream = torch.cuda.current_stream(dev).cuda_stream
         offsets = torch.empty((2, G + 1), dtype=torch.int32, device=dev)
-        count = surface_struct(sigma, axes, level, offsets[0], offsets[1])
-        size = C.c_size_t()
-        _lib.check(lib.pr_surface_workspace_size(C.byref(count), C.byref(size)), "pr_surface_workspace_size")
-        workspace = torch.empty(size.value, dtype=torch.uint8, device=dev)
-        _lib.check(lib.pr_extract_surface(C.byref(count), workspace.data_ptr(), size.value, stream), "pr_extract_surface")
+        workspace, size = _call_with_workspace("pr_surface_workspace_size", "pr_extract_surface",
+                                               surface_struct(sigma, axes, level, offsets[0], offsets[1]), dev)
         vertex_offsets, triangle_offsets = offsets.cpu().tolist()           # (the host synchronisation)
         V, T = vertex_offsets[G], triangle_offsets[G]
         vertices = torch.empty((V, 3), dtype=torch.float32, device=dev)
@@ -1848,13 +1679,13 @@ def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: fl
         triangles = torch.empty((T, 3), dtype=torch.int32, device=dev)
         if V > 0:
             emit = surface_struct(sigma, axes, level, offsets[0], offsets[1], vertices, vertex_normals, triangles)
-            _lib.check(lib.pr_extract_surface(C.byref(emit), workspace.data_ptr(), size.value, stream), "pr_extract_surface")
-    if simplify:
+            _call("pr_extract_surface", emit, workspace, size, dev)
+    if simplify:                                                   # (the mesher's output is packed already: no Mesh objects in between)
         grid = _cluster_grid(*lattice_cluster_grid(axes, simplify))
-        meshes = _simplify_packed(vertices, vertex_normals, triangles, vertex_offsets, triangle_offsets, *grid, bool(keep_duplicates))
+        meshes = _simplify_packed(_packed(vertices, triangles, vertex_offsets, triangle_offsets, vertex_normals), *grid, bool(keep_duplicates))
         return weld_meshes(meshes) if weld else meshes
     if weld:
-        return _weld_packed(vertices, vertex_normals, None, triangles, vertex_offsets, triangle_offsets, True, False)[0]
+        return _weld_packed(_packed(vertices, triangles, vertex_offsets, triangle_offsets, vertex_normals), True, False)[0]
     meshes = []
     for g in range(G):
         v0, v1, t0, t1 = vertex_offsets[g], vertex_offsets[g + 1], triangle_offsets[g], triangle_offsets[g + 1]
