@@ -1379,6 +1379,94 @@ int pr_mesh_intersect_workspace_size(const pr_mesh_intersect_t* s, size_t* bytes
 int pr_mesh_intersect(const pr_mesh_intersect_t* s, void* workspace, size_t workspace_bytes, void* stream);
 
 /*
+ * Placement of the vertices of simplified meshes by quadric error (Lindstrom's placement for Rossignac-Borrel clustering):
+ * pr_mesh_place moves every vertex of a MERGED mesh - what pr_simplify_mesh made, one vertex per cluster at the mean of its members -
+ * to the point that minimises the area-weighted sum of squared distances to the planes of the INPUT triangles that touch the cluster,
+ * with a Tikhonov pull toward the stored position.  Convex edges and corners, which the mean rounds off, are kept.  The triangle
+ * lists are not touched.
+ *   Input: G input meshes packed as pr_simplify_mesh reads them - vertices (V, 3) fp32, triangles (T, 3) int32 LOCAL to their group,
+ *     vertex_offsets (G + 1), triangle_offsets (G + 1), all on the device; total_vertices / total_triangles are V and T as host values.
+ *     vertex_map (V) int32 as pr_simplify_mesh writes it: the merged index of every input vertex, local to its group.  The merged
+ *     mesh: merged_vertices (VO, 3) fp32, merged_vertex_offsets (G + 1), and optionally - both or neither - merged_triangles (TO, 3)
+ *     int32 local to their group with merged_triangle_offsets (G + 1); total_merged_vertices / total_merged_triangles are VO and TO as
+ *     host values (TO is not read without merged_triangles).  Each of the four offset arrays is clamped on its own as pr_simplify_mesh
+ *     clamps: an entry that leaves [0, total] or decreases is clamped, never followed.  Group g then has V_g, T_g, VO_g, TO_g rows.
+ *   Host values: scale h (finite, > 0) - the unit of length of the quadric, e.g. the largest cell size -, max_move[3] (finite, >= 0),
+ *     regularisation (finite, > 0), flags (0).  h, max_move and regularisation enter the arithmetic as (double) of the fp32 values.
+ *   Rule: fp64 without contraction, every operation rounded on its own, sqrt and division correctly rounded.
+ *     An input triangle of group g is VALID if its three indices are in [0, V_g) and its nine coordinates are finite; the others are
+ *     counted and contribute nothing.  A valid triangle (a, b, c) as stored CONTRIBUTES once to every distinct cluster j among
+ *     vertex_map[a], vertex_map[b], vertex_map[c]; a corner whose map entry lies outside [0, VO_g) contributes nothing.  For such a
+ *     cluster, with m = merged vertex j of the group as stored (fp32 -> fp64), per component:
+ *       a' = (a - m) / h, b' = (b - m) / h, c' = (c - m) / h;   e1 = b' - a', e2 = c' - a';
+ *       n0 = e1[1] e2[2] - e1[2] e2[1], n1 = e1[2] e2[0] - e1[0] e2[2], n2 = e1[0] e2[1] - e1[1] e2[0]  (a difference of two products);
+ *       L = sqrt((n0 n0 + n1 n1) + n2 n2);   d = -((n0 a'[0] + n1 a'[1]) + n2 a'[2]).
+ *     A contribution with L not finite or not > 0 is SKIPPED and counted.  Otherwise its nine coefficients are, each a product divided
+ *     by L,  q0 = n0 n0 / L, q1 = n0 n1 / L, q2 = n0 n2 / L, q3 = n1 n1 / L, q4 = n1 n2 / L, q5 = n2 n2 / L, q6 = d n0 / L,
+ *     q7 = d n1 / L, q8 = d n2 / L: the plane quadric weighted by twice the area, in units of h around m.  If any |q_i| > 2^16 or is
+ *     not finite the contribution is skipped and counted.  Otherwise llrint(q_i 2^36) - the product is exact - is added to the
+ *     cluster's nine int64 sums, modulo 2^64, and 1 to its int32 contribution count.  INTEGER SUMS: the order of arrival cannot show.
+ *   Per merged vertex with at least one contribution: S_i = (double)(int64 sum i) 2^-36;
+ *       lambda = (regularisation ((S0 + S3) + S5)) / 3;   m00 = S0 + lambda, m01 = S1, m02 = S2, m11 = S3 + lambda, m12 = S4,
+ *       m22 = S5 + lambda;   r = (-S6, -S7, -S8);
+ *       c00 = m11 m22 - m12 m12, c01 = m02 m12 - m01 m22, c02 = m01 m12 - m02 m11, c11 = m00 m22 - m02 m02,
+ *       c12 = m01 m02 - m00 m12, c22 = m00 m11 - m01 m01;   det = (m00 c00 + m01 c01) + m02 c02;
+ *       y0 = ((c00 r0 + c01 r1) + c02 r2) / det, y1 = ((c01 r0 + c11 r1) + c12 r2) / det, y2 = ((c02 r0 + c12 r1) + c22 r2) / det;
+ *       t_k = h y_k.
+ *     A planar cluster keeps its tangential position up to the regularisation, an edge cluster slides only along its edge.  The vertex
+ *     KEEPS its three stored words, bit for bit, if it has no contribution, if det is not finite or not > 0, if some y_k is not
+ *     finite, or if some |t_k| > max_move[k].  Otherwise it MOVES: out_k = (float)(m_k + t_k).
+ *   With merged triangles: one whose three indices are in [0, VO_g) is TURNED iff (N0 N0' + N1 N1') + N2 N2' < 0, where
+ *     N = (b - a) x (c - a), components as above, in fp64 on the stored merged vertices and N' the same on out_vertices.  Turned
+ *     triangles are reported, never repaired.
+ *   out_vertices (VO, 3): every row of a clamped group is written; the rows that no clamped group owns are not touched.  It must not
+ *     be `vertices` or `merged_vertices`.
+ *   counts (G, 4) int32, always and fully written: vertices moved, vertices kept, contributions skipped plus invalid triangles,
+ *     triangles turned (0 without merged triangles).
+ *   Memory safety: every index read from a mesh or from the map is range-checked where it is read.  Hostile input may cost the
+ *     correctness of the hostile group, never memory safety, and never another group's rows.
+ * Workspace bytes = the sum of these regions, each rounded up to 256 bytes: 8 x 4 (G + 1) (per group and per kind of row - input
+ *   vertices, input triangles, merged vertices, merged triangles -: first row, first block) + 72 VO (nine int64 sums per merged
+ *   vertex) + 4 VO (contribution counts).
+ * Four kernel launches on `stream` (three without merged triangles), no memset, no memcpy, no allocation, no synchronisation:
+ * capturable into a HIP graph.  Integer atomics only.
+ * Additive entry points: PR_ABI_VERSION is unchanged.  sizeof(pr_mesh_place_t) = 136.
+ * Refused (PR_ERR_INVALID, before any device work; by pr_mesh_place_workspace_size too, except the workspace itself): NULL vertices,
+ * triangles, vertex_map, merged_vertices, out_vertices, counts or one of the three required offset arrays, exactly one of
+ * merged_triangles / merged_triangle_offsets, groups < 1, a negative total, a scale or regularisation that is not finite or not > 0,
+ * a max_move entry that is not finite or negative, flags != 0, out_vertices == vertices or == merged_vertices, V + 256 G,
+ * T + 256 G, VO + 256 G or TO + 256 G at or above 2^31 (the block counts are int32), a workspace of 2^62 bytes or more; by the call
+ * only, and last: a NULL, misaligned or too small workspace.
+ */
+typedef struct pr_mesh_place_t {
+    int32_t groups;                       /* G >= 1 */
+    int32_t total_vertices;               /* V, as a host value, >= 0 */
+    int32_t total_triangles;              /* T, as a host value, >= 0 */
+    uint32_t flags;                       /* 0 */
+    int32_t total_merged_vertices;        /* VO, as a host value, >= 0 */
+    int32_t total_merged_triangles;       /* TO, as a host value, >= 0; not read without merged_triangles */
+    float scale;                          /* h: finite, > 0 */
+    float regularisation;                 /* finite, > 0 */
+    float max_move[3];                    /* finite, >= 0 */
+    uint32_t reserved_;
+    const float* vertices;                /* (V, 3) */
+    const int32_t* triangles;             /* (T, 3), indices local to the group */
+    const int32_t* vertex_offsets;        /* (G + 1) */
+    const int32_t* triangle_offsets;      /* (G + 1) */
+    const int32_t* vertex_map;            /* (V): merged index of every input vertex, local to the group */
+    const float* merged_vertices;         /* (VO, 3) */
+    const int32_t* merged_vertex_offsets; /* (G + 1) */
+    const int32_t* merged_triangles;      /* (TO, 3) or NULL; with merged_triangle_offsets */
+    const int32_t* merged_triangle_offsets; /* (G + 1) or NULL; with merged_triangles */
+    float* out_vertices;                  /* (VO, 3); not an input */
+    int32_t* counts;                      /* (G, 4), always written */
+} pr_mesh_place_t;
+/* Host computation, no device work; refuses everything above that does not concern the workspace. */
+int pr_mesh_place_workspace_size(const pr_mesh_place_t* s, size_t* bytes);
+/* `workspace`: 256-byte aligned, pr_mesh_place_workspace_size bytes. */
+int pr_mesh_place(const pr_mesh_place_t* s, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
  * Backward pass of pr_render_forward (what torch.autograd does for the reference's op graph when
  * training/trainer_backpropagated_autoencoder.py:349 calls total_loss.backward()).  The forward call must
  * have run with PR_FLAG_SAVE_FOR_BACKWARD (with or without PR_FLAG_TRAIN_BN) on the same `call`, `objects` and

@@ -341,6 +341,20 @@ class MeshIntersect(C.Structure):
 INTERSECT_SELF = 1               # PR_INTERSECT_SELF
 
 
+class MeshPlace(C.Structure):
+    """pr_mesh_place_t (include/playrender.h)."""
+    _fields_ = [("groups", C.c_int32), ("total_vertices", C.c_int32), ("total_triangles", C.c_int32), ("flags", C.c_uint32),
+                ("total_merged_vertices", C.c_int32), ("total_merged_triangles", C.c_int32), ("scale", C.c_float),
+                ("regularisation", C.c_float), ("max_move", C.c_float * 3), ("reserved_", C.c_uint32),
+                ("vertices", C.c_void_p), ("triangles", C.c_void_p), ("vertex_offsets", C.c_void_p), ("triangle_offsets", C.c_void_p),
+                ("vertex_map", C.c_void_p), ("merged_vertices", C.c_void_p), ("merged_vertex_offsets", C.c_void_p),
+                ("merged_triangles", C.c_void_p), ("merged_triangle_offsets", C.c_void_p), ("out_vertices", C.c_void_p),
+                ("counts", C.c_void_p)]
+
+
+PLACE_COUNTS = 4                 # columns of pr_mesh_place_t.counts: moved, kept, skipped + invalid, turned
+
+
 # every exported symbol of include/playrender.h : (restype, argtypes)
 class SceneSetup(C.Structure):
     """pr_scene_setup_t (include/playrender.h)."""
@@ -399,6 +413,8 @@ SYMBOLS = {
     "pr_mesh_sample": (C.c_int, [C.POINTER(MeshSample), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_mesh_intersect_workspace_size": (C.c_int, [C.POINTER(MeshIntersect), C.POINTER(C.c_size_t)]),
     "pr_mesh_intersect": (C.c_int, [C.POINTER(MeshIntersect), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "pr_mesh_place_workspace_size": (C.c_int, [C.POINTER(MeshPlace), C.POINTER(C.c_size_t)]),
+    "pr_mesh_place": (C.c_int, [C.POINTER(MeshPlace), C.c_void_p, C.c_size_t, C.c_void_p]),
     "pr_backward_workspace_size": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(C.c_size_t)]),
     "pr_render_backward": (C.c_int, [C.POINTER(Call), C.POINTER(Object), C.POINTER(OutputGrads), C.POINTER(OutputGrads),
                                      C.POINTER(InputGrads), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -950,7 +950,7 @@ class ObjectComposer(Tracked, nn.Module):
     def extract_mesh(self, object_idx: int, resolution, style: torch.Tensor, deformation: torch.Tensor, *, level: float,
                      fine: bool = False, canonical_pose: bool = False, normals: bool = True, features: bool = False,
                      keep_largest: int = 0, min_points: int = 0, close_border: bool = False, stride: int = 0, guard: int = 1,
-                     simplify: int = 0, keep_duplicates: bool = False, weld: bool = False, smooth: int = 0):
+                     simplify: int = 0, keep_duplicates: bool = False, weld: bool = False, smooth: int = 0, placement: str = "mean"):
         """Triangle meshes of the density field of object ``object_idx`` in its OBJECT frame: ``density_grid`` at the composer's
         ``precision``, then ``surface.extract_surface`` (marching tetrahedra on the device) on the lattice of voxel centres.  One
         ``surface.Mesh`` per row of ``style (G, S)`` / ``deformation (G, D)``.
@@ -972,6 +972,10 @@ class ObjectComposer(Tracked, nn.Module):
         queried at the simplified vertices, which are means of points of the lattice hull and so lie inside the box.
         ``keep_duplicates=True`` keeps the duplicate triangles of the clustering (``surface.simplify_meshes``): with ``close_border=True``
         the simplified mesh then stays a cycle, which ``RayGrid.contains`` / ``signed_distance`` need for an inside test.
+        ``placement="quadric"`` (``surface.simplify_meshes``; it needs ``simplify``): the clusters' vertices move from the mean to the
+        minimum of their quadrics (``pr_mesh_place``), which keeps edges and corners; ``features`` are queried AFTER the placement, as
+        after welding and smoothing.  A placed vertex can leave the lattice hull by up to a cluster cell (a capped surface at the box), so
+        with this placement the query points are clamped to the hull; the vertices are not.  At ``"mean"`` (the default) nothing changes.
 
         ``weld=True``: ``surface.extract_surface``'s - the meshes are welded (``surface.weld_meshes``: one vertex per value, no
         unreferenced vertex, no dropped triangle) after the simplification and BEFORE the feature query, so ``features`` are
@@ -990,13 +994,15 @@ class ObjectComposer(Tracked, nn.Module):
         axes = self._grid_axes(object_idx, list(sigma.shape[1:]), fine, sigma.device)
         meshes = _surface.extract_surface(sigma, axes, level, normals=normals, keep_largest=keep_largest, min_points=min_points,
                                           close_border=close_border, simplify=simplify, keep_duplicates=keep_duplicates,
-                                          weld=weld, smooth=smooth)
+                                          weld=weld, smooth=smooth, placement=placement)
         if features:
             # one query: the groups padded to the largest one (at least one row) with a lattice point, which is inside the box
             G, most = len(meshes), max(1, max(m.vertices.size(0) for m in meshes))
             points = torch.stack([axes[0][0], axes[1][0], axes[2][0]]).expand(G, most, 3).clone()
             for g, m in enumerate(meshes):
                 points[g, :m.vertices.size(0)] = m.vertices
+            if placement != "mean":
+                points = torch.maximum(torch.minimum(points, torch.stack([a[-1] for a in axes])), torch.stack([a[0] for a in axes]))
             out = self.query_object(object_idx, points, style, deformation, fine=fine, canonical_pose=canonical_pose)["features"]
             for g, m in enumerate(meshes):
                 m.features = out[g, :m.vertices.size(0)]

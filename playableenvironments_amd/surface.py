@@ -16,6 +16,8 @@ around the level set - the opt-in approximation behind ``ObjectComposer.density_
 
 ``simplify_meshes`` / ``Mesh.simplified`` (``pr_simplify_mesh``) reduce extracted meshes by vertex clustering on a uniform grid, on
 the device and independent of the execution order - what ``extract_surface(simplify=k)`` and ``extract_mesh(simplify=k)`` apply.
+``placement="quadric"`` / ``place_vertices`` (``pr_mesh_place``) then move every cluster's vertex from the mean of its members to the
+point that the planes of its triangles ask for: edges and corners stay sharp, and most of the volume that the mean loses is kept.
 
 ``RayGrid`` / ``Mesh.ray_grid`` (``pr_raycast_build`` / ``pr_raycast_query``) answer closest-hit ray queries against such meshes on a
 uniform cell grid: ``RayGrid.build(meshes, *bounding_grid(meshes, 32)).cast(origins, directions)``.  ``RayGrid.closest``
@@ -571,14 +573,17 @@ def lattice_cluster_grid(axes: Sequence, k: int):
     return origin, cell, cells
 
 
-def _simplify_packed(p: _PackedMeshes, origin, cell, cells, keep_duplicates):
+def _simplify_packed(p: _PackedMeshes, origin, cell, cells, keep_duplicates, placement: str = "mean"):
     """``pr_simplify_mesh`` on packed meshes: a counting call, one read-back of the two offset arrays, an exactly sized emitting
-    call.  Returns the list of meshes."""
+    call.  ``placement="quadric"``: the emitting call also writes its vertex map and ONE ``pr_mesh_place`` call follows on the same
+    stream, with ``scale = max(cell)`` and ``max_move = cell`` - nothing more is read back.  Returns the list of meshes."""
     dev, G = p.vertices.device, p.groups
+    quadric = _placement(placement)
     with torch.cuda.device(dev):
         offsets = torch.empty((2, G + 1), dtype=torch.int32, device=dev)
         counts = torch.empty((G, 4), dtype=torch.int32, device=dev)
-        common = (*p.arguments(), origin, cell, cells, counts, offsets[0], offsets[1])
+        mesh = p.arguments()
+        common = (*mesh, origin, cell, cells, counts, offsets[0], offsets[1])
         count = simplify_struct(*common, normals=p.normals, keep_duplicates=keep_duplicates)
         workspace, size = _call_with_workspace("pr_simplify_workspace_size", "pr_simplify_mesh", count, dev)
         out_vo, out_to = offsets.cpu().tolist()                             # (the host synchronisation)
@@ -586,28 +591,134 @@ def _simplify_packed(p: _PackedMeshes, origin, cell, cells, keep_duplicates):
         out_n = None if p.normals is None else torch.empty((out_vo[G], 3), dtype=torch.float32, device=dev)
         out_t = torch.empty((out_to[G], 3), dtype=torch.int32, device=dev)
         if out_vo[G] > 0:
+            vertex_map = torch.empty(p.V, dtype=torch.int32, device=dev) if quadric else None
             emit = simplify_struct(*common, normals=p.normals, out_vertices=out_v, out_normals=out_n,
-                                   out_triangles=out_t if out_to[G] > 0 else None, keep_duplicates=keep_duplicates)
+                                   out_triangles=out_t if out_to[G] > 0 else None, vertex_map=vertex_map,
+                                   keep_duplicates=keep_duplicates)
             _call("pr_simplify_mesh", emit, workspace, size, dev)
+            if quadric:
+                placed = torch.empty_like(out_v)
+                s = place_struct(*mesh, vertex_map, out_v, offsets[0], out_vo[G], placed,
+                                 torch.empty((G, _lib.PLACE_COUNTS), dtype=torch.int32, device=dev), scale=max(cell), max_move=cell,
+                                 merged_triangles=out_t if out_to[G] > 0 else None,
+                                 merged_triangle_offsets=offsets[1] if out_to[G] > 0 else None, total_merged_triangles=out_to[G])
+                _call_with_workspace("pr_mesh_place_workspace_size", "pr_mesh_place", s, dev)
+                out_v = placed
     return [Mesh(out_v[out_vo[g]:out_vo[g + 1]], out_t[out_to[g]:out_to[g + 1]], None if out_n is None else out_n[out_vo[g]:out_vo[g + 1]])
             for g in range(G)]
 
 
-def simplify_meshes(meshes: Sequence[Mesh], origin, cell, cells, *, keep_duplicates: bool = False) -> List[Mesh]:
+PLACEMENTS = ("mean", "quadric")
+PLACE_REGULARISATION = 2.0 ** -10
+
+
+def _placement(placement) -> bool:
+    """Whether ``placement`` asks for the quadric rule; anything but the two names raises."""
+    if placement not in PLACEMENTS:
+        raise ValueError(f"placement must be one of {PLACEMENTS}, got {placement!r}")
+    return placement == "quadric"
+
+
+def simplify_meshes(meshes: Sequence[Mesh], origin, cell, cells, *, keep_duplicates: bool = False, placement: str = "mean") -> List[Mesh]:
     """The meshes simplified by vertex clustering on one uniform grid (``pr_simplify_mesh``, include/playrender.h): the grid has
     ``cells[a]`` cells of size ``cell[a]`` from ``origin[a]`` on along every axis (at most 2^21 cells); a vertex outside it goes to the
     nearest border cell.  All vertices of a cell become one vertex at their mean (normals: the normalised sum), triangles that lose a
     corner that way disappear, and of the triangles that end up with the same corners in the same orientation only the first stays
     (``keep_duplicates=True``: all stay).  The result is fixed by the rule - integer sums, no dependence on the execution order.
 
+    ``placement="quadric"``: every cluster's vertex then moves from the mean to the point that minimises the area-weighted squared
+    distance to the planes of the input triangles that touch the cluster (``pr_mesh_place`` with ``scale = max(cell)``,
+    ``max_move = cell``, ``regularisation = 2^-10``; ``place_vertices`` is the call on its own): convex edges and corners stay where
+    the surface has them instead of being pulled inwards.  One more call on the same stream, no further read-back; the triangle lists
+    are the mean rule's, bit for bit, so edge balance and what ``contains`` and ``audit`` say of a ``keep_duplicates=True`` mesh hold.
+    A few sliver triangles can turn over (``place_vertices`` counts them).  The normals stay the simplifier's normalised sums:
+    ``Mesh.vertex_normals()`` recomputes them from the placed triangles.  ``"mean"`` (the default) is the call as it always was.
+
     The meshes are packed, counted, and - after reading the two offset arrays back, the ONE host synchronisation - emitted into
     exactly sized tensors.  Returns one mesh per input; they have normals iff every input has them; ``features`` are not carried
     over.  There is no CPU fallback."""
     meshes = _listed(meshes, "simplify_meshes")
+    _placement(placement)
     dev = _device_of(meshes)
     origin, cell, cells = _cluster_grid(origin, cell, cells)
     p = _pack_meshes(meshes, dev, normals=all(m.normals is not None for m in meshes))
-    return _simplify_packed(p, origin, cell, cells, keep_duplicates)
+    return _simplify_packed(p, origin, cell, cells, keep_duplicates, placement)
+
+
+def place_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offsets: torch.Tensor, triangle_offsets: torch.Tensor,
+                 total_vertices: int, total_triangles: int, vertex_map: torch.Tensor, merged_vertices: torch.Tensor,
+                 merged_vertex_offsets: torch.Tensor, total_merged_vertices: int, out_vertices: torch.Tensor, counts: torch.Tensor, *,
+                 scale: float, max_move, regularisation: float = PLACE_REGULARISATION, merged_triangles: Optional[torch.Tensor] = None,
+                 merged_triangle_offsets: Optional[torch.Tensor] = None, total_merged_triangles: int = 0) -> _lib.MeshPlace:
+    """``pr_mesh_place_t`` over prepared tensors (fp32 / int32, contiguous, one device)."""
+    s = _lib.MeshPlace()
+    _set_mesh_header(s, vertex_offsets, total_vertices, total_triangles)
+    s.total_merged_vertices = int(total_merged_vertices)
+    s.total_merged_triangles = int(total_merged_triangles)
+    s.scale = float(scale)
+    s.regularisation = float(regularisation)
+    for a in range(3):
+        s.max_move[a] = float(max_move[a])
+    return _set_pointers(s, vertices=vertices, triangles=triangles, vertex_offsets=vertex_offsets, triangle_offsets=triangle_offsets,
+                         vertex_map=vertex_map, merged_vertices=merged_vertices, merged_vertex_offsets=merged_vertex_offsets,
+                         merged_triangles=merged_triangles, merged_triangle_offsets=merged_triangle_offsets, out_vertices=out_vertices,
+                         counts=counts)
+
+
+def _place_arguments(scale, max_move, regularisation):
+    """``(scale, max_move, regularisation)`` checked as ``pr_mesh_place`` checks them."""
+    try:
+        scale, regularisation = float(scale), float(regularisation)
+        max_move = [float(max_move)] * 3 if isinstance(max_move, (int, float)) else [float(x) for x in max_move]
+    except TypeError:
+        raise ValueError("scale and regularisation must be numbers, max_move one number or three") from None
+    if not (math.isfinite(scale) and scale > 0):
+        raise ValueError(f"scale must be finite and > 0, got {scale}")
+    if not (math.isfinite(regularisation) and regularisation > 0):
+        raise ValueError(f"regularisation must be finite and > 0, got {regularisation}")
+    if len(max_move) != 3 or not all(math.isfinite(x) and x >= 0 for x in max_move):
+        raise ValueError(f"max_move must be one or three finite numbers >= 0, got {max_move}")
+    return scale, max_move, regularisation
+
+
+def place_vertices(meshes: Sequence[Mesh], merged: Sequence[Mesh], vertex_maps, *, scale: float, max_move,
+                   regularisation: float = PLACE_REGULARISATION):
+    """The ``merged`` meshes - each a coarser version of the mesh of ``meshes`` at the same place, with ``vertex_maps[g] (V_g)`` the
+    merged vertex of every vertex of ``meshes[g]`` (``pr_simplify_mesh``'s vertex map, ``weld_meshes(maps=True)``'s) - with every vertex
+    moved to the minimum of its cluster's quadric (``pr_mesh_place``, include/playrender.h): the area-weighted squared distance to the
+    planes of the triangles of ``meshes[g]`` with a corner in the cluster, plus ``regularisation`` times the mean diagonal of the
+    quadric as a pull toward the stored position.  ``scale``: the unit of length in which the sums are taken, about a cluster's size
+    (``max(cell)``); ``max_move``: one number or three, the largest move per axis - a vertex that would go further, or whose system
+    cannot be solved, stays bit for bit.  Integer sums: the result does not depend on the execution order.
+
+    Returns ``(meshes, counts)``: the merged meshes with new vertices - triangles shared, normals and features carried as they are -
+    and the ``(G, 4)`` int32 counts on the device: vertices moved, vertices kept, contributions skipped plus invalid triangles,
+    merged triangles that the move turned over.  One call, no host synchronisation.  There is no CPU fallback."""
+    meshes, merged = _listed(meshes, "place_vertices"), list(merged)
+    vertex_maps = list(vertex_maps)
+    if not len(meshes) == len(merged) == len(vertex_maps):
+        raise ValueError(f"place_vertices needs one merged mesh and one vertex map per mesh, got {len(meshes)} / {len(merged)} / {len(vertex_maps)}")
+    scale, max_move, regularisation = _place_arguments(scale, max_move, regularisation)
+    for m, vmap in zip(meshes, vertex_maps):
+        if vmap.numel() != m.vertices.size(0):
+            raise ValueError(f"a vertex map must have one entry per vertex of its mesh ({m.vertices.size(0)}), got {vmap.numel()}")
+    dev = _device_of(meshes + merged)
+    if not all(vmap.is_cuda for vmap in vertex_maps):
+        raise RuntimeError(NO_CPU)
+    fine, coarse = _pack_meshes(meshes, dev), _pack_meshes(merged, dev)
+    G, VO, TO = fine.groups, coarse.V, coarse.T
+    with torch.cuda.device(dev):
+        vertex_map = torch.cat([vmap.detach().to(device=dev, dtype=torch.int32).reshape(-1) for vmap in vertex_maps]).contiguous()
+        if fine.V == 0:
+            vertex_map = torch.empty(1, dtype=torch.int32, device=dev)      # (the placeholder rule of _packed)
+        merged_offsets = torch.tensor([coarse.vo, coarse.to], dtype=torch.int32).to(dev)
+        out = torch.empty((max(VO, 1), 3), dtype=torch.float32, device=dev)
+        counts = torch.empty((G, _lib.PLACE_COUNTS), dtype=torch.int32, device=dev)
+        s = place_struct(*fine.arguments(), vertex_map, coarse.vertices, merged_offsets[0], VO, out, counts, scale=scale, max_move=max_move,
+                         regularisation=regularisation, merged_triangles=coarse.triangles, merged_triangle_offsets=merged_offsets[1],
+                         total_merged_triangles=TO)
+        _call_with_workspace("pr_mesh_place_workspace_size", "pr_mesh_place", s, dev)
+    return [Mesh(out[coarse.vo[g]:coarse.vo[g + 1]], m.triangles, m.normals, m.features) for g, m in enumerate(merged)], counts
 
 
 def raycast_struct(vertices: torch.Tensor, triangles: torch.Tensor, vertex_offsets: torch.Tensor, triangle_offsets: torch.Tensor,
@@ -1614,7 +1725,7 @@ def bounding_grid(meshes: Sequence[Mesh], cells):
 
 def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: float, *, normals: bool = True, keep_largest: int = 0,
                     min_points: int = 0, close_border: bool = False, simplify: int = 0, keep_duplicates: bool = False,
-                    weld: bool = False, smooth: int = 0) -> List[Mesh]:
+                    weld: bool = False, smooth: int = 0, placement: str = "mean") -> List[Mesh]:
     """Meshes of the level set ``sigma = level`` of ``sigma (G, nx, ny, nz)`` (device tensor, z fastest - what ``density_grid``
     returns); ``axes``: the coordinates of the lattice points along x, y, z (``nx``, ``ny``, ``nz`` values).  Returns G meshes.
 
@@ -1629,7 +1740,9 @@ def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: fl
     ``k`` lattice steps (``lattice_cluster_grid``) - evaluate the field finely, keep a mesh of a coarser lattice's size.  Two more
     read-backs (the ends of the axes, the simplified sizes).  At 0 (the default) nothing changes.  ``keep_duplicates`` is
     ``simplify_meshes``'s: duplicate triangles stay, so that every directed edge keeps its partner - what ``RayGrid.winding`` /
-    ``contains`` need of a simplified mesh.
+    ``contains`` need of a simplified mesh.  ``placement`` is ``simplify_meshes``'s too: ``"quadric"`` moves the clusters' vertices from
+    the mean onto the edges and corners that their triangles' planes meet in (no further read-back); it means nothing without
+    ``simplify``.
 
     ``weld=True``: the meshes - after the simplification, if any - go through ``weld_meshes``: one vertex per value, no unreferenced
     vertex, no dropped triangle.  One more read-back.  At False (the default) nothing changes.
@@ -1655,9 +1768,11 @@ def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: fl
         raise ValueError(f"smooth must be an integer >= 0, got {smooth!r}") from None
     if smooth < 0 or 2 * smooth > _lib.SMOOTH_MAX_STEPS:
         raise ValueError(f"smooth must be an integer in 0 .. {_lib.SMOOTH_MAX_STEPS // 2}, got {smooth}")
+    _placement(placement)
     if smooth:
         meshes = extract_surface(sigma, axes, level, normals=normals, keep_largest=keep_largest, min_points=min_points,
-                                 close_border=close_border, simplify=simplify, keep_duplicates=keep_duplicates, weld=True)
+                                 close_border=close_border, simplify=simplify, keep_duplicates=keep_duplicates, weld=True,
+                                 placement=placement)
         return smooth_meshes(meshes, iterations=smooth, weld=False, normals=bool(normals))
     dev = sigma.device
     sigma = sigma.detach().to(torch.float32).contiguous()
@@ -1682,7 +1797,8 @@ def extract_surface(sigma: torch.Tensor, axes: Sequence[torch.Tensor], level: fl
             _call("pr_extract_surface", emit, workspace, size, dev)
     if simplify:                                                   # (the mesher's output is packed already: no Mesh objects in between)
         grid = _cluster_grid(*lattice_cluster_grid(axes, simplify))
-        meshes = _simplify_packed(_packed(vertices, triangles, vertex_offsets, triangle_offsets, vertex_normals), *grid, bool(keep_duplicates))
+        meshes = _simplify_packed(_packed(vertices, triangles, vertex_offsets, triangle_offsets, vertex_normals), *grid, bool(keep_duplicates),
+                                  placement)
         return weld_meshes(meshes) if weld else meshes
     if weld:
         return _weld_packed(_packed(vertices, triangles, vertex_offsets, triangle_offsets, vertex_normals), True, False)[0]
